@@ -2,7 +2,7 @@
 """Headline benchmark: drug-pair x outcome scores/sec for all-pairs scoring (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--drugs 4096] [--outcomes 896]
-                    [--config twosides321] [--precision bf16x3] [--head-only]
+                    [--config twosides321] [--precision bf16x3] [--head-only] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one synthetic drug set, inputs resident in HBM:
     encode + fuse every drug (GIN structure encoder, HGT over the whole KG, cv MLP, chemCPA tx encoder,
@@ -17,12 +17,17 @@ exchange step), then the head is sharded by outcome:
   --scaling strong (default) = BASELINE configs[3] as named: the FIXED job `--drugs`^2 x `--outcomes` split over the
       ranks (896 / 8 = 112 outcomes per GPU), every rank writing its own slab of the score tensor;
   --scaling weak: every rank scores its own `--outcomes` outcomes (global outcomes = outcomes x n_gpus).
-At N > 1 the line of the default mode also carries the other mode's numbers under "weak_scaling".  Rank 0 prints ONE
+At N > 1 the line of the default mode also carries (--full) the other mode's numbers under "weak_scaling".  Rank 0 prints ONE
 JSON line; it states the world size RCCL saw and a checksum of the all-gathered embeddings.
 
-Also in the line (N = 1 unless noted): "roofline_cfg5" -- BASELINE configs[4], 100 352 drugs x 1 024 outcomes = 1.03e13
-scores through the fp16 head with the row-statistics epilogue (nothing materialised), priced against the dense 16-bit
-MFMA peak (outcome-sharded over the ranks at N > 1); "finetune" -- DDI-finetune steps/s; "ranks" -- the rank normalisation
+A plain run sets up, warms up, times the K steps and prints the line: value = scores/s, ms_per_step = one timed step.
+`--dump-outputs DIR` then writes what the last timed step computed (DIR/embeddings.npy: z [N,128]; DIR/scores_sample.npy:
+a fixed, seeded sample of the score tensor) as float32 .npy files; the inputs are seeded, so two builds compare output for output.
+
+With --full the line also carries (N = 1 unless noted): "f32_exact" -- the exact-fp32 head beside the headline's mode;
+"cpu_baseline" -- the CPU oracle on a sample of the same job; the other scaling mode at N > 1 (above); "roofline_cfg5" --
+BASELINE configs[4], 100 352 drugs x 1 024 outcomes = 1.03e13 scores through the fp16 head with the row-statistics epilogue
+(nothing materialised), priced against the dense 16-bit MFMA peak (outcome-sharded over the ranks at N > 1); "finetune" -- DDI-finetune steps/s; "ranks" -- the rank normalisation
 of the score tensor the headline just produced (notebooks/normalize_scores.py) and the 5-seed ensembling on a subset;
 "pretrain" -- contrastive-pretraining steps/s.
 
@@ -49,6 +54,22 @@ BYTES_PER_SCORE = 4.0          # fp32 score stored
 # one drug set on both sides (the all-pairs job): the symmetric sweep
 HEAD_KERNEL = {"f32": "bilinear_allpairs_sym_kernel<0, 0, 8, 0>", "bf16x3": "bilinear_allpairs_sym_kernel<1, 0, 8, 1>",
                "bf16": "bilinear_allpairs_sym_kernel<2, 0, 8, 0>", "f16": "bilinear_allpairs_sym_kernel<3, 0, 8, 0>"}
+
+
+DUMP_SAMPLE = 4_000_000        # score entries in scores_sample.npy (16 MB of float32; the [L,N,N] tensor is 60 GB)
+
+
+def dump_outputs(outdir: str, scores, z) -> None:
+    """What a caller of the timed path receives, as float32 .npy: the embeddings z [N,128] whole, and the score tensor at
+    DUMP_SAMPLE entries drawn on the host from a fixed seed (the same entries for every build at the same shape)."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    L, N, M = scores.shape
+    g = torch.Generator().manual_seed(2024)
+    idx = [torch.randint(0, n, (DUMP_SAMPLE,), generator=g).to(scores.device) for n in (L, N, M)]
+    np.save(os.path.join(outdir, "scores_sample.npy"), scores[idx[0], idx[1], idx[2]].float().cpu().numpy())
+    np.save(os.path.join(outdir, "embeddings.npy"), z.float().cpu().numpy())
 
 
 def stress_leg(args, rank, world, dev, backend):
@@ -777,7 +798,12 @@ def main():
                     "headline produced; -1 = all of them, 0 = skip")
     ap.add_argument("--finetune-triples", type=int, default=1_000_000, help="positive triples; with 2 negatives each and both "
                     "directions (the reference's collation) 6x as many labelled triples per step")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: exact-fp32 head, ranks, finetune, "
+                    "pretraining, cfg5 row statistics, CPU baselines, the other scaling mode at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: be the launcher.  This process has not touched the GPU (torch is not even imported yet) and never will:
@@ -829,12 +855,13 @@ def main():
         batch, bkg = D.make_batch(N, 0, kg_nodes=args.kg_nodes, kg_edges=args.kg_edges)
         torch.manual_seed(1234)                       # identical encoder weights on every rank
         model = configs.build_model(args.config, bkg["data"], L).to(dev).eval()
-        cpu_inputs = ({k: v.detach().cpu() for k, v in model.state_dict().items()}, batch, bkg, args.config) if (world == 1 and not args.no_cpu_baseline) else None
+        cpu_inputs = ({k: v.detach().cpu() for k, v in model.state_dict().items()}, batch, bkg, args.config) if (
+            args.full and world == 1 and not args.no_cpu_baseline) else None
         batch = D.batch_to(batch, dev)
         bkg = {"data": bkg["data"].to(dev), "drug_index_map": bkg["drug_index_map"].to(dev)}
         filler = torch.randn(N, 128, device=dev, generator=torch.Generator(device=dev).manual_seed(5))   # drugs absent from the KG (always masked)
 
-    def headline(mode: str, keep_scores: bool = False) -> dict:
+    def headline(mode: str, keep_scores: bool = False, dump: str | None = None) -> dict:
         """K timed steps of the whole job in one sharding mode -> timings of this rank (+ max over ranks)."""
         if mode == "strong":                          # ONE model of L outcomes, rank r scores outcomes [lo_l, hi_l)
             lo_l, hi_l = (rank * L) // world, ((rank + 1) * L) // world
@@ -917,6 +944,8 @@ def main():
                "enc_ms": mean(0, 2),                          # encode+fuse incl. the exchange step
                "head_ms": mean(2, 3),                         # head launch (+ its two operand-split pre-passes)
                "phases_ms_per_rank": {"columns": ["encode_fuse_own_block", "all_gather_z", "head_own_outcomes"], "rows": per_rank}}
+        if dump and rank == 0:
+            dump_outputs(dump, out, z)
         if keep_scores:
             res["scores"] = out
             res["z"] = z
@@ -926,9 +955,9 @@ def main():
         return res
 
     main_mode = args.scaling if world > 1 else "strong"
-    want_ranks = world == 1 and args.rank_outcomes != 0
-    want_exact = world == 1 and not args.head_only and args.precision != "f32" and not args.no_f32_exact
-    h = headline(main_mode, keep_scores=want_ranks or want_exact)
+    want_ranks = args.full and world == 1 and args.rank_outcomes != 0
+    want_exact = args.full and world == 1 and not args.head_only and args.precision != "f32" and not args.no_f32_exact
+    h = headline(main_mode, keep_scores=want_ranks or want_exact, dump=args.dump_outputs)
     f32_exact = None
     if want_exact:
         try:
@@ -945,7 +974,7 @@ def main():
         h.pop("scores", None)
         h.pop("z", None)
         torch.cuda.empty_cache()
-    other = headline("weak" if main_mode == "strong" else "strong") if world > 1 else None
+    other = headline("weak" if main_mode == "strong" else "strong") if (args.full and world > 1) else None
 
     def secondary_legs():
         """Finetune / pretraining / cfg5 legs -> (finetune, pretrain, stress) blocks (each survives its own failure)."""
@@ -1037,7 +1066,7 @@ def main():
             line["f32_exact"] = f32_exact
         if stress is not None:
             line["roofline_cfg5"] = stress
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, L, encode=cpu_inputs)
         line["phases_ms_per_rank"] = h["phases_ms_per_rank"]
         if ranks is not None:
@@ -1068,7 +1097,7 @@ def main():
                            "cpu_scores_per_s": pick(line.get("cpu_baseline"), "value")}
         print(json.dumps(line), flush=True)
     if world == 1:
-        emit(*secondary_legs())
+        emit(*(secondary_legs() if args.full else (None, None, None)))
     else:
         # N > 1: the line (the scaling curve's point) leaves FIRST.  The data-parallel finetune step and the sharded cfg5 stress run
         # have never executed over RCCL (one GPU in the build box): they are OPT-IN there (--ddp-legs / MDG_BENCH_DDP_LEGS=1), run after

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Copy the rocprofv3 summaries of a gpurun_out/<dir> (kt = --kernel-trace --stats, pmc_w / pmc_r = WRITE_SIZE /
-FETCH_SIZE passes of `bench.py`) into profiles/ under a round tag.   python scripts/collect_profiles.py prof3 r01"""
+"""Copy the rocprofv3 summaries that scripts/profile_bench.sh wrote under $PROFILE_ROOT/<dir> (default profile_out/<dir>; kt =
+--kernel-trace --stats, pmc_w / pmc_r = WRITE_SIZE / FETCH_SIZE passes of `bench.py`) into profiles/ under a round tag.
+    python scripts/collect_profiles.py prof3 r01"""
 import collections, csv, glob, json, os, shutil, sys
 src, tag = sys.argv[1], sys.argv[2]
-root = os.path.join("gpurun_out", src)
+root = os.path.join(os.environ.get("PROFILE_ROOT", "profile_out"), src)
 os.makedirs("profiles", exist_ok=True)
 shutil.copy(glob.glob(f"{root}/kt/*/*_kernel_stats.csv")[0], f"profiles/{tag}_bench_wholejob_bf16x3_kernel_stats.csv")
 # (the kernel-trace run is the FULL default bench command: inference headline + finetune legs + cfg5 row statistics)
