@@ -112,6 +112,22 @@ int mdg_bilinear_allpairs_ld(const float* z_head, const float* z_tail, const flo
                              int64_t n_tail, int64_t n_labels, int64_t D, int precision, int epilogue, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* Checkpoint ensemble of the all-pairs head: out[l,i,j] = mean_k sigmoid(z_head_k[i]^T W_sym_k[l] z_tail_k[j]).
+ * Replaces get_twosides_scores_wrapper / get_drugbank_scores_wrapper, madrigal/evaluate/predict.py:466-499, 582-614.
+ * z_head_host / z_tail_host / w_sym_host: HOST arrays of n_models (1..8) device pointers, model k's z_head [n_head,D],
+ * z_tail [n_tail,D] and W_sym [n_labels,D,D] (already symmetrised), D == 128, 16-byte aligned.  out[(l * n_head + i) * ldo + j],
+ * ldo >= n_tail, fp32, the layout of mdg_bilinear_allpairs_ld.  Per model the logit is the head's own arithmetic in `precision`
+ * (MDG_PREC_F32 or MDG_PREC_BF16X3); each sigmoid is 1 / (1 + expf(-s)); the K sigmoids are summed in fp32 in model order and
+ * divided once by K.  When z_head_k == z_tail_k for every k (one drug set against itself) only the tiles on / right of the
+ * block diagonal are computed and mirrored: out[l] is then exactly symmetric.  Workspace: split-bf16 images of every model's
+ * z_tail and W_sym (0 for F32). */
+size_t mdg_bilinear_ensemble_sigmoid_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D,
+                                                     int n_models, int precision);
+int mdg_bilinear_ensemble_sigmoid(const float* const* z_head_host, const float* const* z_tail_host,
+                                  const float* const* w_sym_host, int n_models, float* out, int64_t ldo,
+                                  int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ dense blocks ---- */
 
 /* Y = alpha * act( (X W^T + bias) * scale + shift ) + beta * R      X [M,K] ldx, W [N,K] ldw (nn.Linear

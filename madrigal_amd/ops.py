@@ -136,6 +136,58 @@ def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
     return out
 
 
+ENSEMBLE_PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}
+
+
+def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Checkpoint ensemble of the all-pairs head: P[l,i,j] = mean_k sigmoid(z_heads[k][i]^T w_syms[k][l] z_tails[k][j]) -> [L,Nh,Nt]
+    fp32 (madrigal/evaluate/predict.py:466-499, 582-614), K = len(z_heads) in 1..8, one launch.  Per model the logit is
+    ``bilinear_allpairs``'s own arithmetic in ``precision`` ("f32" or "bf16x3"); the sigmoids are summed in model order and divided
+    once by K.  When ``z_heads[k] is z_tails[k]`` for every k (one drug set against itself) the symmetric sweep runs and every
+    P[l] is exactly symmetric.  ``out``: None (an ``empty_scores`` tensor) or a contiguous / row-pitched fp32 GPU tensor."""
+    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
+    K = len(zh)
+    if not 1 <= K <= 8:
+        raise ValueError(f"bilinear_ensemble_sigmoid: 1..8 models, got {K}")
+    if len(zt) != K or len(ws) != K:
+        raise ValueError(f"bilinear_ensemble_sigmoid: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
+    if precision not in ENSEMBLE_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
+    sym = all(a is b for a, b in zip(zh, zt))
+    zh = [_f32_cuda(t, f"z_heads[{k}]", 2) for k, t in enumerate(zh)]
+    zt = zh if sym else [_f32_cuda(t, f"z_tails[{k}]", 2) for k, t in enumerate(zt)]
+    ws = [_f32_cuda(t, f"w_syms[{k}]", 3) for k, t in enumerate(ws)]
+    L, D = ws[0].shape[0], ws[0].shape[1]
+    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
+    dev = zh[0].device
+    for k in range(K):
+        if zh[k].shape != (Nh, D) or zt[k].shape != (Nt, D) or ws[k].shape != (L, D, D):
+            raise ValueError(f"bilinear_ensemble_sigmoid: model {k} has z_head {tuple(zh[k].shape)}, z_tail {tuple(zt[k].shape)}, "
+                             f"w_sym {tuple(ws[k].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+        if zh[k].device != dev or zt[k].device != dev or ws[k].device != dev:
+            raise ValueError("bilinear_ensemble_sigmoid: every tensor must be on the same device")
+    shape = (L, Nh, Nt)
+    if out is None:
+        out = empty_scores(L, Nh, Nt, dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+              and (out.numel() == 0 or (out.stride(2) == 1 and out.stride(1) >= Nt and out.stride(0) == Nh * out.stride(1)))):
+        raise ValueError(f"out: expected a float32 GPU tensor {shape}, contiguous or row-pitched (empty_scores)")
+    ldo = out.stride(1) if out.numel() else Nt
+    prec = ENSEMBLE_PRECISIONS[precision]
+    L_ = lib()
+    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
+    a_h, a_t = arr(zh), arr(zt)
+    for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
+        hi = min(L, lo + 65535)
+        nbytes = L_.mdg_bilinear_ensemble_sigmoid_workspace_bytes(_c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), ctypes.c_int(K), prec)
+        wsp = _workspace(nbytes, dev)
+        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
+        check(L_.mdg_bilinear_ensemble_sigmoid(a_h, a_t, a_w, ctypes.c_int(K), _vp(out.data_ptr() + lo * out.stride(0) * 4), _c64(ldo),
+                                               _c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec, _ptr(wsp), ctypes.c_size_t(nbytes),
+                                               _stream(zh[0])), "mdg_bilinear_ensemble_sigmoid")
+    return out
+
+
 def empty_scores(L: int, Nh: int, Nt: int, device) -> torch.Tensor:
     """An uninitialised [L,Nh,Nt] fp32 score (or rank) tensor in the layout the head writes fastest: rows padded to a multiple of
     32 floats, so that every row starts on a 128-byte line whatever Nt is (the real drug counts -- 11 607 in

@@ -170,3 +170,95 @@ def rank_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int]
         return out
     keys = dec(z, z, (lo, hi), epilogue=ops.EPI_TRIKEYS, out=out.view(torch.int32))
     return ops.rank_normalize(keys, max_workspace_bytes=max_workspace_bytes)
+
+
+def _ensemble_weight(m) -> torch.Tensor:
+    """W_sym [L,128,128] of one checkpoint: a NovelDDIMultilabel, its BilinearDDIScorer, or an original [L,D,D] weight."""
+    if isinstance(m, torch.Tensor):
+        if m.dim() != 3 or m.shape[1] != m.shape[2]:
+            raise ValueError(f"models: a weight must be [L,D,D], got {tuple(m.shape)}")
+        return ops.symmetrize(m.detach())
+    dec = getattr(m, "decoder", m)
+    if not hasattr(dec, "symmetric_weight"):
+        raise ValueError(f"models: expected NovelDDIMultilabel, BilinearDDIScorer or an [L,D,D] weight, got {type(m).__name__}")
+    return dec.symmetric_weight()
+
+
+def _index(inds, n: int, name: str, device) -> Optional[torch.Tensor]:
+    if inds is None:
+        return None
+    t = torch.as_tensor(np.asarray(inds, dtype=np.int64) if not isinstance(inds, torch.Tensor) else inds).long().reshape(-1)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+        raise ValueError(f"{name}: indices must lie in [0, {n}), got [{int(t.min())}, {int(t.max())}]")
+    return t.to(device)
+
+
+@torch.no_grad()
+def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_inds=None, out=None, host_chunk: int = 16):
+    """Mean interaction probability over checkpoints for every drug pair: P[o, a, b] = mean_k sigmoid(S_k[outcome_inds[o],
+    drug_inds[a], drug_2_inds[b]]) -> [O, A, B] fp32, in one sweep of ``ops.bilinear_ensemble_sigmoid``.  Replaces
+    get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614), which write K raw-score
+    memmaps and stack, sigmoid and average them on the host.
+
+    ``models[k]``: checkpoint k's NovelDDIMultilabel, its BilinearDDIScorer or its original [L,128,128] head weight (symmetrised
+    here); ``zs[k]``: checkpoint k's [N,128] embeddings (all_drug_embeddings_full_{epoch}.pt).  ``drug_inds`` / ``drug_2_inds`` /
+    ``outcome_inds``: any index lists (unsorted, repeated) -- gathers of z rows and W_sym outcomes before the sweep.
+    ``drug_2_inds=None`` is the same drug set on both sides: the symmetric sweep, P[o] exactly symmetric.  Precision follows
+    ``models.precision(...)`` as the single-model head does.
+
+    ``out``: None / a CUDA tensor (one launch into HBM) or a numpy array / ``np.memmap`` (outcome chunks of ``host_chunk`` streamed
+    through two pinned buffers, as ``score_all_pairs`` does).  Multi-GPU: give each rank its slice of ``outcome_inds``; the slices
+    are independent and no collective is involved."""
+    from .models import get_precision
+    K = len(models)
+    if not 1 <= K <= 8 or len(zs) != K:
+        raise ValueError(f"ensemble_all_pairs: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
+    z0 = zs[0]
+    if not (isinstance(z0, torch.Tensor) and z0.is_cuda):
+        raise ValueError("zs: embeddings must be GPU tensors")
+    N, dev = z0.shape[0], z0.device
+    ws = [_ensemble_weight(m) for m in models]
+    L_all = ws[0].shape[0]
+    oi = _index(outcome_inds, L_all, "outcome_inds", dev)
+    di = _index(drug_inds, N, "drug_inds", dev)
+    d2 = _index(drug_2_inds, N, "drug_2_inds", dev)
+    for k in range(K):
+        if zs[k].shape != z0.shape or ws[k].shape[0] != L_all:
+            raise ValueError(f"ensemble_all_pairs: checkpoint {k} has z {tuple(zs[k].shape)} and {ws[k].shape[0]} outcomes; "
+                             f"checkpoint 0 has {tuple(z0.shape)} and {L_all}")
+    heads = [z if di is None else z.index_select(0, di) for z in zs]
+    tails = heads if d2 is None else [z.index_select(0, d2) for z in zs]
+    wsel = ws if oi is None else [w.index_select(0, oi) for w in ws]
+    prec = get_precision()
+    L, A, B = wsel[0].shape[0], heads[0].shape[0], tails[0].shape[0]
+    if out is None or isinstance(out, torch.Tensor):
+        return ops.bilinear_ensemble_sigmoid(heads, tails, wsel, precision=prec, out=out)
+    if tuple(out.shape) != (L, A, B) or out.dtype != np.float32:
+        raise ValueError(f"out: expected float32 array of shape {(L, A, B)}")
+    copy_stream = torch.cuda.Stream(device=dev)
+    dev_buf = [ops.empty_scores(host_chunk, A, B, dev) for _ in range(2)]
+    pin_buf = [torch.empty((host_chunk, A, B), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+    done = [None, None]
+    pending = [None, None]
+    for k, s in enumerate(range(0, L, host_chunk)):
+        e = min(L, s + host_chunk)
+        b = k & 1
+        if done[b] is not None:                        # staging pair b is free once its last copy has landed
+            done[b].synchronize()
+            ps, pe = pending[b]
+            out[ps:pe] = pin_buf[b][: pe - ps].numpy()
+        ops.bilinear_ensemble_sigmoid(heads, tails, [w[s:e] for w in wsel], precision=prec, out=dev_buf[b][: e - s])
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(ready)
+            pin_buf[b][: e - s].copy_(dev_buf[b][: e - s], non_blocking=True)
+            done[b] = torch.cuda.Event()
+            done[b].record(copy_stream)
+        pending[b] = (s, e)
+    for b in range(2):
+        if done[b] is not None:
+            done[b].synchronize()
+            ps, pe = pending[b]
+            out[ps:pe] = pin_buf[b][: pe - ps].numpy()
+    return out
