@@ -287,6 +287,25 @@ int mdg_gather_bce(const float* scores, int64_t n_labels, int64_t n_head, int64_
  *   MDG_SHARD_KG         [1]  0: multi-GPU inference keeps the KG encoder replicated instead of destination-partitioned
  * Build / bench only: MDG_EXTRA_HIPCC_FLAGS (madrigal_amd/build.py, e.g. -DMDG_RANK_STAMPS), MDG_BENCH_* (bench.py). */
 
+/* ---------------------------------------------------------------------- evaluation metrics ---- */
+
+/* Per-outcome classification metrics of T labelled triples, every label in one call.  Replaces
+ * madrigal/evaluate/metrics.py:60-191 (get_metrics -> get_metrics_binary per label: sklearn confusion_matrix,
+ * precision_recall_curve, roc_auc_score, average_precision_score, matthews_corrcoef, and precision_recall_at_k) after
+ * madrigal/evaluate/evaluate.py:191 copied the dense [L,N,N] probabilities to the host.
+ *   pred fp32 [T] (finite), target fp32 [T] (0 or 1), label int64 [T] in [0, n_labels);
+ *   top-k size: k > 0, or k = 0 and 0 < k_frac < 1 for k = int(k_frac * n_label) per label (0 there sets the status bit 8);
+ *   predicted positive <=> pred > threshold (0.5: np.round's rule for preds in [0, 1]).
+ * values float64 [13, n_labels] in the reference's key order: fmax, mcc, auroc, auprc, npv, specificity, f1, recall@k,
+ * precision@k, ap@k, accuracy, precision, recall (NaN rows for absent labels); count, pos, k_eff int64 [n_labels] (triples,
+ * positives and the resolved k per label); status int32 [1]: OR of 1 (NaN / inf pred), 2 (label out of range),
+ * 4 (target not 0/1), 8 (k resolved to 0).  Top-k ties: descending score, ties in reverse original order.
+ * Needs 0 < T < 2^31, 0 < n_labels <= 65536.  Deterministic: the same inputs give bit-identical values. */
+size_t mdg_label_metrics_workspace_bytes(int64_t n_triples, int64_t n_labels);
+int mdg_label_metrics(const float* pred, const float* target, const int64_t* label, int64_t n_triples, int64_t n_labels,
+                      int64_t k, double k_frac, float threshold, double* values, int64_t* count, int64_t* pos, int64_t* k_eff,
+                      int* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------- rank normalisation ---- */
 
 size_t mdg_rank_normalize_workspace_bytes(int64_t n_outcomes, int64_t N);

@@ -1,11 +1,15 @@
-"""The acceptance metric of the path: AUPRC (average precision) per outcome, macro-averaged
-(madrigal/evaluate/metrics.py:60-191: sklearn ``average_precision_score`` per label, then the mean over labels with both
-classes present).  Harness-side: sorting and prefix sums on the device (torch), no kernels of its own; sklearn is the
-checker in tests/."""
+"""Classification metrics of labelled DDI triples (madrigal/evaluate/metrics.py).
+
+``get_metrics`` is the drop-in for the reference's ``get_metrics`` (metrics.py:129-191): the 13 metrics of
+``get_metrics_binary`` (metrics.py:60-118) for every outcome in one call of ``ops.label_metrics`` (csrc/eval_metrics.hip),
+then the reference's averaging on the host over [13, L] numbers.
+``average_precision`` / ``macro_auprc`` are the earlier acceptance check of the path: AUPRC alone with torch sorts and
+prefix sums, kept as an independent statement of the same quantity; sklearn is the checker in tests/."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Any, Optional, Tuple
 
+import numpy as np
 import torch
 
 
@@ -46,3 +50,112 @@ def macro_auprc(pred: torch.Tensor, target: torch.Tensor, labels: torch.Tensor, 
             if 0 < s < hi - lo:
                 out[l] = average_precision(ps[lo:hi], y)
     return torch.nanmean(out), out
+
+
+_AVERAGES = (None, "macro", "weighted", "micro")
+_TASKS = ("binary", "multilabel", "multiclass")
+
+
+def _metric_names(k_name) -> tuple:
+    return ("fmax", "mcc", "auroc", "auprc", "npv", "specificity", "f1", f"recall@{k_name}", f"precision@{k_name}", f"ap@{k_name}",
+            "accuracy", "precision", "recall")
+
+
+def _print_metrics(names, vals, logger):
+    line = ", ".join(f"{n} = {v:.4f}" for n, v in zip(names, vals))
+    if logger is None:
+        print(line)
+    else:
+        logger.info(line)
+
+
+def get_metrics(preds, ys, labels, k=50, task: str = "multilabel", logger: Any = None, average: Optional[str] = "macro",
+                verbose: bool = True):
+    """madrigal/evaluate/metrics.py:get_metrics on the device -> (metrics dict with the reference's keys in order, pos_samples).
+
+    preds / ys / labels: numpy arrays or CUDA tensors of T triples (numpy input goes to the current device); preds are
+    probabilities (predicted positive <=> pred > 0.5, np.round's rule on [0, 1]).  ``task="binary"`` and ``average="micro"`` score
+    all triples as one problem; otherwise each label present is one problem and ``average`` is "macro" (plain mean: NaN
+    propagates), "weighted" (by positives) or None (arrays over the labels present, ascending).  Values are numpy float64.
+
+    Mirrored quirks of the reference: with a fractional k the names ``recall@{k}`` etc. carry the resolved k of the LAST label
+    present (its loop leaves the last label's names); a problem whose targets and rounded preds are all one class raises
+    ValueError (the reference's ``confusion_matrix(...).ravel()`` unpack fails there), as does a pred that rounds outside {0, 1}.
+    Top-k ties are broken by reverse original order (np.argsort(pred, kind="stable")[::-1]), where the reference's unstable
+    argsort leaves them arbitrary."""
+    from . import ops
+    if average not in _AVERAGES:
+        raise ValueError(f"average must be one of {_AVERAGES}, got {average!r}")
+    if task not in _TASKS:
+        raise ValueError(f"task must be one of {_TASKS}, got {task!r}")
+    if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)):
+        raise ValueError(f"k must be an int or a float in (0, 1), got {k!r}")
+    if isinstance(k, (float, np.floating)):
+        if not 0.0 < float(k) < 1.0:
+            raise ValueError(f"a float k must lie in (0, 1), got {k}")
+        k = float(k)
+    else:
+        k = int(k)
+        if k <= 0:
+            raise ValueError(f"k must be positive, got {k}")
+    n = len(preds)
+    if len(ys) != n or len(labels) != n or n == 0:
+        raise ValueError(f"preds, ys and labels must be non-empty and of one length (got {n}, {len(ys)}, {len(labels)})")
+    ys_dtype = ys.dtype if isinstance(ys, np.ndarray) else torch.empty(0, dtype=ys.dtype).numpy().dtype
+
+    def dev(x, dtype):
+        if isinstance(x, torch.Tensor):
+            if not x.is_cuda:
+                raise ValueError("get_metrics: tensors must live on the GPU (or pass numpy arrays)")
+            return x.reshape(-1).to(dtype)
+        return torch.as_tensor(np.ascontiguousarray(x).reshape(-1)).to(device=torch.device("cuda", torch.cuda.current_device()), dtype=dtype)
+
+    pred, tgt = dev(preds, torch.float32), dev(ys, torch.float32)
+    lab = dev(labels, torch.int64)
+    if pred.device != tgt.device or pred.device != lab.device:
+        raise ValueError("get_metrics: preds, ys and labels must be on one device")
+    single = task == "binary" or average == "micro"
+    micro_pos = None
+    if single:
+        if task != "binary":                                            # micro: pos_samples stay per label
+            if int(lab.min()) < 0:
+                raise ValueError("labels must be non-negative")
+            cnt = torch.bincount(lab)
+            micro_pos = torch.bincount(lab, weights=tgt.double())[cnt > 0].cpu().numpy()
+        lab, L = torch.zeros_like(lab), 1
+    else:
+        lo_hi = torch.stack([lab.min(), lab.max()]).tolist()
+        if lo_hi[0] < 0:
+            raise ValueError(f"labels must be non-negative, got {lo_hi[0]}")
+        L = lo_hi[1] + 1
+    p_lo, p_hi = torch.aminmax(pred)
+    r = ops.label_metrics(pred, tgt, lab, L, k=k, threshold=0.5)
+    if not (float(p_lo) >= -0.5 and float(p_hi) < 1.5):
+        raise ValueError("get_metrics: a pred rounds outside {0, 1} (the reference's confusion_matrix unpack fails)")
+    values, count, pos, k_eff = (r[x].cpu().numpy() for x in ("values", "count", "pos", "k_eff"))
+    present = np.flatnonzero(count > 0)
+    one_class = ((pos[present] == 0) | (pos[present] == count[present])) & (values[10, present] == 1.0)
+    if one_class.any():
+        raise ValueError(f"label {int(present[np.argmax(one_class)])}: targets and rounded preds are all one class "
+                         "(the reference's confusion_matrix(...).ravel() unpack fails)")
+    k_name = int(k_eff[present[-1]]) if isinstance(k, float) else k
+    names = _metric_names(k_name)
+    if single:
+        vals = values[:, 0]
+        pos_samples = ys_dtype.type(pos[0]) if task == "binary" else micro_pos.astype(ys_dtype)
+        if task == "binary":
+            if verbose:
+                _print_metrics(names, vals, logger)
+            return dict(zip(names, vals)), pos_samples
+    else:
+        per = np.ascontiguousarray(values[:, present].T)                # [n_present, 13], as the reference stacks its rows
+        pos_samples = pos[present].astype(ys_dtype)
+        if average == "macro":
+            vals = per.mean(axis=0)
+        elif average == "weighted":
+            vals = per.T @ pos_samples / pos_samples.sum()
+        else:
+            vals = per.T
+    if verbose and average is not None:
+        _print_metrics(names, vals, logger)
+    return dict(zip(names, vals)), pos_samples

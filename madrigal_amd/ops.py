@@ -1624,3 +1624,55 @@ def sync_batchnorm_train_bwd(dy: torch.Tensor, x: torch.Tensor, stats: torch.Ten
     check(lib().mdg_batchnorm_bwd_apply(_ptr(dy), _ptr(x), _ptr(stats), _ptr(both[:C].contiguous()), _ptr(both[C:].contiguous()), _ptr(dx),
                                         _c64(R), _c64(C), ctypes.c_double(0.0), _ptr(count), _stream(x)), "mdg_batchnorm_bwd_apply")
     return dx, dg, db
+
+
+# ------------------------------------------------------------------------------- evaluation metrics
+LABEL_METRIC_NAMES = ("fmax", "mcc", "auroc", "auprc", "npv", "specificity", "f1", "recall@k", "precision@k", "ap@k",
+                      "accuracy", "precision", "recall")
+_LABEL_METRIC_STATUS = ((1, "pred holds a NaN or infinite value"), (2, "a label is outside [0, n_labels)"),
+                        (4, "target holds a value other than 0 and 1"), (8, "k resolves to 0 for a label (k * n_label < 1)"))
+
+
+def label_metrics(pred: torch.Tensor, target: torch.Tensor, label: torch.Tensor, n_labels: int, k=50, threshold: float = 0.5) -> dict:
+    """Per-label metrics of get_metrics_binary (madrigal/evaluate/metrics.py:60-118) for every label at once (csrc/eval_metrics.hip).
+
+    pred / target fp32 [T] (target 0 or 1), label int64 [T] in [0, n_labels).  ``k`` is an int > 0, or a float in (0, 1) resolved per
+    label to int(k * n_label).  Returns device tensors: ``values`` float64 [13, n_labels] in the order of LABEL_METRIC_NAMES (NaN
+    columns for labels without triples), ``count`` / ``pos`` / ``k_eff`` int64 [n_labels].  One host read (the status word): raises
+    ValueError on a NaN / infinite pred, a label out of range, a target other than 0/1, or k resolving to 0."""
+    pred, target = _f32_cuda(pred, "pred", 1), _f32_cuda(target, "target", 1)
+    T = int(pred.numel())
+    if not (isinstance(label, torch.Tensor) and label.is_cuda and label.dtype == torch.int64 and label.dim() == 1 and label.numel() == T):
+        raise ValueError(f"label: expected int64 cuda [{T}]")
+    if target.numel() != T or pred.device != target.device or pred.device != label.device:
+        raise ValueError("label_metrics: pred, target and label must be [T] on one device")
+    if not 0 < T < 2 ** 31:
+        raise ValueError(f"label_metrics: need 0 < T < 2^31 triples, got {T}")
+    n_labels = int(n_labels)
+    if not 0 < n_labels <= 65536:
+        raise ValueError(f"label_metrics: need 0 < n_labels <= 65536, got {n_labels}")
+    if isinstance(k, bool) or not isinstance(k, (int, float)):
+        raise ValueError(f"label_metrics: k must be an int or a float in (0, 1), got {k!r}")
+    if isinstance(k, float):
+        if not 0.0 < k < 1.0:
+            raise ValueError(f"label_metrics: a float k must lie in (0, 1), got {k}")
+        k_int, k_frac = 0, float(k)
+    else:
+        if k <= 0:
+            raise ValueError(f"label_metrics: k must be positive, got {k}")
+        k_int, k_frac = int(k), 0.0
+    dev, L = pred.device, n_labels
+    label = label.contiguous()
+    values = torch.empty(13, L, dtype=torch.float64, device=dev)
+    count, pos, k_eff = (torch.empty(L, dtype=torch.int64, device=dev) for _ in range(3))
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    lb = lib()
+    nbytes = lb.mdg_label_metrics_workspace_bytes(_c64(T), _c64(L))
+    ws = _workspace(nbytes, dev)
+    check(lb.mdg_label_metrics(_ptr(pred), _ptr(target), _ptr(label), _c64(T), _c64(L), _c64(k_int), ctypes.c_double(k_frac),
+                               ctypes.c_float(threshold), _ptr(values), _ptr(count), _ptr(pos), _ptr(k_eff), _ptr(status), _ptr(ws),
+                               ctypes.c_size_t(nbytes), _stream(pred)), "mdg_label_metrics")
+    st = int(status.item())
+    if st:
+        raise ValueError("label_metrics: " + "; ".join(msg for bit, msg in _LABEL_METRIC_STATUS if st & bit))
+    return {"values": values, "count": count, "pos": pos, "k_eff": k_eff}
