@@ -174,6 +174,16 @@ size_t mdg_linear_packed_x_workspace_bytes(int64_t M, int64_t N, int64_t K, int 
 int mdg_linear_packed_x(const void* x_packed, int64_t M, int64_t K, const float* w, int64_t ldw, const void* w_packed, float* y,
                         int64_t ldy, int64_t N, const float* bias, int act, const float* residual, int64_t ldr, float alpha,
                         float beta, int precision, void* workspace, size_t workspace_bytes, void* stream);
+/* Layer 0 of the fusion transformer (models.py:401-455: embed2latent, then norm1 -> self_attn.in_proj of the first
+ * nn.TransformerEncoderLayer) with norm1 and embed2latent folded into one short-K weight: QKV = rstd (T M^T + c) + c2 over the
+ * 128-wide token rows T.  mdg_row_rstd writes the one number per row the fold leaves over, rstd[r] = 1 / sqrt(var(h[r]) + eps)
+ * (the factor mdg_layernorm applies to row r of h, bit for bit; d multiple of 4, <= 2048).  mdg_linear_rowscaled is mdg_linear
+ * with the row-scaled epilogue y[m, n] = row_scale[m] * ((x W^T)[m, n] + bias_pre[n]) + bias[n] (bias_pre and bias nullable),
+ * on the 128-tile kernel; workspace: mdg_linear_workspace_bytes. */
+int mdg_row_rstd(const float* x, int64_t ldx, float* rstd, int64_t rows, int64_t d, float eps, void* stream);
+int mdg_linear_rowscaled(const float* x, int64_t ldx, const float* w, int64_t ldw, const void* w_packed, float* y, int64_t ldy,
+                         int64_t M, int64_t N, int64_t K, const float* row_scale, const float* bias_pre, const float* bias,
+                         int precision, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------- cross-modal fusion ---- */
 

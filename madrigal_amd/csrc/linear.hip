@@ -259,6 +259,9 @@ struct LinearArgs {
   Operand A, B;            // K is a multiple of 32 in both images (zero padded by the pre-pass when needed)
   float* y; int64_t ldy;
   const float* bias; const float* scale; const float* shift;
+  // row-scaled epilogue (null: off): acc -> row_scale[m] * (acc + bias_pre[n]) + bias[n] ahead of the scale / activation / residual
+  // steps (a LayerNorm folded into the weights: the per-row 1/std the fold leaves over; bias_pre may be null)
+  const float* row_scale; const float* bias_pre;
   const float* res; int64_t ldr;
   float alpha, beta;
   int act;
@@ -435,8 +438,8 @@ __device__ __forceinline__ void k_loop(const LinearArgs& p, int64_t row0, int64_
 // apart) and for the float4 rows on the way out.
 __device__ __forceinline__ int slab_off(int row, int col) { return row * 64 + ((((col >> 4) ^ ((row >> 2) & 3)) << 4) | (col & 15)); }
 
-__device__ __forceinline__ float finish(const LinearArgs& p, float v, float bias, float scale, float shift) {
-  float val = v + bias;
+__device__ __forceinline__ float finish(const LinearArgs& p, float v, float bias, float scale, float shift, float bpre, float rs) {
+  float val = p.row_scale ? (v + bpre) * rs + bias : v + bias;
   if (p.scale) val = val * scale + shift;
   val = apply_act(val, p.act);
   if (p.alpha != 1.0f) val *= p.alpha;
@@ -449,12 +452,13 @@ __device__ __forceinline__ void slab_to_global(const LinearArgs& p, const float*
   const int64_t n = n0 + 4 * c4;
   if (n >= p.N) return;
   const bool full = n + 3 < p.N;
-  float bias[4] = {0.f, 0.f, 0.f, 0.f}, scale[4] = {1.f, 1.f, 1.f, 1.f}, shift[4] = {0.f, 0.f, 0.f, 0.f};
+  float bias[4] = {0.f, 0.f, 0.f, 0.f}, scale[4] = {1.f, 1.f, 1.f, 1.f}, shift[4] = {0.f, 0.f, 0.f, 0.f}, bpre[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int e = 0; e < 4; ++e)
     if (n + e < p.N) {
       if (p.bias) bias[e] = p.bias[n + e];
       if (p.scale) { scale[e] = p.scale[n + e]; shift[e] = p.shift[n + e]; }
+      if (p.bias_pre) bpre[e] = p.bias_pre[n + e];
     }
 #pragma unroll 4
   for (int it = 0; it < 16; ++it) {
@@ -462,9 +466,10 @@ __device__ __forceinline__ void slab_to_global(const LinearArgs& p, const float*
     const int64_t m = m0 + row;
     const f32x4 a = *reinterpret_cast<const f32x4*>(slab + slab_off(row, 4 * c4));
     if (m >= p.M) continue;
+    const float rs = p.row_scale ? p.row_scale[m] : 1.f;
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = finish(p, a[e], bias[e], scale[e], shift[e]);
+    for (int e = 0; e < 4; ++e) o[e] = finish(p, a[e], bias[e], scale[e], shift[e], bpre[e], rs);
     if (p.drop_scale != 0.f) {
       const uint64_t i0 = static_cast<uint64_t>(m) * static_cast<uint64_t>(p.N) + static_cast<uint64_t>(n);
       if ((p.N & 3) == 0) {                               // n is a multiple of 4: the lane's four columns are one hash group
@@ -1093,15 +1098,9 @@ inline int64_t pad64(int64_t k) { return (k + 63) / 64 * 64; }
 inline int64_t pad32(int64_t k) { return (k + 31) / 32 * 32; }
 
 // ---- LayerNorm: one wave per row -------------------------------------------------------------
+// the row's mean and 1 / sqrt(biased variance + eps), two passes over the row held in registers (v: the row, for the caller)
 template <int VEC>   // floats per lane = 4*VEC, d <= 256*VEC
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
-                                                        const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
-                                                        int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* xr = x + row * ldx;
-  f32x4 v[VEC];
+__device__ __forceinline__ void ln_row_stats(const float* __restrict__ xr, int lane, int d, float eps, f32x4 (&v)[VEC], float& mean, float& rstd) {
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -1109,7 +1108,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     v[i] = c < d ? *reinterpret_cast<const f32x4*>(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
   }
-  const float mean = mdg_wave_sum(s) / d;
+  mean = mdg_wave_sum(s) / d;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -1122,7 +1121,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       }
     }
   }
-  const float rstd = 1.0f / sqrtf(mdg_wave_sum(q) / d + eps);
+  rstd = 1.0f / sqrtf(mdg_wave_sum(q) / d + eps);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
+                                                        const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
+                                                        int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  f32x4 v[VEC];
+  float mean, rstd;
+  ln_row_stats<VEC>(x + row * ldx, lane, d, eps, v, mean, rstd);
   float* yr = y + row * ldy;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -1152,6 +1163,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       }
     }
   }
+}
+
+// LayerNorm's row statistics only: rstd[row] = 1 / sqrt(var + eps), the same reduction as layernorm_kernel (mdg_row_rstd)
+template <int VEC>
+__global__ __launch_bounds__(256) void row_rstd_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ rstd, int64_t rows, int d,
+                                                       float eps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  f32x4 v[VEC];
+  float mean, r;
+  ln_row_stats<VEC>(x + row * ldx, lane, d, eps, v, mean, r);
+  if (lane == 0) rstd[row] = r;
 }
 
 }  // namespace
@@ -1205,9 +1229,10 @@ static bool pp_shape(int precision, int64_t M, int64_t N) {
 }
 
 // tile shape: the 256x256 / 8-wave shape once the problem fills the chip with it, else 128x128 / 4 waves
-// (measured on the fusion GEMMs: bf16x3 -9 % time with the big tile, fp32 +6 %: the fp32 MFMA wants two workgroups per CU)
-static bool choose_big(int precision, int64_t M, int64_t N) {
-  bool big = pp_shape(precision, M, N);
+// (measured on the fusion GEMMs: bf16x3 -9 % time with the big tile, fp32 +6 %: the fp32 MFMA wants two workgroups per CU).
+// prefer_small: the 128-tile kernel at any size (a short-K product bound by its stores: mdg_linear_rowscaled)
+static bool choose_big(int precision, int64_t M, int64_t N, bool prefer_small = false) {
+  bool big = !prefer_small && pp_shape(precision, M, N);
   static MdgEnvInt tile_sw{"MDG_LINEAR_TILE", 0};
   if (tile_sw.get() == 256) big = precision != MDG_PREC_F32;
   else if (tile_sw.get() == 128) big = false;
@@ -1221,10 +1246,11 @@ static bool raw_x_ok(int precision, bool big) {
 }
 
 // sk_ws / sk_avail: what is left of the caller's workspace behind the operand images (the stream-K slots and flags)
-static void launch_linear_core(LinearArgs& a, int precision, int64_t M, int64_t N, hipStream_t st, char* sk_ws = nullptr, size_t sk_avail = 0) {
+static void launch_linear_core(LinearArgs& a, int precision, int64_t M, int64_t N, hipStream_t st, char* sk_ws = nullptr, size_t sk_avail = 0,
+                               bool prefer_small = false) {
   a.vec_y = mdg_aligned16(a.y) && a.ldy % 4 == 0;
   a.vec_r = a.res && mdg_aligned16(a.res) && a.ldr % 4 == 0;
-  const bool big = choose_big(precision, M, N);
+  const bool big = choose_big(precision, M, N, prefer_small);
   // 1-D grid; the kernel maps the linear workgroup id to a tile (XCD-aware order once there are enough tiles to matter)
   constexpr int swz_env = -1;                              // XCD-aware tile order once there are 64 tiles
   const auto grid_for = [&](int bm, int bn) {
@@ -1376,7 +1402,8 @@ extern "C" size_t mdg_linear_packed_x_workspace_bytes(int64_t M, int64_t N, int6
 static int linear_impl(const float* x, int64_t ldx, const float* w, int64_t ldw, const void* w_packed, float* y, int64_t ldy,
                        int64_t M, int64_t N, int64_t K, const float* bias, const float* scale, const float* shift, int act,
                        const float* residual, int64_t ldr, float alpha, float beta, int precision, void* workspace,
-                       size_t workspace_bytes, void* stream, float drop_p, uint64_t drop_seed) {
+                       size_t workspace_bytes, void* stream, float drop_p, uint64_t drop_seed, const float* row_scale = nullptr,
+                       const float* bias_pre = nullptr, bool prefer_small = false) {
   MDG_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "mdg_linear: negative size");
   MDG_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "mdg_linear: dropout p must be in [0,1)");
   if (M == 0 || N == 0) return MDG_OK;
@@ -1391,7 +1418,7 @@ static int linear_impl(const float* x, int64_t ldx, const float* w, int64_t ldw,
   MDG_CHECK_ARG(mdg_cdiv(M, Small::BM) * mdg_cdiv(N, Small::BN) < (1ll << 31) - 8, "mdg_linear: too many tiles for one launch");
   MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16, "mdg_linear: unknown precision %d", precision);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool rawx = raw_x_ok(precision, choose_big(precision, M, N));
+  const bool rawx = raw_x_ok(precision, choose_big(precision, M, N, prefer_small));
   const size_t xb = rawx ? 0 : image_bytes(M, K, precision), wb = image_bytes(N, K, precision);
   const bool w_ready = w_packed != nullptr || wb == 0;      // fp32 with K % 32 == 0 needs no image at all
   MDG_CHECK_ARG(w || w_ready, "mdg_linear: raw w missing");
@@ -1409,6 +1436,7 @@ static int linear_impl(const float* x, int64_t ldx, const float* w, int64_t ldw,
   }
   LinearArgs a{};
   a.y = y; a.ldy = ldy; a.bias = bias; a.scale = scale; a.shift = shift; a.res = residual; a.ldr = ldr;
+  a.row_scale = row_scale; a.bias_pre = bias_pre;
   a.alpha = alpha; a.beta = beta; a.act = act; a.M = M; a.N = N; a.K = pad_k(K, precision);
   set_operand(a.A, x, ldx, ximg, M, K, precision);
   if (rawx) { a.a_raw = x; a.a_ldx = ldx; a.a_k = K; a.A.nrows = M; }
@@ -1418,7 +1446,7 @@ static int linear_impl(const float* x, int64_t ldx, const float* w, int64_t ldw,
     a.drop_seed = drop_seed;
     a.drop_scale = 1.0f / (1.0f - drop_p);
   }
-  launch_linear_core(a, precision, M, N, st, workspace ? ws + need : nullptr, workspace_bytes > need ? workspace_bytes - need : 0);
+  launch_linear_core(a, precision, M, N, st, workspace ? ws + need : nullptr, workspace_bytes > need ? workspace_bytes - need : 0, prefer_small);
   MDG_CHECK_LAUNCH("mdg_linear");
   return MDG_OK;
 }
@@ -1436,6 +1464,17 @@ extern "C" int mdg_linear_dropout(const float* x, int64_t ldx, const float* w, i
                                   float drop_p, uint64_t drop_seed, int precision, void* workspace, size_t workspace_bytes, void* stream) {
   return linear_impl(x, ldx, w, ldw, w_packed, y, ldy, M, N, K, bias, nullptr, nullptr, act, residual, ldr, 1.0f, beta, precision, workspace,
                      workspace_bytes, stream, drop_p, drop_seed);
+}
+
+// Row-scaled dense block: y[m, n] = row_scale[m] * ((x W^T)[m, n] + bias_pre[n]) + bias[n] (bias_pre, bias nullable).  Made for short
+// K (the fusion transformer's layer-0 QKV block with norm1 folded into its weights): it runs on the 128-tile kernel, which stages x
+// straight from its fp32 rows in the 16-bit modes; MDG_LINEAR_TILE=256 selects the 256-tile kernel (x then goes through the pre-pass).
+extern "C" int mdg_linear_rowscaled(const float* x, int64_t ldx, const float* w, int64_t ldw, const void* w_packed, float* y, int64_t ldy,
+                                    int64_t M, int64_t N, int64_t K, const float* row_scale, const float* bias_pre, const float* bias,
+                                    int precision, void* workspace, size_t workspace_bytes, void* stream) {
+  MDG_CHECK_ARG(M == 0 || row_scale, "mdg_linear_rowscaled: null row_scale");
+  return linear_impl(x, ldx, w, ldw, w_packed, y, ldy, M, N, K, bias, nullptr, nullptr, MDG_ACT_NONE, nullptr, 0, 1.f, 1.f, precision, workspace,
+                     workspace_bytes, stream, 0.f, 0, row_scale, bias_pre, true);
 }
 
 // ---- grouped launch: see the GROUPED kernel variant -------------------------------------------------------------------------
@@ -1684,6 +1723,26 @@ extern "C" int mdg_layernorm_packed(const float* x, int64_t ldx, const float* ga
                                     int64_t d, float eps, int precision, void* y_packed, size_t y_packed_bytes, void* stream) {
   MDG_CHECK_ARG(y_packed, "mdg_layernorm_packed: null image");
   return layernorm_impl(x, ldx, gamma, beta, y, ldy, rows, d, eps, precision, y_packed, y_packed_bytes, stream);
+}
+
+// LayerNorm's row statistics alone (no normalised rows): rstd[r] = 1 / sqrt(var(x[r, :d]) + eps), bit-identical to the factor
+// mdg_layernorm applies to row r.
+extern "C" int mdg_row_rstd(const float* x, int64_t ldx, float* rstd, int64_t rows, int64_t d, float eps, void* stream) {
+  MDG_CHECK_ARG(rows >= 0 && d > 0, "mdg_row_rstd: bad shape");
+  if (rows == 0) return MDG_OK;
+  MDG_CHECK_ARG(x && rstd, "mdg_row_rstd: null pointer");
+  MDG_CHECK_ARG(d % 4 == 0 && d <= 2048 && ldx % 4 == 0 && ldx >= d, "mdg_row_rstd: d must be a multiple of 4 and <= 2048 (got %lld), ldx >= d",
+                (long long)d);
+  MDG_CHECK_ARG(mdg_aligned16(x), "mdg_row_rstd: 16-byte alignment");
+  const dim3 grid(static_cast<unsigned>(mdg_cdiv(rows, 4)));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int di = static_cast<int>(d);
+  if (d <= 256) hipLaunchKernelGGL(row_rstd_kernel<1>, grid, dim3(256), 0, st, x, ldx, rstd, rows, di, eps);
+  else if (d <= 512) hipLaunchKernelGGL(row_rstd_kernel<2>, grid, dim3(256), 0, st, x, ldx, rstd, rows, di, eps);
+  else if (d <= 1024) hipLaunchKernelGGL(row_rstd_kernel<4>, grid, dim3(256), 0, st, x, ldx, rstd, rows, di, eps);
+  else hipLaunchKernelGGL(row_rstd_kernel<8>, grid, dim3(256), 0, st, x, ldx, rstd, rows, di, eps);
+  MDG_CHECK_LAUNCH("mdg_row_rstd");
+  return MDG_OK;
 }
 
 // mdg_linear on an x that already exists as an operand image (written by mdg_layernorm_packed / mdg_pack_operand): no pre-pass.

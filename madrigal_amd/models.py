@@ -1087,6 +1087,19 @@ def get_tx_encoder(tx_encoder_name, tx_encoder_hparams, embed_dim, use_modality_
 
 
 # ------------------------------------------------------------------------------------- fusion
+def compose_qkv0(We, be, Wq, bq, norm=None):
+    """fp64 composite of embed2latent (We [d,D], be), an optional LayerNorm ``norm`` = (gamma, beta) and the QKV projection (Wq [3d,d], bq):
+    (M [3d,D], c [3d] or None, c2 [3d]) with  Wq LN(T We^T + be) + bq = rstd * (T M^T + c) + c2  row by row (rstd = 1 / sqrt(var + eps)
+    of h = T We^T + be), or = T M^T + c2 without the norm.  Centring the rows of h is the same as centring We and be over their d outputs."""
+    f8 = torch.float64
+    We, be, Wq, bq = (t.detach().to(f8) for t in (We, be, Wq, bq))
+    if norm is None:
+        return Wq @ We, None, Wq @ be + bq
+    g1, b1 = (t.detach().to(f8) for t in norm)
+    Wg = Wq * g1                                                          # Wq diag(gamma)
+    return Wg @ (We - We.mean(0, keepdim=True)), Wg @ (be - be.mean()), Wq @ b1 + bq
+
+
 class TransformerFusion(nn.Module):
     """madrigal/models/models.py:352-455.  Holds a stock ``nn.TransformerEncoder`` / ``nn.MultiheadAttention``
     ONLY for their parameters (identical state_dict keys; ``transformer_encoder.layers[-1].self_attn`` stays
@@ -1123,11 +1136,35 @@ class TransformerFusion(nn.Module):
                 kpm[:, -len(CELL_LINES):] = True
             self.x_attn_key_padding_mask = kpm
         self.last_attention_weights = None
+        # eval path: layer 0's QKV block from the token rows through the composed weights (_qkv0); False: norm1 -> in_proj on h
+        self.compose_layer0 = True
+
+    # ---- layer 0's QKV block with embed2latent and norm1 folded into its weights ---------------------
+    def _qkv0(self, L, tokens, h):
+        """q | k | v rows of layer 0 from its 128-wide token rows T (h = T W_e^T + b_e).  Row-centring is linear in T, so all of
+        norm1 but the per-row factor rstd = 1 / sqrt(var(h) + eps) folds into the weights (W_e centred over its d outputs, in fp64):
+            pre-norm   qkv = rstd * (T M^T + c) + c2,   M = W_qkv diag(g1) W_c,  c = W_qkv (g1 * b_c),  c2 = W_qkv b1 + b_qkv
+            post-norm  qkv = T (W_qkv W_e)^T + (W_qkv b_e + b_qkv)
+        a K = 128 product in place of the K = d one.  The composite and its operand image are rebuilt only when a source changes."""
+        sa, prec = L.self_attn, _state["precision"]
+
+        def build():
+            norm = (L.norm1.weight, L.norm1.bias) if self.norm_first else None
+            M, c, c2 = (None if t is None else t.to(torch.float32).contiguous()
+                        for t in compose_qkv0(self.embed2latent.weight, self.embed2latent.bias, sa.in_proj_weight, sa.in_proj_bias, norm))
+            return M, c, c2, ops.pack_operand(M, prec)
+        srcs = (self.embed2latent.weight, self.embed2latent.bias, sa.in_proj_weight, sa.in_proj_bias) + \
+            ((L.norm1.weight, L.norm1.bias) if self.norm_first else ())
+        M, c, c2, img = _cached(self, ("qkv0", self.norm_first, prec), srcs, build)
+        if not self.norm_first:
+            return ops.linear(tokens, M, c2, precision=prec, weight_image=img)
+        return ops.linear_rowscaled(tokens, M, ops.row_rstd(h, L.norm1.eps), c, c2, precision=prec, weight_image=img)
 
     # ---- one transformer layer on a set of token rows (dense or compact) --------------------
-    def _layer(self, L, h, attend, keep_rows=None):
+    def _layer(self, L, h, attend, keep_rows=None, tokens=None):
         """``attend(qkv) -> attention output rows``; ``keep_rows`` (int64 index) prunes the rows that
-        continue after the attention (last layer: only the pooled key tokens are ever read again)."""
+        continue after the attention (last layer: only the pooled key tokens are ever read again).  ``tokens``: layer 0's input
+        rows ahead of embed2latent, whose QKV block then comes from ``_qkv0`` (``attend`` sees no normalised rows)."""
         sa = L.self_attn
 
         def norm(x, ln, want_fp32=True):
@@ -1153,15 +1190,18 @@ class TransformerFusion(nn.Module):
             qkv[:, :d].index_copy_(0, keep_rows, _lin(a.index_select(0, keep_rows), w[:d], b[:d]))
             return qkv
         if self.norm_first:
-            a, a_img = norm(h, L.norm1)
-            att = attend(in_proj(a, a_img), a)
+            if tokens is not None:
+                att = attend(self._qkv0(L, tokens, h), None)
+            else:
+                a, a_img = norm(h, L.norm1)
+                att = attend(in_proj(a, a_img), a)
             if keep_rows is not None:
                 att, h = att.index_select(0, keep_rows), h.index_select(0, keep_rows)
             h = _lin(att, sa.out_proj.weight, sa.out_proj.bias, residual=h)
             f, f_img = norm(h, L.norm2, want_fp32=False)
             u = lin_of(f, f_img, L.linear1.weight, L.linear1.bias, rows=h.shape[0], act=self.actn)
             return _lin(u, L.linear2.weight, L.linear2.bias, residual=h)
-        att = attend(in_proj(h), h)
+        att = attend(in_proj(h) if tokens is None else self._qkv0(L, tokens, h), h)
         if keep_rows is not None:
             att, h = att.index_select(0, keep_rows), h.index_select(0, keep_rows)
         t = _lin(att, sa.out_proj.weight, sa.out_proj.bias, residual=h)
@@ -1284,7 +1324,8 @@ class TransformerFusion(nn.Module):
             else:
                 keep, Tk = torch.arange(n, device=dev) * S, None
             return self._forward_train(fusion_sequence.reshape(n * S, D), n, S, attend_t, keep, True, Tk)
-        h = _lin(fusion_sequence.reshape(n * S, D), self.embed2latent.weight, self.embed2latent.bias)
+        x0 = fusion_sequence.reshape(n * S, D)
+        h = _lin(x0, self.embed2latent.weight, self.embed2latent.bias)
         layers = self.transformer_encoder.layers
         for li, L in enumerate(layers):
             want = li == len(layers) - 1
@@ -1294,7 +1335,9 @@ class TransformerFusion(nn.Module):
                 att, pr = ops.fusion_attention(qkv, n, S, H, dh, kbits, sbits, want_probs=want)
                 seen["att"], seen["pr"], seen["in"] = att, pr, x_in
                 return att
-            h = self._layer(L, h, attend)
+            # the hooks of a last layer 0 are handed its normalised rows: those exist on the uncomposed path only
+            compose = li == 0 and self.compose_layer0 and not (want and self.norm_first and len(L.self_attn._forward_hooks))
+            h = self._layer(L, h, attend, tokens=x0 if compose else None)
             if want:
                 self.last_attention_weights = seen["pr"]
                 for hook in list(L.self_attn._forward_hooks.values()):      # analysis hooks expect (attn_out, weights)
@@ -1415,7 +1458,8 @@ class TransformerFusion(nn.Module):
         for li, L in enumerate(layers):
             last = li == len(layers) - 1
             keep = plan.get("key_rows") if (last and agg in ('x-attn', 'cls')) else None
-            h = self._layer(L, h, attend, keep_rows=keep)
+            compose = li == 0 and self.compose_layer0 and keep is None            # (a last layer 0 with kept rows: queries of those only)
+            h = self._layer(L, h, attend, keep_rows=keep, tokens=tokens if compose else None)
         self.last_attention_weights = None
         if agg == 'x-attn':
             return self._x_attn_pool(h, n, plan["Tk"])

@@ -436,6 +436,50 @@ def layernorm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: fl
     return out.view(*lead, d) if lead is not None and out.is_contiguous() else out
 
 
+def row_rstd(x: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """LayerNorm's per-row factor 1 / sqrt(var + eps) of a 2-D ``x`` [R, d] -> [R] (the factor ``layernorm`` applies, bit for bit)."""
+    forward_only(x)
+    x2 = x if (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.is_cuda and x.dtype == torch.float32) else _rows2d(x, "x")[0]
+    R, d = x2.shape
+    out = torch.empty(R, dtype=torch.float32, device=x2.device)
+    check(lib().mdg_row_rstd(_ptr(x2), _c64(x2.stride(0)), _ptr(out), _c64(R), _c64(d), _f(eps), _stream(x2)), "mdg_row_rstd")
+    return out
+
+
+def linear_rowscaled(x: torch.Tensor, weight: torch.Tensor, row_scale: torch.Tensor, bias_pre: Optional[torch.Tensor] = None,
+                     bias: Optional[torch.Tensor] = None, *, precision="bf16x3", weight_image: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[m] = row_scale[m] * (x[m] W^T + bias_pre) + bias on the 128-tile dense block (short K; nn.Linear layout W [N,K]).
+    ``weight_image``: the weight's operand image when the caller keeps one, else the per-storage cache of ``linear``."""
+    forward_only(x, weight, row_scale, bias_pre, bias)
+    x2, lead = _rows2d(x, "x")
+    if x2.shape[1] % 4:
+        x2 = _pad_last(x2)
+    w = padded_weight(_f32_cuda(weight, "weight", 2))
+    M, K, N = x2.shape[0], x2.shape[1], w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"linear_rowscaled: x has inner dim {x.shape[-1]} but weight is {tuple(weight.shape)}")
+    if row_scale.numel() != M or not row_scale.is_cuda or row_scale.dtype != torch.float32:
+        raise ValueError(f"row_scale: expected fp32 cuda [{M}]")
+    for nm, t in (("bias_pre", bias_pre), ("bias", bias)):
+        if t is not None and (t.numel() != N or not t.is_cuda or t.dtype != torch.float32):
+            raise ValueError(f"{nm}: expected fp32 cuda [{N}]")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x2.device)
+    elif out.dim() != 2 or out.shape != (M, N) or out.stride(1) != 1 or out.dtype != torch.float32 or not out.is_cuda:
+        raise ValueError(f"out: expected fp32 cuda [{M},{N}] with unit inner stride")
+    prec = _prec(precision)
+    wimg = weight_image if weight_image is not None else packed_weight_image(w, prec)
+    nbytes = lib().mdg_linear_workspace_bytes(_c64(M), _c64(N), _c64(K), _c(prec), _c(1 if wimg is not None else 0))
+    ws = _workspace(nbytes, x2.device)
+    check(lib().mdg_linear_rowscaled(_ptr(x2), _c64(x2.stride(0)), _ptr(w), _c64(w.stride(0)), _ptr(wimg), _ptr(out), _c64(out.stride(0)),
+                                     _c64(M), _c64(N), _c64(K), _ptr(row_scale.contiguous()),
+                                     _ptr(None if bias_pre is None else bias_pre.detach().contiguous()),
+                                     _ptr(None if bias is None else bias.detach().contiguous()), _c(prec), _ptr(ws), ctypes.c_size_t(nbytes),
+                                     _stream(x2)), "mdg_linear_rowscaled")
+    return out.view(*lead, N) if len(lead) != 1 or lead[0] != M else out
+
+
 # ------------------------------------------------------------------------------- fusion
 def mask_bits(mask: torch.Tensor) -> torch.Tensor:
     """bool [..., S] (True = masked) -> uint32-valued int32 [...] bit field, bit j = mask[..., j]."""
