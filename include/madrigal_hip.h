@@ -217,6 +217,19 @@ int mdg_fusion_attention(const float* qkv, int64_t ld, float* out, int64_t ldo, 
  * Replaces x_attn_mha_layer, madrigal/models/models.py:430-438. */
 int mdg_xattn_pool(const float* q_proj, const float* kv_proj, int64_t ld, float* out, int64_t ldo, int64_t n, int Tk, int H, int dh,
                    void* stream);
+/* The same pooling in eval mode with a pre-norm layer, folded through V, out_proj, the query residual and latent2embed
+ * (models.py:422-443; TransformerFusion._x_attn_pool_folded).  With u_t = x_attn_kv_norm(h_t) the kept key rows:
+ *   logit[t, h] = u_t . G[h]                      G [H, d] = W_k,h^T qp_h / sqrt(dh) (the query bias term cancels in the softmax)
+ *   P = U [C_1; ...; C_H]^T  [n*Tk, H*D]         C_h = W_le W_o[:, h] W_v,h [D, d]
+ *   z[i] = sum_h sum_t softmax_t(logit[i*Tk + t, h]) P[i*Tk + t, h*D : (h+1)*D] + cz     (cz = W_le (W_o b_v + b_o + q) + b_le)
+ * mdg_layernorm_logits is mdg_layernorm_packed that also writes logits [rows, H] (H <= 64) from the normalised fp32 rows;
+ * y_packed may be NULL (fp32 rows only, any precision), y may be NULL (image only); y and the image equal mdg_layernorm_packed's
+ * bit for bit.  mdg_xattn_fold_pool writes z [n, D] from P and the logits (Tk <= 32, D even and <= 256, fixed summation order). */
+int mdg_layernorm_logits(const float* x, int64_t ldx, const float* gamma, const float* beta, float* y, int64_t ldy, int64_t rows,
+                         int64_t d, float eps, int precision, void* y_packed, size_t y_packed_bytes, const float* G, int H,
+                         float* logits, void* stream);
+int mdg_xattn_fold_pool(const float* P, int64_t ldp, const float* logits, int64_t ldl, const float* cz, float* z, int64_t ldz,
+                        int64_t n, int Tk, int H, int D, void* stream);
 
 /* y = x / max(||x||_2, 1e-12) per row (F.normalize; models.py:849-850,858-859,872,892-893,947-949). d % 4 == 0. */
 int mdg_l2_normalize(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t d, void* stream);

@@ -380,6 +380,48 @@ __global__ __launch_bounds__(256) void xattn_pool_kernel(const float* __restrict
   }
 }
 
+// Folded cross-attention pooling (models.py:422-443 in eval mode, pre-norm; TransformerFusion._x_attn_pool_folded): the key
+// logits and the key rows already carried through V, out_proj and latent2embed, per head:
+//   z[i, :] = sum_h sum_t a[t, h] P[i*Tk + t, h*D : (h+1)*D] + cz,   a[., h] = softmax over the Tk keys of logits[i*Tk + ., h].
+// One wave per drug, lanes span the D outputs two columns each (D even, <= 256); every lane forms the Tk*H weights itself.
+// Fixed summation order (head-major, then key), no atomics: bit-identical from one launch to the next.
+__global__ __launch_bounds__(256) void xattn_fold_pool_kernel(const float* __restrict__ P, int64_t ldp, const float* __restrict__ logits,
+                                                              int64_t ldl, const float* __restrict__ cz, float* __restrict__ z, int64_t ldz,
+                                                              int64_t n, int Tk, int H, int D) {
+  const int lane = threadIdx.x & 63;
+  const int64_t drug = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (drug >= n) return;
+  float acc[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+  const float* lrow = logits + drug * Tk * ldl;
+#pragma unroll 1
+  for (int h = 0; h < H; ++h) {
+    float m = -INFINITY;
+    for (int t = 0; t < Tk; ++t) m = fmaxf(m, lrow[t * ldl + h]);
+    float s = 0.f;
+    for (int t = 0; t < Tk; ++t) s += expf(lrow[t * ldl + h] - m);
+    const float inv = 1.0f / s;
+#pragma unroll 1
+    for (int t = 0; t < Tk; ++t) {
+      const float a = expf(lrow[t * ldl + h] - m) * inv;
+      const float* pr = P + (drug * Tk + t) * ldp + static_cast<int64_t>(h) * D;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int c = 2 * (lane + 64 * u);
+        if (c < D) {
+          const float2 pv = *reinterpret_cast<const float2*>(pr + c);
+          acc[u][0] += a * pv.x;
+          acc[u][1] += a * pv.y;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int c = 2 * (lane + 64 * u);
+    if (c < D) *reinterpret_cast<float2*>(z + drug * ldz + c) = make_float2(acc[u][0] + cz[c], acc[u][1] + cz[c + 1]);
+  }
+}
+
 // Backward of the one-query cross-attention pooling: one wave per (drug, head); lane j keeps the score, weight and
 // weight gradient of key j (Tk <= 32).  dq is written per drug ([n, d]) and reduced over drugs by the caller
 // (the query is a shared parameter): fixed summation order, no atomics.
@@ -655,6 +697,20 @@ extern "C" int mdg_xattn_pool_dropout(const float* q_proj, const float* kv_proj,
 extern "C" int mdg_xattn_pool(const float* q_proj, const float* kv_proj, int64_t ld, float* out, int64_t ldo, int64_t n, int Tk,
                               int H, int dh, void* stream) {
   return mdg_xattn_pool_dropout(q_proj, kv_proj, ld, out, ldo, n, Tk, H, dh, 0.f, 0, stream);
+}
+
+extern "C" int mdg_xattn_fold_pool(const float* P, int64_t ldp, const float* logits, int64_t ldl, const float* cz, float* z, int64_t ldz,
+                                   int64_t n, int Tk, int H, int D, void* stream) {
+  MDG_CHECK_ARG(n >= 0 && Tk >= 1 && Tk <= 32 && H >= 1 && H <= 64 && D >= 2 && D <= 256 && D % 2 == 0,
+                "mdg_xattn_fold_pool: bad shape (Tk=%d H=%d D=%d)", Tk, H, D);
+  if (n == 0) return MDG_OK;
+  MDG_CHECK_ARG(P && logits && cz && z && ldp >= static_cast<int64_t>(H) * D && ldl >= H && ldz >= D, "mdg_xattn_fold_pool: bad pointers / strides");
+  MDG_CHECK_ARG(ldp % 2 == 0 && ldz % 2 == 0 && reinterpret_cast<uintptr_t>(P) % 8 == 0 && reinterpret_cast<uintptr_t>(z) % 8 == 0,
+                "mdg_xattn_fold_pool: P and z need 8-byte aligned rows");
+  hipLaunchKernelGGL(xattn_fold_pool_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n, 4))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     P, ldp, logits, ldl, cz, z, ldz, n, Tk, H, D);
+  MDG_CHECK_LAUNCH("mdg_xattn_fold_pool");
+  return MDG_OK;
 }
 
 extern "C" int mdg_xattn_pool_bwd(const float* q_proj, const float* kv_proj, int64_t ld, const float* dout, int64_t lddo, float* dkv,

@@ -1124,16 +1124,12 @@ __device__ __forceinline__ void ln_row_stats(const float* __restrict__ xr, int l
   rstd = 1.0f / sqrtf(mdg_wave_sum(q) / d + eps);
 }
 
+// the normalised row from its statistics, written as fp32 (y non-null) and / or as operand image (img_hi non-null); v is left
+// holding the normalised row (what layernorm_logits_kernel dots with G)
 template <int VEC>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
-                                                        const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
-                                                        int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  f32x4 v[VEC];
-  float mean, rstd;
-  ln_row_stats<VEC>(x + row * ldx, lane, d, eps, v, mean, rstd);
+__device__ __forceinline__ void ln_apply_store(f32x4 (&v)[VEC], int lane, int d, float mean, float rstd, const float* __restrict__ g,
+                                               const float* __restrict__ b, float* __restrict__ y, int64_t ldy, int64_t row,
+                                               char* __restrict__ img_hi, int img_x3) {
   float* yr = y + row * ldy;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -1143,6 +1139,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       f32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
+      v[i] = o;
       if (y) *reinterpret_cast<f32x4*>(yr + c) = o;
       if (img_hi) {                                      // the next dense block's operand image (what its pre-pass would write)
         bf16x4 hi, lo;
@@ -1163,6 +1160,55 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       }
     }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
+                                                        const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
+                                                        int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  f32x4 v[VEC];
+  float mean, rstd;
+  ln_row_stats<VEC>(x + row * ldx, lane, d, eps, v, mean, rstd);
+  ln_apply_store<VEC>(v, lane, d, mean, rstd, g, b, y, ldy, row, img_hi, img_x3);
+}
+
+// layernorm_kernel plus H dot products of each normalised fp32 row, taken while the row is in registers:
+// logits[row, h] = sum_c LN(x)[row, c] * G[h, c] (the folded cross-attention pooling's key logits; H <= 64).
+// The row's fp32 output and image are those of layernorm_kernel bit for bit; the dot order is fixed (lane-major, then the
+// wave's butterfly), so the logits are bit-identical from one launch to the next.
+template <int VEC>
+__global__ __launch_bounds__(256) void layernorm_logits_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
+                                                               const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
+                                                               int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3,
+                                                               const float* __restrict__ G, int H, float* __restrict__ logits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  f32x4 v[VEC];
+  float mean, rstd;
+  ln_row_stats<VEC>(x + row * ldx, lane, d, eps, v, mean, rstd);
+  ln_apply_store<VEC>(v, lane, d, mean, rstd, g, b, y, ldy, row, img_hi, img_x3);
+  float mine = 0.f;                                      // lane h keeps logit h: one coalesced store per row
+#pragma unroll 1
+  for (int h = 0; h < H; ++h) {
+    const float* gh = G + static_cast<int64_t>(h) * d;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      const int c = (lane + 64 * i) * 4;
+      if (c < d) {
+        const f32x4 gg = *reinterpret_cast<const f32x4*>(gh + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += v[i][e] * gg[e];
+      }
+    }
+    s = mdg_wave_sum(s);
+    if (lane == h) mine = s;
+  }
+  if (lane < H) logits[row * H + lane] = mine;
 }
 
 // LayerNorm's row statistics only: rstd[row] = 1 / sqrt(var + eps), the same reduction as layernorm_kernel (mdg_row_rstd)
@@ -1681,7 +1727,8 @@ extern "C" int mdg_linear_tn_packed_g(const void* gt_image, const float* x, int6
 }
 
 static int layernorm_impl(const float* x, int64_t ldx, const float* gamma, const float* beta, float* y, int64_t ldy, int64_t rows, int64_t d,
-                          float eps, int precision, void* y_packed, size_t y_packed_bytes, void* stream) {
+                          float eps, int precision, void* y_packed, size_t y_packed_bytes, void* stream, const float* G = nullptr, int H = 0,
+                          float* logits = nullptr) {
   MDG_CHECK_ARG(rows >= 0 && d > 0, "mdg_layernorm: bad shape");
   if (rows == 0) return MDG_OK;
   MDG_CHECK_ARG(x && gamma && beta && (y || y_packed), "mdg_layernorm: null pointer");
@@ -1704,6 +1751,14 @@ static int layernorm_impl(const float* x, int64_t ldx, const float* gamma, const
   const dim3 grid(static_cast<unsigned>(mdg_cdiv(rows, 4)));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int di = static_cast<int>(d);
+  if (G) {
+    if (d <= 256) hipLaunchKernelGGL(layernorm_logits_kernel<1>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
+    else if (d <= 512) hipLaunchKernelGGL(layernorm_logits_kernel<2>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
+    else if (d <= 1024) hipLaunchKernelGGL(layernorm_logits_kernel<4>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
+    else hipLaunchKernelGGL(layernorm_logits_kernel<8>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
+    MDG_CHECK_LAUNCH("mdg_layernorm_logits");
+    return MDG_OK;
+  }
   if (d <= 256) hipLaunchKernelGGL(layernorm_kernel<1>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3);
   else if (d <= 512) hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3);
   else if (d <= 1024) hipLaunchKernelGGL(layernorm_kernel<4>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3);
@@ -1723,6 +1778,17 @@ extern "C" int mdg_layernorm_packed(const float* x, int64_t ldx, const float* ga
                                     int64_t d, float eps, int precision, void* y_packed, size_t y_packed_bytes, void* stream) {
   MDG_CHECK_ARG(y_packed, "mdg_layernorm_packed: null image");
   return layernorm_impl(x, ldx, gamma, beta, y, ldy, rows, d, eps, precision, y_packed, y_packed_bytes, stream);
+}
+
+// mdg_layernorm / mdg_layernorm_packed that also writes logits[r, h] = LN(x)[r, :] . G[h, :] (G [H, d] fp32, H <= 64, logits [rows, H])
+// from the normalised fp32 row while it is in registers.  y_packed null: the fp32 rows only (any precision); y null: the image only.
+// y and the image are bit-identical to what mdg_layernorm_packed writes.
+extern "C" int mdg_layernorm_logits(const float* x, int64_t ldx, const float* gamma, const float* beta, float* y, int64_t ldy, int64_t rows,
+                                    int64_t d, float eps, int precision, void* y_packed, size_t y_packed_bytes, const float* G, int H,
+                                    float* logits, void* stream) {
+  MDG_CHECK_ARG(G && logits && H >= 1 && H <= 64, "mdg_layernorm_logits: G / logits null or H = %d not in [1, 64]", H);
+  MDG_CHECK_ARG(mdg_aligned16(G) && d % 4 == 0, "mdg_layernorm_logits: G must be 16-byte aligned (d multiple of 4)");
+  return layernorm_impl(x, ldx, gamma, beta, y, ldy, rows, d, eps, precision, y_packed, y_packed_bytes, stream, G, H, logits);
 }
 
 // LayerNorm's row statistics alone (no normalised rows): rstd[r] = 1 / sqrt(var(x[r, :d]) + eps), bit-identical to the factor

@@ -1100,6 +1100,29 @@ def compose_qkv0(We, be, Wq, bq, norm=None):
     return Wg @ (We - We.mean(0, keepdim=True)), Wg @ (be - be.mean()), Wq @ b1 + bq
 
 
+def compose_xattn_pool(query, q_norm, Wi, bi, Wo, bo, Wle, ble, H: int):
+    """fp64 fold of the eval-mode cross-attention pooling (models.py:422-443, pre-norm) through V, out_proj, the query residual and
+    latent2embed.  query [1, d], q_norm = (gamma, beta, eps) of x_attn_query_norm or None, in_proj (Wi [3d, d], bi), out_proj (Wo, bo),
+    latent2embed (Wle [D, d], ble), H heads -> (C [H*D, d], G [H, d], c_z [D]) such that for the kv-normed key rows u_t of one drug
+        z = sum_h sum_t softmax_t(u_t . G[h]) (u_t C_h^T) + c_z,   C_h = C[h*D:(h+1)*D] = W_le W_o[:, h] W_v,h,
+        G[h] = W_k,h^T qp_h / sqrt(dh),   c_z = W_le (W_o b_v + b_o + q) + b_le   (qp = W_q q + b_q, q = LN_q(query)).
+    The key bias adds qp_h . b_k,h / sqrt(dh) to every logit of head h and cancels in the softmax; the weights of a head sum to one,
+    which carries b_v through.  (W_le W_o) is formed first, then one [D, dh] x [dh, d] product per head: ~2 D d^2 flops, not d^3."""
+    f8 = torch.float64
+    query, Wi, bi, Wo, bo, Wle, ble = (t.detach().to(f8) for t in (query, Wi, bi, Wo, bo, Wle, ble))
+    d, D = Wo.shape[0], Wle.shape[0]
+    dh = d // H
+    q = query.reshape(-1)
+    if q_norm is not None:
+        g, b, eps = q_norm
+        q = (q - q.mean()) / torch.sqrt(q.var(unbiased=False) + eps) * g.detach().to(f8) + b.detach().to(f8)
+    qp = Wi[:d] @ q + bi[:d]
+    G = (Wi[d:2 * d].reshape(H, dh, d) * qp.reshape(H, dh, 1)).sum(1) / math.sqrt(dh)
+    A = Wle @ Wo                                                                    # [D, d]
+    C = torch.einsum("ahk,hkc->hac", A.reshape(D, H, dh), Wi[2 * d:].reshape(H, dh, d)).reshape(H * D, d)
+    return C, G, Wle @ (Wo @ bi[2 * d:] + bo + q) + ble
+
+
 class TransformerFusion(nn.Module):
     """madrigal/models/models.py:352-455.  Holds a stock ``nn.TransformerEncoder`` / ``nn.MultiheadAttention``
     ONLY for their parameters (identical state_dict keys; ``transformer_encoder.layers[-1].self_attn`` stays
@@ -1138,6 +1161,8 @@ class TransformerFusion(nn.Module):
         self.last_attention_weights = None
         # eval path: layer 0's QKV block from the token rows through the composed weights (_qkv0); False: norm1 -> in_proj on h
         self.compose_layer0 = True
+        # eval path: the x-attn pooling folded through V, out_proj and latent2embed (_x_attn_pool_folded); False: K|V block -> pool
+        self.compose_pool = True
 
     # ---- layer 0's QKV block with embed2latent and norm1 folded into its weights ---------------------
     def _qkv0(self, L, tokens, h):
@@ -1276,8 +1301,40 @@ class TransformerFusion(nn.Module):
             return _linT(h, self.latent2embed.weight, self.latent2embed.bias)
         raise NotImplementedError(f"transformer_agg={agg!r} in training mode (the shipped configs train with 'x-attn')")
 
+    def _pool_folds(self, Tk) -> bool:
+        """Whether the eval-mode x-attn pooling takes the folded path: pre-norm (post-norm applies LN_q after the residual, which is not
+        linear), no forward hooks on x_attn_mha_layer, and a fold no more expensive than the K|V block it replaces (H*D <= 2d)."""
+        D = self.latent2embed.out_features
+        return (self.compose_pool and self.norm_first and _state["precision"] in ("f32", "bf16x3", "bf16")
+                and not len(self.x_attn_mha_layer._forward_hooks) and self.num_heads * D <= 2 * self.latent_dim
+                and D % 2 == 0 and D <= 256 and 1 <= Tk <= 32 and self.num_heads <= 64 and self.latent_dim % 4 == 0)
+
+    def _x_attn_pool_folded(self, h_keys, n, Tk):
+        """The pooling with everything after x_attn_kv_norm folded into fixed weights (compose_xattn_pool): the norm kernel writes the
+        H key logits of each row beside its operand image, one product P = U C^T [n*Tk, H*D] replaces the K|V block, and
+        ops.xattn_fold_pool forms z from the per-head softmax over the Tk keys.  C, G, c_z and C's image are rebuilt only when a
+        source parameter changes."""
+        mha, prec, ln, qn = self.x_attn_mha_layer, _state["precision"], self.x_attn_kv_norm, self.x_attn_query_norm
+
+        def build():
+            C, G, c_z = (t.to(torch.float32).contiguous() for t in compose_xattn_pool(
+                self.x_attn_query, (qn.weight, qn.bias, qn.eps), mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
+                mha.out_proj.bias, self.latent2embed.weight, self.latent2embed.bias, self.num_heads))
+            return C, G, c_z, ops.pack_operand(C, prec)
+        srcs = (self.x_attn_query, qn.weight, qn.bias, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+                self.latent2embed.weight, self.latent2embed.bias)
+        C, G, c_z, C_img = _cached(self, ("x_attn_fold", prec), srcs, build)
+        u, img, logits = ops.layernorm_logits(h_keys, ln.weight, ln.bias, ln.eps, G, prec)
+        if img is not None:
+            P = ops.linear_packed(img, h_keys.shape[0], C, precision=prec, weight_image=C_img)
+        else:
+            P = ops.linear(u, C, precision=prec, weight_image=C_img)
+        return ops.xattn_fold_pool(P, logits, c_z, n, Tk)
+
     def _x_attn_pool(self, h_keys, n, Tk):
         """Cross-attention pooling over the (already selected) key tokens h_keys [n*Tk, d] (models.py:422-443)."""
+        if self._pool_folds(Tk):
+            return self._x_attn_pool_folded(h_keys, n, Tk)
         d, H, dh = self.latent_dim, self.num_heads, self.head_dim
         mha = self.x_attn_mha_layer
         w, b = mha.in_proj_weight.detach(), mha.in_proj_bias.detach()

@@ -385,6 +385,32 @@ def layernorm_packed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     return y, img
 
 
+def layernorm_logits(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, G: torch.Tensor, precision):
+    """``layernorm_packed`` of a 2-D ``x`` [R, d] plus logits [R, H] = LN(x) G^T, formed from the normalised fp32 rows inside the
+    norm kernel (G [H, d] fp32, H <= 64) -> (y, image, logits).  As in ``layernorm_packed(.., want_fp32=False)``: y is None when the
+    image exists, image is None where the arithmetic mode or the width takes none (then y holds the rows)."""
+    forward_only(x, weight, bias, G)
+    x2 = x if (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.is_cuda and x.dtype == torch.float32) else _rows2d(x, "x")[0]
+    R, d = x2.shape
+    G = _f32_cuda(G, "G", 2)
+    if G.shape[1] != d or not 1 <= G.shape[0] <= 64:
+        raise ValueError(f"layernorm_logits: G must be [H <= 64, {d}], got {tuple(G.shape)}")
+    H = G.shape[0]
+    prec = _prec(precision)
+    logits = torch.empty((R, H), dtype=torch.float32, device=x2.device)
+    if prec == PREC_F32 or d % 64:
+        y, img, nbytes = torch.empty((R, d), dtype=torch.float32, device=x2.device), None, 0
+    else:
+        nbytes = int(lib().mdg_pack_operand_bytes(_c64(R), _c64(d), _c(prec)))
+        y, img = None, torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
+    if R == 0:
+        return y, img, logits
+    check(lib().mdg_layernorm_logits(_ptr(x2), _c64(x2.stride(0)), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), _ptr(y),
+                                     _c64(d), _c64(R), _c64(d), _f(eps), _c(prec), _ptr(img), ctypes.c_size_t(nbytes), _ptr(G), _c(H),
+                                     _ptr(logits), _stream(x2)), "mdg_layernorm_logits")
+    return y, img, logits
+
+
 def linear_packed(x_img: torch.Tensor, M: int, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act=None,
                   residual: Optional[torch.Tensor] = None, alpha: float = 1.0, beta: float = 1.0, precision="bf16x3",
                   out: Optional[torch.Tensor] = None, weight_image: Optional[torch.Tensor] = None, cache_weight: bool = True) -> torch.Tensor:
@@ -567,6 +593,24 @@ def xattn_pool(q_proj: torch.Tensor, kv_proj: torch.Tensor, n: int, Tk: int, H: 
     check(lib().mdg_xattn_pool_dropout(_ptr(q), _ptr(kv), _c64(kv.stride(0)), _ptr(out), _c64(d), _c64(n), _c(Tk), _c(H), _c(dh),
                                        _f(p_drop), ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(kv)), "mdg_xattn_pool")
     return out
+
+
+def xattn_fold_pool(P: torch.Tensor, logits: torch.Tensor, c_z: torch.Tensor, n: int, Tk: int) -> torch.Tensor:
+    """Folded cross-attention pooling (mdg_xattn_fold_pool): P [n*Tk, H*D] (key rows through V, out_proj and latent2embed, head-major
+    column blocks), logits [n*Tk, H], c_z [D] -> z [n, D] = sum_h sum_t softmax_t(logits[., h]) P[., h*D:(h+1)*D] + c_z."""
+    P, logits, c_z = _f32_cuda(P, "P", 2), _f32_cuda(logits, "logits", 2), _f32_cuda(c_z.reshape(-1), "c_z", 1)
+    D = c_z.numel()
+    H = logits.shape[1]
+    if P.shape != (n * Tk, H * D) or logits.shape[0] != n * Tk:
+        raise ValueError(f"xattn_fold_pool: expected P [{n * Tk},{H * D}] and logits [{n * Tk},{H}], got {tuple(P.shape)} and {tuple(logits.shape)}")
+    if P.device != logits.device or P.device != c_z.device:
+        raise ValueError("xattn_fold_pool: P, logits and c_z must be on one device")
+    if P.stride(0) % 2 or P.data_ptr() % 8:
+        P = P.contiguous()
+    z = torch.empty((n, D), dtype=torch.float32, device=P.device)
+    check(lib().mdg_xattn_fold_pool(_ptr(P), _c64(P.stride(0)), _ptr(logits), _c64(logits.stride(0)), _ptr(c_z), _ptr(z), _c64(D), _c64(n), _c(Tk),
+                                    _c(H), _c(D), _stream(P)), "mdg_xattn_fold_pool")
+    return z
 
 
 def xattn_pool_bwd(q_proj: torch.Tensor, kv_proj: torch.Tensor, dout: torch.Tensor, n: int, Tk: int, H: int, dh: int,
