@@ -329,6 +329,31 @@ int mdg_label_metrics(const float* pred, const float* target, const int64_t* lab
                       int64_t k, double k_frac, float threshold, double* values, int64_t* count, int64_t* pos, int64_t* k_eff,
                       int* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------- pretraining retrieval metrics ---- */
+
+/* Match counts of two views X, Y fp32 [n,128] (row-major, 16-byte aligned, 1 <= n <= 65536) of the same n drugs; the true
+ * match of row i is column i.  Replaces the CPU torch sweeps of madrigal/evaluate/evaluate.py:406-450
+ * (get_inst_dist_topk_accuracy: cosine matrix + torch.topk), madrigal/evaluate/eval_utils.py:159-174
+ * (stacked_inst_dist_topk_accuracy on the [2n,2n-1] stacked similarities), :232-247 (foscttm, a Python loop over rows) and
+ * :153-156 (alignment_loss).  With x^ = x/|x| and G = X Y^T (one fp32 Gram, exact fp32 MFMA products):
+ *   cos_row[i]  = #{j != i : x^_i.y^_j > x^_i.y^_i}     cos_col[j] = #{i != j : x^_i.y^_j > x^_j.y^_j}
+ *   same_x[i]   = #{b != i : x^_i.x^_b > x^_i.y^_i}     same_y[i]  = #{b != i : y^_i.y^_b > x^_i.y^_i}
+ *   dist_row[i] = #{j : |x_i - y_j| < |x_i - y_i|}      dist_col[j] = #{i : |x_i - y_j| < |x_j - y_j|}   (raw embeddings)
+ *   align[i]    = |x^_i - y^_i|^2 (fp32)
+ * Ties with the true match do not count against it (strict comparisons: ties count as hits); the true match is excluded by
+ * index.  All outputs int32 [n] except align.  status int32 [1]: OR of 1 (NaN / inf input or squared norm), 2 (zero-norm row).
+ * Deterministic: integer counts, no atomics on them; bit-identical from run to run. */
+size_t mdg_pair_match_counts_workspace_bytes(int64_t n);
+int mdg_pair_match_counts(const float* x, const float* y, int64_t n, int64_t d, int* cos_row, int* cos_col, int* same_x, int* same_y,
+                          int* dist_row, int* dist_col, float* align, int* status, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* uniform_loss (madrigal/evaluate/eval_utils.py:147-150, torch.pdist over all rows): out fp32 [1] =
+ * log(mean_{i<j} exp(-t |x^_i - x^_j|^2)) over X fp32 [m,128] (2 <= m <= 65536), |x^_i - x^_j|^2 = 2 - 2 x^_i.x^_j.  fp32 sums per
+ * 128 x 128 tile, fp64 across tiles in a fixed order: bit-identical from run to run.  status as above. */
+size_t mdg_pair_uniformity_workspace_bytes(int64_t m);
+int mdg_pair_uniformity(const float* x, int64_t m, int64_t d, float t, float* out, int* status, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* ---------------------------------------------------------------------- rank normalisation ---- */
 
 size_t mdg_rank_normalize_workspace_bytes(int64_t n_outcomes, int64_t N);

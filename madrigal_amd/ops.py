@@ -1764,3 +1764,73 @@ def label_metrics(pred: torch.Tensor, target: torch.Tensor, label: torch.Tensor,
     if st:
         raise ValueError("label_metrics: " + "; ".join(msg for bit, msg in _LABEL_METRIC_STATUS if st & bit))
     return {"values": values, "count": count, "pos": pos, "k_eff": k_eff}
+
+
+# ------------------------------------------------------------------------------- pretraining retrieval metrics
+PAIR_MATCH_COUNT_NAMES = ("cos_row", "cos_col", "same_x", "same_y", "dist_row", "dist_col")
+_PAIR_STATUS = ((1, "holds a NaN or infinite value"), (2, "has a zero-norm row (its cosines would be NaN)"))
+
+
+def _embeds_128(x: torch.Tensor, name: str) -> torch.Tensor:
+    x = _f32_cuda(x, name, 2)
+    if x.shape[1] != 128:
+        raise ValueError(f"{name}: expected [n,128] embeddings, got shape {tuple(x.shape)}")
+    return x
+
+
+def _pair_status(status: torch.Tensor, what: str) -> None:
+    st = int(status.item())
+    if st:
+        raise ValueError(f"{what}: input " + "; ".join(msg for bit, msg in _PAIR_STATUS if st & bit))
+
+
+def pair_match_counts(x: torch.Tensor, y: torch.Tensor) -> dict:
+    """Retrieval counts of two views of the same n drugs (csrc/retrieval.hip, mdg_pair_match_counts): row i of x and of y is
+    drug i, and column i is row i's true match.  x, y fp32 [n,128] on the GPU, 1 <= n <= 65536.
+
+    Returns device tensors: int32 [n] ``cos_row`` / ``cos_col`` (competitors with a strictly higher cosine than the true match,
+    per row of x / per row of y), ``same_x`` / ``same_y`` (same-view competitors of the stacked top-k), ``dist_row`` /
+    ``dist_col`` (FOSCTTM counts of strictly closer raw embeddings), and fp32 [n] ``align`` = |x^_i - y^_i|^2.  Ties count as
+    hits: a competitor equal to the true match is not counted, and the true match itself is excluded by index.  One host read
+    (the status word): raises ValueError for NaN / inf entries and zero-norm rows."""
+    x, y = _embeds_128(x, "x"), _embeds_128(y, "y")
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError(f"pair_match_counts: x and y must have one shape and device, got {tuple(x.shape)} and {tuple(y.shape)}")
+    n = int(x.shape[0])
+    if not 1 <= n <= 65536:
+        raise ValueError(f"pair_match_counts: need 1 <= n <= 65536 rows, got {n}")
+    dev = x.device
+    out = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in PAIR_MATCH_COUNT_NAMES}
+    out["align"] = torch.empty(n, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    lb = lib()
+    nbytes = lb.mdg_pair_match_counts_workspace_bytes(_c64(n))
+    ws = _workspace(nbytes, dev)
+    check(lb.mdg_pair_match_counts(_ptr(x), _ptr(y), _c64(n), _c64(128), *(_ptr(out[k]) for k in PAIR_MATCH_COUNT_NAMES), _ptr(out["align"]),
+                                   _ptr(status), _ptr(ws), ctypes.c_size_t(nbytes), _stream(x)), "mdg_pair_match_counts")
+    _pair_status(status, "pair_match_counts")
+    return out
+
+
+def pair_uniformity(x: torch.Tensor, t: float = 2.0) -> torch.Tensor:
+    """uniform_loss of madrigal/evaluate/eval_utils.py:147-150 (csrc/retrieval.hip, mdg_pair_uniformity): 0-dim fp32 device tensor
+    log(mean_{i<j} exp(-t |x^_i - x^_j|^2)) over x fp32 [m,128] on the GPU, 2 <= m <= 65536.  fp32 tile sums, fp64 across tiles in
+    a fixed order: bit-identical from run to run.  One host read (the status word): raises ValueError for NaN / inf entries and
+    zero-norm rows."""
+    x = _embeds_128(x, "x")
+    m = int(x.shape[0])
+    if not 2 <= m <= 65536:
+        raise ValueError(f"pair_uniformity: need 2 <= m <= 65536 rows, got {m}")
+    t = float(t)
+    if t != t:
+        raise ValueError("pair_uniformity: t is NaN")
+    dev = x.device
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    lb = lib()
+    nbytes = lb.mdg_pair_uniformity_workspace_bytes(_c64(m))
+    ws = _workspace(nbytes, dev)
+    check(lb.mdg_pair_uniformity(_ptr(x), _c64(m), _c64(128), ctypes.c_float(t), _ptr(out), _ptr(status), _ptr(ws), ctypes.c_size_t(nbytes),
+                                 _stream(x)), "mdg_pair_uniformity")
+    _pair_status(status, "pair_uniformity")
+    return out
