@@ -299,6 +299,8 @@ int mdg_gather_bce(const float* scores, int64_t n_labels, int64_t n_head, int64_
  *   MDG_RANKS_MSD        [1]  0: rank normalisation by the four-pass LSD sort only (what N > 5793 and flagged outcomes take)
  *   MDG_RANKS_GROUP      [8]  outcomes per launch group of the MSD path (its scratch is reused from group to group)
  *   MDG_RANKS_DIRECT     [0]  test hook: the LSD sort's last pass stores ranks one by one (what N > 16256 takes) at any N
+ *   MDG_GROUP_WALK       [0 = by size]  test hook of mdg_group_metrics: 1 every group by the one-thread walk, any other
+ *                        non-zero value every group by the 256-thread walk (no one-wave walk is built)
  *   MDG_BILINEAR_SYMMETRIC [1] 0: z_head == z_tail takes the general sweep instead of the symmetric one
  *   MDG_LINEAR_TILE      [0 = by shape]  128 / 256: force the dense block's tile shape
  *   MDG_LINEAR_RAWX      [1]  0: the 128-tile kernel's x through an operand pre-pass instead of rounded while staged
@@ -328,6 +330,25 @@ size_t mdg_label_metrics_workspace_bytes(int64_t n_triples, int64_t n_labels);
 int mdg_label_metrics(const float* pred, const float* target, const int64_t* label, int64_t n_triples, int64_t n_labels,
                       int64_t k, double k_frac, float threshold, double* values, int64_t* count, int64_t* pos, int64_t* k_eff,
                       int* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same 13 metrics per GROUP, for arbitrary group ids: the drug-stratified evaluation of
+ * madrigal/evaluate/predict.py:274-355 (get_drug_specific_scores: get_metrics per drug, one problem per (drug, label)).
+ *   pred, target, k, k_frac, threshold as above; group int64 [T] in [0, n_groups), 0 < T < 2^31, 0 < n_groups <= 2^31.
+ * Keys: score image in bits 0-31, target in bit 32, group in bits 33-63; the stable LSD sort takes 4 score passes and
+ * ceil(bits(n_groups - 1) / 8) group passes (ties inside a group in input order: the top-k tie rule above).  Only the groups
+ * present are reported, compact and ascending by group id; with cap = min(T, n_groups) the caller allocates group_id int64 [cap],
+ * values float64 [13, cap] (column j = the j-th present group), count / pos / k_eff int64 [cap], n_present int64 [1]; only the
+ * first *n_present columns are written.  The walk is picked per group: at most 32 triples by one thread walking serially (the
+ * same formulas), larger groups by the 256-thread walk of mdg_label_metrics (MDG_GROUP_WALK forces one of them).
+ * inner > 0: also outer_values float64 [13, ceil(n_groups / inner)] and outer_groups int64 [ceil(n_groups / inner)], the mean
+ * of each metric over the present groups of outer o = group / inner: an f64 sum in ascending group order divided once (numpy's
+ * mean(axis=0) over those rows, bit for bit), NaN and 0 for an outer without groups.  inner = 0: both may be null.
+ * status as above with 16 (group out of range) in place of 2.  Deterministic; no atomics except the status word. */
+size_t mdg_group_metrics_workspace_bytes(int64_t n_triples, int64_t n_groups);
+int mdg_group_metrics(const float* pred, const float* target, const int64_t* group, int64_t n_triples, int64_t n_groups, int64_t k,
+                      double k_frac, float threshold, int64_t inner, int64_t* group_id, double* values, int64_t* count, int64_t* pos,
+                      int64_t* k_eff, int64_t* n_present, double* outer_values, int64_t* outer_groups, int* status, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------- pretraining retrieval metrics ---- */
 

@@ -255,6 +255,28 @@ def make_labelled_triples(n_drugs: int, n_outcomes: int, n_pos: int, seed: int, 
             torch.from_numpy(tails.astype(np.int64)), torch.from_numpy(y))
 
 
+def make_eval_triples(n_head: int, n_tail: int, n_outcomes: int, n_pos: int, seed: int, between: bool = True):
+    """Labelled triples in the collator's val/test layout (madrigal/data/data.py:850-868): ``n_pos`` positives, then two negative
+    blocks aligned with them (negative i and i + n_pos belong to positive i, same label).  ``between``: the negatives keep the
+    positive's head and draw new tails (val/test_between); otherwise block 1 draws a new tail and block 2 a new head.  Heads
+    index [0, n_head), tails [0, n_tail).  Every head index has at least one positive (needs n_pos >= n_head).  Returns int64
+    label / head / tail and float32 pos_neg, each [3 * n_pos]."""
+    if n_pos < n_head:
+        raise ValueError(f"make_eval_triples: every head drug needs a positive, so n_pos >= n_head (got {n_pos} < {n_head})")
+    rng = np.random.default_rng([seed, 606])
+    lab = rng.integers(0, n_outcomes, size=n_pos)
+    h = rng.integers(0, n_head, size=n_pos)
+    h[rng.permutation(n_pos)[:n_head]] = np.arange(n_head)
+    t = rng.integers(0, n_tail, size=n_pos)
+    n1, n2 = rng.integers(0, n_tail, size=n_pos), rng.integers(0, n_tail if between else n_head, size=n_pos)
+    labels = np.concatenate([lab, lab, lab])
+    heads = np.concatenate([h, h, h if between else n2])
+    tails = np.concatenate([t, n1, n2 if between else t])
+    pos_neg = np.concatenate([np.ones(n_pos), np.zeros(2 * n_pos)]).astype(np.float32)
+    return (torch.from_numpy(labels.astype(np.int64)), torch.from_numpy(heads.astype(np.int64)),
+            torch.from_numpy(tails.astype(np.int64)), torch.from_numpy(pos_neg))
+
+
 def batch_to(batch: dict, device) -> dict:
     """Device move of a batch dict (numpy string arrays stay on the host)."""
     out = {}

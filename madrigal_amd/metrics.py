@@ -159,3 +159,81 @@ def get_metrics(preds, ys, labels, k=50, task: str = "multilabel", logger: Any =
     if verbose and average is not None:
         _print_metrics(names, vals, logger)
     return dict(zip(names, vals)), pos_samples
+
+
+_DRUG_MODES = ("test_between", "test_between_train")
+
+
+def drug_specific_metrics(preds, heads, tails, labels, pos_neg, n_head: int, mode: str = "test_between"):
+    """The metric part of madrigal/evaluate/predict.py:get_drug_specific_scores on the device -> (metrics, owners): ``metrics`` maps
+    the reference's names (k = 50, get_metrics order) to one np.float64 per drug of interest; ``owners`` (int64 numpy) are the
+    drugs' indices, all head indices (``test_between``) or the sorted tail indices of the positives (``test_between_train``).
+
+    preds: probabilities, and heads / tails / labels / pos_neg: the labelled triples, all CUDA tensors of one length T, in the
+    collator's val/test layout: positive i owns the negatives i and i + n_pos of the negative list (each keeps its own label).  A
+    drug's problems are its (drug, label) groups of positives, first negatives and second negatives, each macro-averaged over
+    labels with NaN propagating, as get_metrics(task="multiclass", average="macro", k=50) does per drug; one
+    ``ops.group_metrics`` call computes all of them (group id = owner rank * L + label, L = labels.max() + 1).
+    Raises ValueError where the reference fails: fewer than 2 * n_pos negatives (an IndexError there), a drug of interest
+    without positives, or a (drug, label) problem whose targets and rounded preds are all one class."""
+    from . import ops
+    if mode not in _DRUG_MODES:
+        raise NotImplementedError(f"drug_specific_metrics: mode must be one of {_DRUG_MODES}, got {mode!r}")
+    ts = (preds, heads, tails, labels, pos_neg)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        raise ValueError("drug_specific_metrics: preds, heads, tails, labels and pos_neg must be CUDA tensors")
+    T = int(preds.numel())
+    if any(int(t.numel()) != T for t in ts) or T == 0:
+        raise ValueError("drug_specific_metrics: preds, heads, tails, labels and pos_neg must be non-empty and of one length")
+    dev = preds.device
+    n_head = int(n_head)
+    is_pos = pos_neg.reshape(-1).bool()
+    pos_idx, neg_idx = torch.nonzero(is_pos).flatten(), torch.nonzero(~is_pos).flatten()
+    heads, tails, labels = (t.reshape(-1).to(torch.int64) for t in (heads, tails, labels))
+    owner = (heads if mode == "test_between" else tails)[pos_idx]
+    n_pos, n_neg = int(pos_idx.numel()), int(neg_idx.numel())
+    l_hi = int(labels.max()) if T else 0
+    L = l_hi + 1
+    if mode == "test_between":
+        drugs = np.arange(n_head, dtype=np.int64)
+        if n_pos and not bool(((owner >= 0) & (owner < n_head)).all()):
+            raise ValueError(f"drug_specific_metrics: a positive's head index lies outside [0, {n_head})")
+        rank = owner
+    else:
+        uniq, rank = torch.unique(owner, sorted=True, return_inverse=True)
+        drugs = uniq.cpu().numpy().astype(np.int64)
+    n_drugs = int(drugs.size)
+    if n_pos == 0:
+        if mode == "test_between_train":                              # no drug of interest: the reference's loop runs zero times
+            return {}, drugs
+        raise ValueError(f"drug {int(drugs[0]) if n_drugs else 0}: no positive triples (the reference's confusion_matrix(...).ravel() "
+                         "unpack fails on the empty problem)")
+    if n_neg < 2 * n_pos:                                             # the reference's negative gather runs off the end
+        short = rank[n_neg - n_pos:] if n_neg >= n_pos else rank
+        first = int(short.min())
+        raise ValueError(f"drug {int(drugs[first])}: its positives lack negatives ({n_neg} negatives for {n_pos} positives; "
+                         "the collator's layout has 2 per positive)")
+    if n_drugs * L > 2 ** 31:
+        raise ValueError(f"drug_specific_metrics: {n_drugs} drugs x {L} labels exceed 2^31 (drug, label) groups")
+    order = torch.cat([pos_idx, neg_idx[:2 * n_pos]])                 # positives, negative block 1, negative block 2
+    pred = preds.reshape(-1)[order].to(torch.float32)
+    target = torch.cat([torch.ones(n_pos, device=dev), torch.zeros(2 * n_pos, device=dev)])
+    group = rank.repeat(3) * L + labels[order]
+    r = ops.group_metrics(pred, target, group, n_drugs * L, k=50, threshold=0.5, inner=L)
+    n_groups = r["outer_groups"].cpu().numpy()
+    gid, pos, cnt = (r[x].cpu().numpy() for x in ("group_id", "pos", "count"))
+    acc = r["values"][10].cpu().numpy()
+    one_class = ((pos == 0) | (pos == cnt)) & (acc == 1.0)
+    bad_drug = np.flatnonzero(n_groups == 0)
+    first_empty = int(bad_drug[0]) if bad_drug.size else n_drugs
+    first_one = int(gid[np.argmax(one_class)] // L) if one_class.any() else n_drugs
+    if first_empty < n_drugs and first_empty <= first_one:
+        raise ValueError(f"drug {int(drugs[first_empty])}: no positive triples (the reference's confusion_matrix(...).ravel() "
+                         "unpack fails on the empty problem)")
+    if first_one < n_drugs:
+        j = int(np.argmax(one_class))
+        raise ValueError(f"drug {int(drugs[first_one])}, label {int(gid[j] % L)}: targets and rounded preds are all one class "
+                         "(the reference's confusion_matrix(...).ravel() unpack fails)")
+    vals = r["outer_values"].cpu().numpy()
+    names = _metric_names(50)
+    return {nm: [np.float64(v) for v in vals[m]] for m, nm in enumerate(names)}, drugs

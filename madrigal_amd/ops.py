@@ -1766,6 +1766,74 @@ def label_metrics(pred: torch.Tensor, target: torch.Tensor, label: torch.Tensor,
     return {"values": values, "count": count, "pos": pos, "k_eff": k_eff}
 
 
+_GROUP_METRIC_STATUS = ((1, "pred holds a NaN or infinite value"), (16, "a group id is outside [0, n_groups)"),
+                        (4, "target holds a value other than 0 and 1"), (8, "k resolves to 0 for a group (k * n_group < 1)"))
+
+
+def group_metrics(pred: torch.Tensor, target: torch.Tensor, group: torch.Tensor, n_groups: int, k=50, threshold: float = 0.5,
+                  inner: Optional[int] = None) -> dict:
+    """The metrics of ``label_metrics`` per group, for group ids in [0, n_groups) with n_groups up to 2^31 (csrc/eval_metrics.hip,
+    mdg_group_metrics): only the groups present are reported, ascending by id.
+
+    pred / target fp32 [T] (target 0 or 1), group int64 [T]; ``k`` as in ``label_metrics`` (a float resolves per group).  Returns
+    device tensors sliced to the n_present groups: ``group_id`` int64, ``values`` float64 [13, n_present] in the order of
+    LABEL_METRIC_NAMES, ``count`` / ``pos`` / ``k_eff`` int64.  With ``inner`` (an int > 0) also ``outer_values`` float64
+    [13, ceil(n_groups / inner)], the mean of each metric over the present groups of outer index group // inner (bit-equal to
+    numpy's mean(axis=0) over those columns; NaN where an outer has none) and ``outer_groups`` int64, the number of groups
+    averaged.  One host read (status and n_present): raises ValueError on a NaN / infinite pred, a group id out of range, a
+    target other than 0/1, or k resolving to 0."""
+    pred, target = _f32_cuda(pred, "pred", 1), _f32_cuda(target, "target", 1)
+    T = int(pred.numel())
+    if not (isinstance(group, torch.Tensor) and group.is_cuda and group.dtype == torch.int64 and group.dim() == 1 and group.numel() == T):
+        raise ValueError(f"group: expected int64 cuda [{T}]")
+    if target.numel() != T or pred.device != target.device or pred.device != group.device:
+        raise ValueError("group_metrics: pred, target and group must be [T] on one device")
+    if not 0 < T < 2 ** 31:
+        raise ValueError(f"group_metrics: need 0 < T < 2^31 triples, got {T}")
+    n_groups = int(n_groups)
+    if not 0 < n_groups <= 2 ** 31:
+        raise ValueError(f"group_metrics: need 0 < n_groups <= 2^31, got {n_groups}")
+    if isinstance(k, bool) or not isinstance(k, (int, float)):
+        raise ValueError(f"group_metrics: k must be an int or a float in (0, 1), got {k!r}")
+    if isinstance(k, float):
+        if not 0.0 < k < 1.0:
+            raise ValueError(f"group_metrics: a float k must lie in (0, 1), got {k}")
+        k_int, k_frac = 0, float(k)
+    else:
+        if k <= 0:
+            raise ValueError(f"group_metrics: k must be positive, got {k}")
+        k_int, k_frac = int(k), 0.0
+    if inner is not None and (isinstance(inner, bool) or not isinstance(inner, int) or inner <= 0):
+        raise ValueError(f"group_metrics: inner must be a positive int or None, got {inner!r}")
+    dev, cap = pred.device, min(T, n_groups)
+    group = group.contiguous()
+    group_id = torch.empty(cap, dtype=torch.int64, device=dev)
+    values = torch.empty(13, cap, dtype=torch.float64, device=dev)
+    count, pos, k_eff = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3))
+    meta = torch.zeros(2, dtype=torch.int64, device=dev)             # [0]: the status word (low 32 bits), [1]: n_present
+    outer_values = outer_groups = None
+    if inner is not None:
+        n_outer = -(-n_groups // inner)
+        outer_values = torch.empty(13, n_outer, dtype=torch.float64, device=dev)
+        outer_groups = torch.empty(n_outer, dtype=torch.int64, device=dev)
+    lb = lib()
+    nbytes = lb.mdg_group_metrics_workspace_bytes(_c64(T), _c64(n_groups))
+    ws = _workspace(nbytes, dev)
+    check(lb.mdg_group_metrics(_ptr(pred), _ptr(target), _ptr(group), _c64(T), _c64(n_groups), _c64(k_int), ctypes.c_double(k_frac),
+                               ctypes.c_float(threshold), _c64(inner or 0), _ptr(group_id), _ptr(values), _ptr(count), _ptr(pos),
+                               _ptr(k_eff), _vp(meta.data_ptr() + 8), _ptr(outer_values), _ptr(outer_groups), _ptr(meta), _ptr(ws),
+                               ctypes.c_size_t(nbytes), _stream(pred)), "mdg_group_metrics")
+    m = meta.cpu()
+    st, n_present = int(m.view(torch.int32)[0]), int(m[1])
+    if st:
+        raise ValueError("group_metrics: " + "; ".join(msg for bit, msg in _GROUP_METRIC_STATUS if st & bit))
+    out = {"group_id": group_id[:n_present], "values": values[:, :n_present], "count": count[:n_present], "pos": pos[:n_present],
+           "k_eff": k_eff[:n_present]}
+    if inner is not None:
+        out["outer_values"], out["outer_groups"] = outer_values, outer_groups
+    return out
+
+
 # ------------------------------------------------------------------------------- pretraining retrieval metrics
 PAIR_MATCH_COUNT_NAMES = ("cos_row", "cos_col", "same_x", "same_y", "dist_row", "dist_col")
 _PAIR_STATUS = ((1, "holds a NaN or infinite value"), (2, "has a zero-norm row (its cosines would be NaN)"))
