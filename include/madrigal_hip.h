@@ -50,7 +50,8 @@ enum mdg_bilinear_epilogue {
   MDG_EPI_STORE = 0,         /* out[l,i,j] = S            (raw logits, as the reference returns) */
   MDG_EPI_STORE_SIGMOID = 1, /* out[l,i,j] = sigmoid(S)   (train_ddi_batch.py:285)               */
   MDG_EPI_ROWSTATS = 2,      /* nothing is materialised: stats[l,i,0] = sum_j S, stats[l,i,1] =
-                                max_j S (roofline stress runs whose [L,N,N] cannot exist)        */
+                                max_j S (roofline stress runs whose [L,N,N] cannot exist; callers who
+                                want results rather than statistics: mdg_bilinear_topk)          */
   MDG_EPI_TRIKEYS = 3        /* for callers whose product is ranks (notebooks/normalize_scores.py:36-85 reads
                                 the strict lower triangle only): out[l,i,j] for j < i = the order-preserving
                                 uint32 key of S[l,i,j] (the bits mdg_rank_normalize sorts), the same value the
@@ -127,6 +128,26 @@ int mdg_bilinear_ensemble_sigmoid(const float* const* z_head_host, const float* 
                                   const float* const* w_sym_host, int n_models, float* out, int64_t ldo,
                                   int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision,
                                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* Per-row top-k of the all-pairs sweep: for every outcome l and head row i the k largest scores S[l,i,j] (the arithmetic of
+ * mdg_bilinear_allpairs' general sweep in `precision`, bit for bit in F32 / BF16X3; the 16-bit modes run the row-statistics
+ * sweep, whose fp32 sums are grouped differently: <= 2e-6 of the scale) over the ELIGIBLE tail columns j, and those columns.
+ * The screening product of the head -- "for this drug and outcome, which partners" -- without materialising [L,N,N]: what the
+ * reference looks up in its stored score / rank tensor (notebooks/quick_predictions.ipynb cell 8) and, in LOWER mode, the
+ * candidates of the pairs notebooks/normalize_scores.py:39-46 ranks.
+ *   vals [n_labels,n_head,k] fp32, idx [n_labels,n_head,k] int32; each row ordered by (score descending, column ascending),
+ *   which is also the tie rule for what is kept; a row with fewer than k eligible columns is padded with -inf / -1.
+ *   eligible: MDG_TOPK_ALL (two drug sets), MDG_TOPK_NOT_SELF (j != i), MDG_TOPK_LOWER (j < i, the strict lower triangle;
+ *   column tiles wholly on or above the diagonal are not computed); the last two need n_head == n_tail.
+ *   1 <= k <= mdg_bilinear_topk_max_k() (32); n_tail >= 1 and < 2^31 - 64; n_labels <= 65535 per call; D == 128.
+ * Scores must be finite (a NaN is never kept).  Workspace: the operand images of mdg_bilinear_allpairs (0 for F32).
+ * Deterministic: no atomics, the lists live in registers; bit-identical from launch to launch. */
+enum mdg_topk_eligible { MDG_TOPK_ALL = 0, MDG_TOPK_NOT_SELF = 1, MDG_TOPK_LOWER = 2 };
+int mdg_bilinear_topk_max_k(void);
+size_t mdg_bilinear_topk_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision, int k);
+int mdg_bilinear_topk(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx, int64_t n_head,
+                      int64_t n_tail, int64_t n_labels, int64_t D, int precision, int k, int eligible, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ dense blocks ---- */
 

@@ -1564,6 +1564,18 @@ class BilinearDDIScorer(nn.Bilinear):
         ops.forward_only(input1, input2)
         return ops.bilinear_allpairs(input1, input2, weight, precision=_state["precision"], epilogue=epilogue, out=out)
 
+    def topk(self, input1, input2, k: int, label_range: tuple = None, eligible: str = "all"):
+        """Extension (screening): ``(vals, idx)`` [L', n1, k] -- for every outcome and row of ``input1`` the ``k`` highest scores of
+        ``forward(input1, input2, label_range)`` over the eligible columns (``"all"``, ``"not_self"``: j != i, ``"lower"``: j < i) and
+        those columns, ordered by (score descending, column ascending), in the precision ``forward`` uses; nothing of
+        [L', n1, n2] is materialised (``ops.bilinear_topk``).  Inference only."""
+        ops.forward_only(input1, input2)
+        w = self.symmetric_weight()
+        if label_range is not None:
+            assert len(label_range) == 2
+            w = w[label_range[0]:label_range[1]]
+        return ops.bilinear_topk(input1, input2, w, k, eligible=eligible, precision=_state["precision"])
+
     def score_triples(self, input1, input2, plan: dict) -> torch.Tensor:
         """Extension (finetune step): scores of the plan's (label, head, tail) triples only, in the plan's
         label-sorted order, differentiable w.r.t. both embeddings and the weight (train_ddi_batch.py:285-286

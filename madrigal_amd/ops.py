@@ -136,6 +136,70 @@ def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
     return out
 
 
+TOPK_ELIGIBLE = {"all": 0, "not_self": 1, "lower": 2}
+
+
+def bilinear_topk_max_k() -> int:
+    """Largest ``k`` of ``bilinear_topk`` (at least 32)."""
+    return int(lib().mdg_bilinear_topk_max_k())
+
+
+def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, k: int, *, eligible: str = "all",
+                  precision="bf16x3", out=None):
+    """Per-row top-k of the all-pairs sweep: ``(vals [L,Nh,k] fp32, idx [L,Nh,k] int32)``, for every outcome and head row the
+    ``k`` largest scores ``z_head[i]^T W_sym[l] z_tail[j]`` over the eligible tail columns and those columns, ordered by
+    (score descending, column ascending); rows with fewer than ``k`` eligible columns are padded with ``-inf`` / ``-1``.
+    Nothing of [L,Nh,Nt] is materialised.
+
+    ``eligible``: ``"all"`` (two drug sets), ``"not_self"`` (``j != i``), ``"lower"`` (``j < i``, the strict lower triangle the
+    rank normalisation reads; tiles on or above the diagonal are not computed); the last two need ``Nh == Nt``.  The scores
+    are those of ``bilinear_allpairs``'s general sweep in the same ``precision`` ("f32" / "bf16x3": bit for bit; "bf16" / "f16":
+    the row-statistics sweep, fp32 sums grouped differently, <= 2e-6 of the scale).  ``out``: optional ``(vals, idx)`` pair."""
+    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
+    D = zh.shape[1]
+    if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
+        raise ValueError(f"feature dims disagree: z_head {tuple(zh.shape)}, z_tail {tuple(zt.shape)}, w {tuple(w.shape)}")
+    if zh.device != zt.device or zh.device != w.device:
+        raise ValueError("z_head, z_tail and w_sym must be on the same device")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
+    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    L_ = lib()
+    max_k = int(L_.mdg_bilinear_topk_max_k())
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
+        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
+    L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    shape = (L, Nh, k)
+    if out is None:
+        vals = torch.empty(shape, dtype=torch.float32, device=zh.device)
+        idx = torch.empty(shape, dtype=torch.int32, device=zh.device)
+    else:
+        vals, idx = out
+        for t, dt, name in ((vals, torch.float32, "out[0]"), (idx, torch.int32, "out[1]")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous {dt} GPU tensor of shape {shape}")
+    if vals.numel() == 0:
+        return vals, idx
+    if Nt == 0:                                  # no column at all: every row is padding
+        vals.fill_(float("-inf"))
+        idx.fill_(-1)
+        return vals, idx
+    # the grid's y extent caps one call at 65535 outcomes; chunk above that
+    for lo in range(0, L, 65535):
+        hi = min(L, lo + 65535)
+        nbytes = L_.mdg_bilinear_topk_workspace_bytes(_c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec, int(k))
+        ws = _workspace(nbytes, zh.device)
+        check(L_.mdg_bilinear_topk(_ptr(zh), _ptr(zt), _vp(w.data_ptr() + lo * D * D * 4), _vp(vals.data_ptr() + lo * Nh * k * 4),
+                                   _vp(idx.data_ptr() + lo * Nh * k * 4), _c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec, int(k),
+                                   TOPK_ELIGIBLE[eligible], _ptr(ws), ctypes.c_size_t(nbytes), _stream(zh)),
+              "mdg_bilinear_topk")
+    return vals, idx
+
+
 ENSEMBLE_PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}
 
 

@@ -172,6 +172,152 @@ def rank_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int]
     return ops.rank_normalize(keys, max_workspace_bytes=max_workspace_bytes)
 
 
+def _outcomes(model, label_range) -> Tuple[int, int]:
+    dec = model.decoder
+    L_all = dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
+    lo, hi = (0, L_all) if label_range is None else label_range
+    if not (0 <= lo <= hi <= L_all):
+        raise ValueError(f"label_range {label_range} outside [0, {L_all}]")
+    return lo, hi
+
+
+@torch.no_grad()
+def top_partners(model, z: torch.Tensor, k: int, label_range: Optional[Tuple[int, int]] = None, drug_rows=None,
+                 max_temp_bytes: int = 1 << 30):
+    """The ``k`` highest-scoring partners of every drug per outcome -> ``(vals, idx)`` [L', n, k] (fp32, int32): row i of
+    outcome l holds the k largest S[l, i, j] over j != i and those j, ordered by (score descending, j ascending); padded with
+    -inf / -1 when k > N - 1.  What the reference looks up in its stored [L,N,N] tensor (notebooks/quick_predictions.ipynb cell 8),
+    without that tensor: ``decoder.topk`` keeps the lists inside the sweep.  ``z`` from ``generate_embeddings``.
+
+    ``drug_rows``: only these drugs (indices into z; n = their number) -- the sweep still visits every drug, and the lists of
+    ``drug_rows`` are picked from outcome chunks whose temporaries ([c, N, k] values and indices) stay under ``max_temp_bytes``.
+    Without ``drug_rows`` the kernel writes straight into the result and there is no temporary.  The result itself is the
+    caller's: L' * n * k * 8 bytes (1 024 outcomes x 100 352 drugs x k = 8: 6.6 GB).
+    Multi-GPU: pass the outcome shard the rank owns as ``label_range``; no collective is involved."""
+    lo, hi = _outcomes(model, label_range)
+    N = z.shape[0]
+    rows = _index(drug_rows, N, "drug_rows", z.device)
+    if rows is None:
+        return model.decoder.topk(z, z, k, (lo, hi), eligible="not_self")
+    n = int(rows.numel())
+    vals = torch.empty((hi - lo, n, k), dtype=torch.float32, device=z.device)
+    idx = torch.empty((hi - lo, n, k), dtype=torch.int32, device=z.device)
+    chunk = max(1, int(max_temp_bytes) // max(N * k * 8, 1))
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        v, i = model.decoder.topk(z, z, k, (s, e), eligible="not_self")
+        vals[s - lo:e - lo] = v[:, rows]
+        idx[s - lo:e - lo] = i[:, rows]
+    return vals, idx
+
+
+def _best_pairs(v: torch.Tensor, i: torch.Tensor, j: torch.Tensor, K: int, N: int):
+    """The first K of flat candidates (v, i, j) in the order (score descending, i ascending, j ascending)."""
+    by_pair = torch.argsort(i * N + j)
+    sv, o = torch.sort(v[by_pair], descending=True, stable=True)
+    o = by_pair[o[:K]]
+    return v[o], i[o], j[o]
+
+
+def merge_row_candidates(vals: torch.Tensor, idx: torch.Tensor, K: int, rescore, info: Optional[dict] = None):
+    """Step 2 and 3 of ``top_pairs`` on any device: from the per-row lists ``vals`` / ``idx`` [L, N, k_row] of the strict lower
+    triangle (row i: its k_row best S[l, i, j], j < i, ordered by (score descending, j ascending), padded with -inf / -1) to the
+    K best pairs of every outcome, exactly -> ``(vals [L, K] fp32, head [L, K] int64, tail [L, K] int64)`` ordered by (score
+    descending, head ascending, tail ascending), padded with -inf / -1.
+
+    The K best of the N * k_row candidates are taken first.  A pair the lists dropped sits behind its row's last entry in that
+    order, so it can only belong to the answer if that entry lies strictly inside the K best (before their last place).  Rows
+    that are truncated (i > k_row) and whose last entry does are "open" -- at most K / k_row per outcome; ``rescore(l, rows)``
+    returns their dense scores [len(rows), N] (rows: ascending int64 indices), the lower-triangle part of which replaces their
+    candidates, and the K best are taken again.  One round suffices: the K-th score only rises, so every other row stays
+    closed and only its entries among the first K best can remain.  ``info["open_rows"]`` receives the open rows per outcome."""
+    L, N, kr = vals.shape
+    dev = vals.device
+    out_v = torch.full((L, K), float("-inf"), dtype=torch.float32, device=dev)
+    out_h = torch.full((L, K), -1, dtype=torch.int64, device=dev)
+    out_t = torch.full((L, K), -1, dtype=torch.int64, device=dev)
+    if info is not None:
+        info["open_rows"] = [0] * L
+    if L == 0 or K == 0 or N * kr == 0:
+        return out_v, out_h, out_t
+    take = min(K, N * kr)
+    # row-major candidates are already in (i ascending, then the row's own order): a stable sort by score is the pair order
+    sv, sp = torch.sort(vals.reshape(L, N * kr), dim=1, descending=True, stable=True)
+    sv, sp = sv[:, :take], sp[:, :take]
+    tail = torch.gather(idx.reshape(L, N * kr), 1, sp).long()
+    head = torch.where(tail >= 0, sp // kr, torch.full_like(sp, -1))
+    out_v[:, :take], out_h[:, :take], out_t[:, :take] = sv, head, tail
+    inside = torch.arange(take, device=dev)[None, :] < K - 1
+    opened = (tail >= 0) & (sp % kr == kr - 1) & (head > kr) & inside
+    hits = opened.nonzero()
+    if hits.numel() == 0:
+        return out_v, out_h, out_t
+    cols = torch.arange(N, device=dev)
+    for l in torch.unique(hits[:, 0]).tolist():
+        rows = torch.sort(head[l][opened[l]]).values
+        if info is not None:
+            info["open_rows"][l] = int(rows.numel())
+        dense = rescore(l, rows).to(torch.float32)
+        dense = torch.where(cols[None, :] < rows[:, None], dense, torch.full_like(dense, float("-inf")))
+        closed = (tail[l] >= 0) & ~torch.isin(head[l], rows)
+        v = torch.cat([sv[l][closed], dense.reshape(-1)])
+        i = torch.cat([head[l][closed], rows[:, None].expand(-1, N).reshape(-1)])
+        j = torch.cat([tail[l][closed], cols[None, :].expand(rows.numel(), -1).reshape(-1)])
+        live = v > float("-inf")
+        bv, bi, bj = _best_pairs(v[live], i[live], j[live], K, N)
+        n = int(bv.numel())
+        out_v[l].fill_(float("-inf"))
+        out_h[l].fill_(-1)
+        out_t[l].fill_(-1)
+        out_v[l, :n], out_h[l, :n], out_t[l, :n] = bv, bi, bj
+    return out_v, out_h, out_t
+
+
+@torch.no_grad()
+def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, int]] = None, k_row: Optional[int] = None,
+              max_temp_bytes: int = 1 << 30, info: Optional[dict] = None):
+    """The ``K`` highest-scoring unordered drug pairs of every outcome -> ``(vals [L', K] fp32, head [L', K], tail [L', K]
+    int64)``: the pair {i, j} is scored as S[l, i, j] with i > j (the strict lower triangle the rank normalisation reads,
+    notebooks/normalize_scores.py:39-46; the value is the general sweep's (z_i W) z_j), ordered by (score descending, i ascending,
+    j ascending), padded with -inf / -1 when K > N (N - 1) / 2.  Exact for every K, and no [L', N, N] tensor is made:
+      1. ``decoder.topk`` in lower-triangle mode keeps the ``k_row`` best of every row inside the sweep (default min(K, 16), at most
+         ``ops.bilinear_topk_max_k()``);
+      2. the K best of the N * k_row candidates of an outcome (a sort on the device);
+      3. the rows whose list was cut short AND whose last entry lies inside those K best are re-scored densely with the general
+         sweep and merged (``merge_row_candidates``): at most K / k_row rows per outcome, none when k_row >= K.
+    In "f32" / "bf16x3" the re-scored rows are bit-identical to what the sweep of step 1 saw.  In the 16-bit modes ("bf16" /
+    "f16") the two sweeps group their fp32 sums differently (<= 2e-6 of the score scale): re-scored rows carry the dense sweep's
+    values, so pairs closer than that may swap places against a brute-force ranking of either sweep.
+    Temporaries: outcome chunks sized so that the candidate lists and their sort stay under ``max_temp_bytes`` (48 bytes per
+    candidate), plus, per open outcome, the dense rows ([<= K / k_row, N] fp32).  Multi-GPU: pass the rank's outcome shard as
+    ``label_range``.  ``info["open_rows"]``: open rows per outcome."""
+    lo, hi = _outcomes(model, label_range)
+    N = z.shape[0]
+    max_k = ops.bilinear_topk_max_k()
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"K: expected a positive int, got {K!r}")
+    k_row = min(K, 16) if k_row is None else k_row
+    if isinstance(k_row, bool) or not isinstance(k_row, int) or not 1 <= k_row <= max_k:
+        raise ValueError(f"k_row: expected an int in 1..{max_k}, got {k_row!r}")
+    dec = model.decoder
+    out_v = torch.empty((hi - lo, K), dtype=torch.float32, device=z.device)
+    out_h = torch.empty((hi - lo, K), dtype=torch.int64, device=z.device)
+    out_t = torch.empty((hi - lo, K), dtype=torch.int64, device=z.device)
+    opened = []
+    chunk = max(1, int(max_temp_bytes) // max(N * k_row * 48, 1))
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        vals, idx = dec.topk(z, z, k_row, (s, e), eligible="lower")
+        part = {}
+        v, h, t = merge_row_candidates(vals, idx, K, lambda l, rows: dec(z[rows].contiguous(), z, (s + l, s + l + 1))[0], part)
+        out_v[s - lo:e - lo], out_h[s - lo:e - lo], out_t[s - lo:e - lo] = v, h, t
+        opened += part["open_rows"]
+        del vals, idx, v, h, t
+    if info is not None:
+        info["open_rows"] = opened
+    return out_v, out_h, out_t
+
+
 def _ensemble_weight(m) -> torch.Tensor:
     """W_sym [L,128,128] of one checkpoint: a NovelDDIMultilabel, its BilinearDDIScorer, or an original [L,D,D] weight."""
     if isinstance(m, torch.Tensor):
