@@ -205,6 +205,20 @@ int mdg_row_rstd(const float* x, int64_t ldx, float* rstd, int64_t rows, int64_t
 int mdg_linear_rowscaled(const float* x, int64_t ldx, const float* w, int64_t ldw, const void* w_packed, float* y, int64_t ldy,
                          int64_t M, int64_t N, int64_t K, const float* row_scale, const float* bias_pre, const float* bias,
                          int precision, void* workspace, size_t workspace_bytes, void* stream);
+/* A chain of 128-wide dense blocks as ONE launch (ABI 11): the dense part of a GIN layer in inference -- torchdrug's
+ * GraphIsomorphismConv as used at madrigal/models/models.py:217,720: edge_linear on the summed bond features added to the
+ * aggregated rows, the conv's MLP, eval BatchNorm and the activation --
+ *   u0 = e . We^T + x                          (only when e != NULL: e [M, k_e], We [k_in, k_e]; x [M, k_in] is then its residual)
+ *   u1 = act(u0 . W1^T + b1)   u2 = act(u1 . W2^T + b2)   ...   y = act((u . Wn^T + bn) * scale + shift)      n = n_stages in 1..3
+ * W1 [128, k_in], W2 / W3 [128, 128]; k_in, k_e multiples of 4 in (0, 128]; N must be 128; y [M, 128] with ldy % 4 == 0.
+ * The intermediate rows stay on the CU; every stage is bit-identical to the mdg_linear call it replaces.  All weights are given
+ * as their operand images (mdg_pack_operand with the same precision: We as [k_in, k_e], the others as [128, K]); biases,
+ * scale and shift nullable ([128] each, scale and shift together).  16-bit modes only (MDG_PREC_BF16X3 / MDG_PREC_BF16); all
+ * pointers 16-byte aligned; no workspace. */
+int mdg_linear_chain128(const float* x, int64_t ldx, int64_t k_in, const float* e, int64_t lde, int64_t k_e, const void* we_packed,
+                        int n_stages, const void* w1_packed, const void* w2_packed, const void* w3_packed, const float* b1,
+                        const float* b2, const float* b3, const float* scale, const float* shift, int act, float* y,
+                        int64_t ldy, int64_t M, int64_t N, int precision, void* stream);
 
 /* ------------------------------------------------------------------- cross-modal fusion ---- */
 

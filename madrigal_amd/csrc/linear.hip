@@ -446,7 +446,8 @@ __device__ __forceinline__ float finish(const LinearArgs& p, float v, float bias
   return val;
 }
 
-// 64 x 64 slab -> y[m0.., n0..]
+// ROWS x 64 slab -> y[m0.., n0..]
+template <int ROWS = 64>
 __device__ __forceinline__ void slab_to_global(const LinearArgs& p, const float* slab, int64_t m0, int64_t n0, int lane) {
   const int c4 = lane & 15;
   const int64_t n = n0 + 4 * c4;
@@ -461,7 +462,7 @@ __device__ __forceinline__ void slab_to_global(const LinearArgs& p, const float*
       if (p.bias_pre) bpre[e] = p.bias_pre[n + e];
     }
 #pragma unroll 4
-  for (int it = 0; it < 16; ++it) {
+  for (int it = 0; it < ROWS / 4; ++it) {
     const int row = it * 4 + (lane >> 4);
     const int64_t m = m0 + row;
     const f32x4 a = *reinterpret_cast<const f32x4*>(slab + slab_off(row, 4 * c4));
@@ -600,6 +601,189 @@ __global__ __launch_bounds__(S::THREADS, 2) void linear_kernel(const LinearArgs 
       slab_to_global(p, slab, pm0 + pass * 64, pn0, lane);
     }
   }
+}
+
+// ---- chained dense blocks over a resident row panel (16-bit modes) ----------------------------------------------------------
+// A GIN layer's dense chain in inference (torchdrug's GraphIsomorphismConv as used at madrigal/models/models.py:217,720):
+//   u0 = e . We^T + x  (optional)     u_s = act(u_{s-1} . W_s^T + b_s)     y = act((u . W_last^T + b_last) * scale + shift)
+// with every stage 128 wide, so a workgroup's output tile is whole rows and the next stage's A operand is exactly what the
+// epilogue holds.  One workgroup owns a panel of S::BM rows from the first operand to y; the intermediate rows never leave
+// the CU.  Per stage and output element the arithmetic is that of linear_kernel<MODE, Small, 16, false, true> launched on
+// the same tensors: the fp32 value split by mdg_split_bf16, the 16x16x32 MFMA in mma_stage16's product order, the k tiles
+// in ascending order, finish() -- the results are bit-identical to the chain of launches.
+//
+// LDS: [panel | weight stage 0 | weight stage 1].  The panel is the A operand of the running stage, all its k tiles: tile kt
+// at kt * S::A_BYTES as [hi | lo] bf16 planes in the off_bf16_m16 layout mma_stage16 reads.  The weights come k tile by
+// k tile from their cached images by LDS-DMA (L2 hits: 64 KB per stage, shared by every panel), double buffered, the next
+// tile issued under the MFMAs of the running one.  After a stage's k loop the panel is dead: each wave turns its patch
+// through its slice of it as an fp32 slab (slab_off), reads it back row-major with the stage's finish() applied (the
+// residual rows are read 16 B per lane here), and -- after a barrier, since a wave's A rows overwrite other waves' slabs --
+// writes the split values back as the next panel.  The next stage's first weight tile is in flight during all of that.
+// The last stage leaves through slab_to_global.
+struct ChainArgs {
+  const float* x; int64_t ldx; int kx;         // first operand rows (fp32; kx valid columns, zero-filled to the k tiles)
+  const float* e; int64_t lde; int ke;         // edge stage (null: none): its operand rows; x [M, kx] is then its residual
+  Operand We;                                  // edge weight image: kx rows
+  Operand W[3];                                // stage weight images: 128 rows each
+  const float* bias[3];
+  int n_stages;
+  const float* scale; const float* shift;      // last stage
+  int act;
+  float* y; int64_t ldy; int64_t M;
+  int vec_y;
+};
+
+template <int MODE, class S>
+__global__ __launch_bounds__(S::THREADS, (S::BM == 64 ? 2 : 1)) void linear_chain_kernel(const ChainArgs ca) {
+  static_assert(MODE != MDG_PREC_F32 && S::BN == 128 && S::WAVES == 4 && S::WN == 2, "16-bit modes, full-width tile, 2 x 2 waves");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int ROWS = 32 * S::MT;             // rows of a wave's patch
+  constexpr int PANEL = S::BM * 128 * 4;       // == 4 waves x ROWS x 64 fp32 of slab
+  constexpr int ITS = ROWS / 4;
+  char* const panel = smem;
+  char* const wbuf = smem + PANEL;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1, c = lane & 15, g = lane >> 4;
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * S::BM;
+  float* const slab = reinterpret_cast<float*>(panel) + wave * (ROWS * 64);
+  const int c4 = lane & 15, n = wc * 64 + 4 * c4;             // this lane's four columns in the row-major epilogue
+
+  // every lambda below is always_inline: one left as a call keeps the accumulators it captures in memory behind the call
+  const auto write_panel = [&](int row, int col, const f32x4& v) __attribute__((always_inline)) {
+    bf16x4 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      __bf16 a_, b_;
+      mdg_split_bf16(v[i], a_, b_);
+      hi[i] = a_;
+      lo[i] = b_;
+    }
+    const int off = (col >> 5) * S::A_BYTES + off_bf16_m16(row, (col & 31) >> 3) + (col & 7) * 2;
+    *reinterpret_cast<bf16x4*>(panel + off) = hi;
+    if constexpr (MODE == MDG_PREC_BF16X3) *reinterpret_cast<bf16x4*>(panel + S::A_LO + off) = lo;
+  };
+  // fp32 rows -> panel: what the raw-x loader of linear_kernel stages (zeros past column k, rows past the end clamped)
+  const auto load_panel = [&](const float* src, int64_t ld, int k) __attribute__((always_inline)) {
+    const int sh = ((k + 63) & ~63) == 128 ? 5 : 4;           // float4 groups per row: 32 or 16
+    constexpr int G = S::BM * 32 / S::THREADS;
+    f32x4 v[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const int idx = i * S::THREADS + tid, row = idx >> sh, col = (idx & ((1 << sh) - 1)) * 4;
+      int64_t gr = row0 + row;
+      gr = gr < ca.M ? gr : ca.M - 1;
+      v[i] = (row < S::BM && col < k) ? *reinterpret_cast<const f32x4*>(src + gr * ld + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const int idx = i * S::THREADS + tid, row = idx >> sh, col = (idx & ((1 << sh) - 1)) * 4;
+      if (row < S::BM) write_panel(row, col, v[i]);
+    }
+  };
+  const auto dma_b = [&](const Operand& W, int kt, char* buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      dma_piece<S::BN, S::WAVES, 16>(W.p0, W.ld_bytes, W.kb, 0, W.nrows, static_cast<int64_t>(kt) * BK, buf, wave, lane, i);
+      if constexpr (MODE == MDG_PREC_BF16X3)
+        dma_piece<S::BN, S::WAVES, 16>(W.p1, W.ld_bytes, W.kb, 0, W.nrows, static_cast<int64_t>(kt) * BK, buf + S::B_LO, wave, lane, i);
+    }
+  };
+
+  f32x4 acc[2 * S::MT][4];
+  // one stage's k loop; its first weight tile is already on its way into weight stage 0
+  const auto run = [&](const Operand& W, int nk) __attribute__((always_inline)) {
+#pragma unroll
+    for (int a = 0; a < 2 * S::MT; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < nk; ++kt) {
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // this wave's weight DMA and its panel writes
+      __builtin_amdgcn_s_barrier();
+      const bool more = kt + 1 < nk;
+      mma_stage16<MODE, S>(panel + kt * S::A_BYTES, wbuf + (kt & 1) * S::B_BYTES, wr, wc, c, g, acc,
+                           [&](int slot) __attribute__((always_inline)) { if (slot == 0 && more) dma_b(W, kt + 1, wbuf + ((kt + 1) & 1) * S::B_BYTES); });
+    }
+    __syncthreads();                                      // every wave is done with the panel and the weight stages
+  };
+  const auto acc_to_slab = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int mt = 0; mt < 2 * S::MT; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) slab[slab_off(mt * 16 + 4 * g + v, nt * 16 + c)] = acc[mt][nt][v];
+  };
+  // an inner stage's epilogue: finish(), the residual rows (edge stage: columns past res_n are the next operand's zero fill)
+  const auto to_panel = [&](const float* bias, int act, const float* res, int64_t ldr, int res_n) __attribute__((always_inline)) {
+    acc_to_slab();
+    float b[4] = {0.f, 0.f, 0.f, 0.f};
+    if (bias) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) b[i] = bias[n + i];
+    }
+    f32x4 o[ITS];
+    // the activation as a constant where it is one of the path's own (ReLU / none): finish() folds to a few instructions
+    const auto finish_rows = [&](int act_) __attribute__((always_inline)) {
+      LinearArgs q{};
+      q.act = act_;
+      q.alpha = 1.0f;
+#pragma unroll
+      for (int it = 0; it < ITS; ++it) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(slab + slab_off(it * 4 + (lane >> 4), 4 * c4));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[it][i] = finish(q, a[i], b[i], 1.f, 0.f, 0.f, 1.f);
+      }
+    };
+    if (act == MDG_ACT_RELU) finish_rows(MDG_ACT_RELU);
+    else if (act == MDG_ACT_NONE) finish_rows(MDG_ACT_NONE);
+    else finish_rows(act);
+#pragma unroll
+    for (int it = 0; it < ITS; ++it) {
+      const int row = it * 4 + (lane >> 4);
+      if (res) {
+        if (n < res_n) {
+          int64_t m = row0 + wr * ROWS + row;
+          m = m < ca.M ? m : ca.M - 1;
+          const f32x4 rv = *reinterpret_cast<const f32x4*>(res + m * ldr + n);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) o[it][i] += rv[i];
+        } else o[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    __syncthreads();                                      // every wave has read its slab: the panel may be overwritten
+#pragma unroll
+    for (int it = 0; it < ITS; ++it) write_panel(wr * ROWS + it * 4 + (lane >> 4), n, o[it]);
+  };
+
+  if (ca.e) {
+    load_panel(ca.e, ca.lde, ca.ke);
+    dma_b(ca.We, 0, wbuf);
+    run(ca.We, ((ca.ke + 63) & ~63) / BK);
+    dma_b(ca.W[0], 0, wbuf);
+    to_panel(nullptr, MDG_ACT_NONE, ca.x, ca.ldx, ca.kx);
+  } else {
+    load_panel(ca.x, ca.ldx, ca.kx);
+    dma_b(ca.W[0], 0, wbuf);
+  }
+  const auto stage = [&](auto sc) __attribute__((always_inline)) {
+    constexpr int s = decltype(sc)::value;
+    run(ca.W[s], s == 0 ? ((ca.kx + 63) & ~63) / BK : 128 / BK);
+    if (s + 1 < ca.n_stages) {                            // workgroup-uniform
+      if constexpr (s < 2) dma_b(ca.W[s + 1], 0, wbuf);
+      to_panel(ca.bias[s], ca.act, nullptr, 0, 0);
+    } else {
+      LinearArgs q{};
+      q.y = ca.y; q.ldy = ca.ldy; q.bias = ca.bias[s]; q.scale = ca.scale; q.shift = ca.shift;
+      q.alpha = 1.0f; q.beta = 1.0f; q.act = ca.act; q.M = ca.M; q.N = 128; q.vec_y = ca.vec_y;
+      acc_to_slab();
+      if (ca.act == MDG_ACT_RELU) { q.act = MDG_ACT_RELU; slab_to_global<ROWS>(q, slab, row0 + wr * ROWS, wc * 64, lane); }
+      else if (ca.act == MDG_ACT_NONE) { q.act = MDG_ACT_NONE; slab_to_global<ROWS>(q, slab, row0 + wr * ROWS, wc * 64, lane); }
+      else slab_to_global<ROWS>(q, slab, row0 + wr * ROWS, wc * 64, lane);
+    }
+  };
+  stage(std::integral_constant<int, 0>{});
+  if (ca.n_stages > 1) stage(std::integral_constant<int, 1>{});
+  if (ca.n_stages > 2) stage(std::integral_constant<int, 2>{});
 }
 
 // ---- 256 x 256 "ping-pong" dense block (16-bit modes) -----------------------------------------------------------------------
@@ -1524,6 +1708,67 @@ extern "C" int mdg_linear_rowscaled(const float* x, int64_t ldx, const float* w,
 }
 
 // ---- grouped launch: see the GROUPED kernel variant -------------------------------------------------------------------------
+// ---- chained dense blocks (see linear_chain_kernel) ---------------------------------------------------------------------------
+using ChainTall = Shape<2, 2, 2, 2>;           // 128-row panel, 96 KB LDS: one workgroup per CU
+using ChainShort = Shape<1, 2, 2, 2>;          // 64-row panel, 64 KB LDS: two workgroups per CU (the default: measured)
+
+extern "C" int mdg_linear_chain128(const float* x, int64_t ldx, int64_t k_in, const float* e, int64_t lde, int64_t k_e, const void* we_packed,
+                                   int n_stages, const void* w1_packed, const void* w2_packed, const void* w3_packed, const float* b1,
+                                   const float* b2, const float* b3, const float* scale, const float* shift, int act, float* y,
+                                   int64_t ldy, int64_t M, int64_t N, int precision, void* stream) {
+  MDG_CHECK_ARG(precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16, "mdg_linear_chain128: a 16-bit operand mode (got precision %d)", precision);
+  MDG_CHECK_ARG(N == 128, "mdg_linear_chain128: every stage is 128 wide (got %lld)", (long long)N);
+  MDG_CHECK_ARG(M >= 0 && mdg_cdiv(M, ChainShort::BM) < (1ll << 31), "mdg_linear_chain128: bad row count");
+  MDG_CHECK_ARG(n_stages >= 1 && n_stages <= 3, "mdg_linear_chain128: 1 to 3 stages (got %d)", n_stages);
+  MDG_CHECK_ARG(k_in > 0 && k_in <= 128 && k_in % 4 == 0 && ldx % 4 == 0 && ldx >= k_in,
+                "mdg_linear_chain128: first-stage K must be a multiple of 4 in (0, 128] with ldx >= K a multiple of 4 (K=%lld ldx=%lld)",
+                (long long)k_in, (long long)ldx);
+  MDG_CHECK_ARG(act >= MDG_ACT_NONE && act <= MDG_ACT_SELU, "mdg_linear_chain128: unknown activation %d", act);
+  MDG_CHECK_ARG((scale == nullptr) == (shift == nullptr), "mdg_linear_chain128: scale and shift come together");
+  if (M == 0) return MDG_OK;
+  const void* const w[3] = {w1_packed, w2_packed, w3_packed};
+  const float* const b[3] = {b1, b2, b3};
+  MDG_CHECK_ARG(x && y && mdg_aligned16(x) && mdg_aligned16(y), "mdg_linear_chain128: x and y must be non-null and 16-byte aligned");
+  MDG_CHECK_ARG(ldy >= 128 && ldy % 4 == 0, "mdg_linear_chain128: ldy must be a multiple of 4 and >= 128 (got %lld)", (long long)ldy);
+  for (int s = 0; s < n_stages; ++s)
+    MDG_CHECK_ARG(w[s] && mdg_aligned16(w[s]), "mdg_linear_chain128: weight image of stage %d null or misaligned", s + 1);
+  if (e) {
+    MDG_CHECK_ARG(k_e > 0 && k_e <= 128 && k_e % 4 == 0 && lde % 4 == 0 && lde >= k_e && mdg_aligned16(e),
+                  "mdg_linear_chain128: edge-stage K must be a multiple of 4 in (0, 128], lde >= K a multiple of 4, e 16-byte aligned (K=%lld lde=%lld)",
+                  (long long)k_e, (long long)lde);
+    MDG_CHECK_ARG(we_packed && mdg_aligned16(we_packed), "mdg_linear_chain128: edge weight image null or misaligned");
+  }
+  ChainArgs a{};
+  a.x = x; a.ldx = ldx; a.kx = static_cast<int>(k_in);
+  if (e) {
+    a.e = e; a.lde = lde; a.ke = static_cast<int>(k_e);
+    set_image(a.We, static_cast<const char*>(we_packed), k_in, pad_k(k_e, precision), precision);
+  }
+  for (int s = 0; s < n_stages; ++s) {
+    set_image(a.W[s], static_cast<const char*>(w[s]), 128, pad_k(s == 0 ? k_in : 128, precision), precision);
+    a.bias[s] = b[s];
+  }
+  a.n_stages = n_stages; a.scale = scale; a.shift = shift; a.act = act;
+  a.y = y; a.ldy = ldy; a.M = M; a.vec_y = 1;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static MdgEnvInt rows_sw{"MDG_CHAIN_ROWS", 64};          // panel height: 64 (two workgroups per CU) or 128
+  if (rows_sw.get() == 128) {
+    using S = ChainTall;
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(M, S::BM)));
+    const size_t lds = S::BM * 512 + 2 * S::B_BYTES;
+    if (precision == MDG_PREC_BF16X3) hipLaunchKernelGGL((linear_chain_kernel<MDG_PREC_BF16X3, S>), grid, dim3(S::THREADS), lds, st, a);
+    else hipLaunchKernelGGL((linear_chain_kernel<MDG_PREC_BF16, S>), grid, dim3(S::THREADS), lds, st, a);
+  } else {
+    using S = ChainShort;
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(M, S::BM)));
+    const size_t lds = S::BM * 512 + 2 * S::B_BYTES;
+    if (precision == MDG_PREC_BF16X3) hipLaunchKernelGGL((linear_chain_kernel<MDG_PREC_BF16X3, S>), grid, dim3(S::THREADS), lds, st, a);
+    else hipLaunchKernelGGL((linear_chain_kernel<MDG_PREC_BF16, S>), grid, dim3(S::THREADS), lds, st, a);
+  }
+  MDG_CHECK_LAUNCH("mdg_linear_chain128");
+  return MDG_OK;
+}
+
 extern "C" int mdg_linear_group_tile_words(void) { return kGroupTileWords; }
 
 extern "C" size_t mdg_linear_grouped_workspace_bytes(int64_t rows_total, int64_t K, int precision) { return image_bytes(rows_total, K, precision); }

@@ -373,6 +373,24 @@ class GraphIsomorphismNetwork(nn.Module):
         g = ag.csr_aggregate(h, plan["graph_rowptr"], None, None, plan["t_readout"], mean=(self.readout_kind == "mean"))
         return {"graph_feature": g[:, : self.output_dim], "node_feature": h}
 
+    # Inference: a layer's dense chain (edge_linear + residual, the MLP, BatchNorm(eval), activation) as ONE launch of
+    # mdg_linear_chain128 -- the 128-wide rows stay on the CU between the blocks; bit-identical to the launches it replaces.
+    # Taken where the kernel applies (see _chain_ok); False keeps one dense block per launch.
+    fuse_layer_chain = True
+
+    def _chain_ok(self, layer) -> bool:
+        lins = layer.mlp.layers
+        return (self.fuse_layer_chain and _state["precision"] in ("bf16x3", "bf16") and 1 <= len(lins) <= 3
+                and all(lin.weight.shape[0] == 128 for lin in lins) and lins[0].weight.shape[1] <= 128)
+
+    def _layer_chain(self, layer, agg, esum, we):
+        scale = shift = None
+        if hasattr(layer, "batch_norm"):
+            scale, shift = _bn_scale_shift(layer.batch_norm)
+        lins = layer.mlp.layers
+        return ops.linear_chain(agg, [lin.weight for lin in lins], [lin.bias for lin in lins], edge=esum, edge_weight=we,
+                                scale=scale, shift=shift, act=self.activation, precision=_state["precision"])
+
     def forward(self, graph, input, all_loss=None, metric=None):
         if _train_path(self) or ag.needs_grad(input):
             return self._forward_train(graph, input)
@@ -381,6 +399,7 @@ class GraphIsomorphismNetwork(nn.Module):
         esum = None
         for layer in self.layers:
             k_in = layer.mlp.layers[0].weight.shape[1]
+            chain = self._chain_ok(layer)
             agg = ops.csr_aggregate(h, plan["rowptr"], plan["col"], edge_weight=plan["w"], x_self=h,
                                     self_coef_dev=layer.eps.detach(), self_coef_add=1.0)        # [A, pad4(k_in)]
             if layer.edge_linear is not None:
@@ -394,7 +413,13 @@ class GraphIsomorphismNetwork(nn.Module):
                     we[:k_in, fe] = layer.edge_linear.bias.detach()
                     return we
                 we = _cached(layer.edge_linear, ("aug", agg.shape[1], esum.shape[1]), (layer.edge_linear.weight, layer.edge_linear.bias), build)
+                if chain and esum.shape[1] <= 128:       # edge_linear, the MLP, BatchNorm(eval) and the activation in one launch
+                    h = self._layer_chain(layer, agg, esum, we)
+                    continue
                 agg = _lin(esum, we, None, residual=agg)                 # + W_e sum_e(e_uv) + b_e
+            elif chain:
+                h = self._layer_chain(layer, agg, None, None)
+                continue
             u = agg
             n_mlp = len(layer.mlp.layers)
             for j, lin in enumerate(layer.mlp.layers):

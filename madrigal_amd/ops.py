@@ -430,6 +430,54 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     return out.view(*lead, N) if len(lead) != 1 or lead[0] != M else out
 
 
+def linear_chain(x: torch.Tensor, weights, biases, *, edge: Optional[torch.Tensor] = None, edge_weight: Optional[torch.Tensor] = None,
+                 scale=None, shift=None, act=None, precision="bf16x3", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch for a chain of 128-wide dense blocks (mdg_linear_chain128), bit-identical to the ``linear`` calls it stands for:
+
+        u = linear(edge, edge_weight, residual=x)          (only with ``edge``; edge_weight [K, K_e], x [M, K])
+        for W, b in zip(weights, biases): u = linear(u, W, b, act=act)     (scale / shift join the LAST one)
+
+    ``weights``: 1 to 3 fp32 matrices, the first [128, K] with K <= 128 (a multiple of 4), the others [128, 128]; ``biases``: one
+    entry per weight, each [128] or None.  bf16x3 / bf16 only; the weights' operand images are cached like ``linear``'s."""
+    forward_only(x, edge, edge_weight, scale, shift, *weights, *[b for b in biases if b is not None])
+    prec = _prec(precision)
+    x = _f32_cuda(x, "x", 2) if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1) else x
+    M, K = x.shape
+    n = len(weights)
+    if len(biases) != n:
+        raise ValueError("linear_chain: one bias entry (or None) per weight")
+    ws = [padded_weight(_f32_cuda(w, "weight", 2)) for w in weights]
+    N = ws[-1].shape[0] if n else 0
+    for j, w in enumerate(ws):
+        if tuple(w.shape) != (N, K if j == 0 else N):
+            raise ValueError(f"linear_chain: weight {j} is {tuple(w.shape)}, expected {(N, K if j == 0 else N)}")
+    for nm, t in [("bias", b) for b in biases] + [("scale", scale), ("shift", shift)]:
+        if t is not None and (t.numel() != N or not t.is_cuda or t.dtype != torch.float32):
+            raise ValueError(f"{nm}: expected fp32 cuda [{N}]")
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    e_ptr, lde, k_e, we_img = None, 0, 0, None
+    if edge is not None:
+        edge = _f32_cuda(edge, "edge", 2) if not (edge.is_cuda and edge.dtype == torch.float32 and edge.dim() == 2 and edge.stride(1) == 1) else edge
+        we = padded_weight(_f32_cuda(edge_weight, "edge_weight", 2))
+        if edge.shape[0] != M or tuple(we.shape) != (K, edge.shape[1]):
+            raise ValueError(f"linear_chain: edge {tuple(edge.shape)} / edge_weight {tuple(we.shape)} do not fit x {tuple(x.shape)}")
+        e_ptr, lde, k_e = edge, edge.stride(0), edge.shape[1]
+        we_img = packed_weight_image(we, prec) if prec != PREC_F32 else None
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    elif out.dim() != 2 or out.shape != (M, N) or out.stride(1) != 1 or out.dtype != torch.float32 or not out.is_cuda:
+        raise ValueError(f"out: expected fp32 cuda [{M},{N}] with unit inner stride")
+    imgs = [packed_weight_image(w, prec) if prec != PREC_F32 else None for w in ws] + [None] * (3 - n)
+    bs = [None if b is None else b.detach().contiguous() for b in biases] + [None] * (3 - n)
+    check(lib().mdg_linear_chain128(_ptr(x), _c64(x.stride(0)), _c64(K), _ptr(e_ptr), _c64(lde), _c64(k_e), _ptr(we_img), _c(n),
+                                    _ptr(imgs[0]), _ptr(imgs[1]), _ptr(imgs[2]), _ptr(bs[0]), _ptr(bs[1]), _ptr(bs[2]),
+                                    _ptr(None if scale is None else scale.contiguous()), _ptr(None if shift is None else shift.contiguous()),
+                                    _c(ACTS[act]), _ptr(out), _c64(out.stride(0)), _c64(M), _c64(N), _c(prec), _stream(x)),
+          "mdg_linear_chain128")
+    return out
+
+
 def layernorm_packed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, precision, want_fp32: bool = True):
     """LayerNorm of a 2-D ``x`` -> (y, image): ``image`` is y as the packed operand of the dense block that consumes it
     (linear_packed), written by the same kernel; None where the arithmetic mode or the width takes no image (then the
