@@ -566,6 +566,26 @@ int mdg_symmetrize_bwd(const float* dw_sym, float* dw_original, int64_t n_labels
 int mdg_adamw_chunk_elems(void);
 int mdg_adamw_multi(const int64_t* chunk_ptrs, const int32_t* chunk_lens, const int32_t* chunk_tensor, const float* hyper,
                     int64_t n_chunks, void* stream);
+/* torch.optim.RAdam semantics (madrigal/utils.py:602 OPTIMIZER_CLASSES, `--optimizer radam`) over the same tables, one launch.
+ * hyper [n_tensors,8] = {lr, beta1, beta2, eps, weight_decay, 1/(1-beta1^t), rect_t * sqrt(1-beta2^t), decoupled}: the host works
+ * out rho_t = rho_inf - 2 t beta2^t / (1-beta2^t) per tensor and passes 0 in slot 6 while rho_t <= 5, where the update is the
+ * unrectified p -= lr * m_hat.  Weight decay is L2 (g += wd * p, torch's default and so the reference's) unless `decoupled` != 0. */
+int mdg_radam_multi(const int64_t* chunk_ptrs, const int32_t* chunk_lens, const int32_t* chunk_tensor, const float* hyper,
+                    int64_t n_chunks, void* stream);
+/* The reference's LARS (madrigal/utils.py:628-662; selected by pretrain.py:175-176, `--pretrain_optimizer lars`) for every parameter
+ * tensor in three launches, whatever the number of tensors.  chunk_ptrs [n_chunks,3] = (param, grad, mu) addresses of chunks of
+ * mdg_adamw_chunk_elems() elements, a tensor's chunks consecutive: first_chunk / tensor_chunks [n_tensors].  hyper [n_tensors,5] =
+ * {lr, weight_decay, momentum, trust_coefficient, scaled}, scaled = 1 for tensors with more than one dimension:
+ *     scaled:   u = g + weight_decay * p;  q = trust_coefficient * |p| / |u| if both norms are > 0 else 1;  u = q * u
+ *     unscaled: u = g
+ *     mu = momentum * mu + u;  p = p - lr * mu
+ * The norms are fixed-order sums (per-chunk fp32 partials, per-tensor sum in double; no atomics): results are reproducible bit for
+ * bit and do not depend on the 16-byte alignment of the tensors, which only selects the width of the accesses.  `workspace` is
+ * device memory, 16-byte aligned, of mdg_lars_multi_workspace_bytes; nothing is read back to the host. */
+size_t mdg_lars_multi_workspace_bytes(int64_t n_chunks, int64_t n_tensors);
+int mdg_lars_multi(const int64_t* chunk_ptrs, const int32_t* chunk_lens, const int32_t* chunk_tensor, const float* hyper,
+                   const int32_t* first_chunk, const int32_t* tensor_chunks, int64_t n_chunks, int64_t n_tensors, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------- backward-pass building blocks ---- */
 /* (the finetune step of train_ddi_batch.py:285-354: loss.backward() through the modules above) */

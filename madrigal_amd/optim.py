@@ -1,6 +1,7 @@
-"""AdamW on the HIP path + the reference's parameter grouping (madrigal/utils.py:446-613).
+"""The reference's optimizers on the HIP path + its parameter grouping (madrigal/utils.py:446-613, 628-662).
 
-``AdamW`` is a ``torch.optim.Optimizer`` subclass (param_groups, ``state_dict`` layout of ``torch.optim.AdamW``:
+``RAdam`` (torch.optim.RAdam's state and semantics) and ``LARS`` (the reference's own class: ``mu`` per parameter) update every
+parameter in one and three launches.  ``AdamW`` is a ``torch.optim.Optimizer`` subclass (param_groups, ``state_dict`` layout of ``torch.optim.AdamW``:
 ``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter, so LR schedulers and checkpoints interoperate); ``step()`` updates
 every parameter in ONE kernel launch (mdg_adamw_multi) instead of torch's per-tensor / foreach arithmetic.
 """
@@ -17,30 +18,15 @@ import torch.nn as nn
 from ._lib import check, lib
 
 
-class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
-        if amsgrad:
-            raise NotImplementedError("amsgrad is not used by the reference")
-        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
-            raise ValueError("invalid AdamW hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+class _ChunkedOptimizer(torch.optim.Optimizer):
+    """What the multi-tensor kernels share on the host: the tensors are cut into chunks of ``mdg_adamw_chunk_elems()`` elements; the
+    chunk layout is cached per set of tensor sizes, and the per-step tables (chunk addresses, per-tensor hyper-parameters) reach the
+    device through a ring of pinned staging buffers."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self._chunk = int(lib().mdg_adamw_chunk_elems())
         self._layouts = {}
-        self._count = {}                # parameter -> number of updates so far (mirrored into state[p]["step"] on demand)
-
-    def _sync_steps(self) -> None:
-        for p, k in self._count.items():
-            st = self.state.get(p)
-            if st:
-                st["step"].fill_(float(k))
-
-    def state_dict(self):
-        self._sync_steps()
-        return super().state_dict()
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._count = {}                # re-read from the loaded ``step`` tensors at the next update
 
     @staticmethod
     def _upload(lay: dict, name: str, host: np.ndarray, dev) -> torch.Tensor:
@@ -60,6 +46,80 @@ class AdamW(torch.optim.Optimizer):
         ent[1].record(torch.cuda.current_stream(dev))
         return out
 
+    def _refuse(self, p, g) -> None:
+        if g.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
+            raise RuntimeError(f"madrigal_amd.optim.{type(self).__name__}: dense fp32 parameters on the GPU only")
+        if not p.is_contiguous():
+            raise RuntimeError(f"madrigal_amd.optim.{type(self).__name__}: parameters must be contiguous")
+
+    def _layout(self, dev, sizes: tuple) -> dict:
+        # chunk layout (offsets / lengths / owning tensor) depends only on the tensor sizes: built once, vectorised
+        lay = self._layouts.get((dev, sizes))
+        if lay is None:
+            offs, lens, owner = [], [], []
+            for ti, n in enumerate(sizes):
+                o = np.arange(0, n, self._chunk, dtype=np.int64)
+                offs.append(o * 4)
+                lens.append(np.minimum(self._chunk, n - o).astype(np.int32))
+                owner.append(np.full(o.shape, ti, dtype=np.int32))
+            offs, lens, owner = (np.concatenate(a) if a else np.zeros(0, dtype=np.int64) for a in (offs, lens, owner))
+            lay = {"offs": offs, "owner": owner, "n": int(offs.shape[0]), "t_len": torch.from_numpy(lens).to(dev),
+                   "t_own": torch.from_numpy(owner).to(dev), "base": None, "t_ptr": None}
+            self._layouts[(dev, sizes)] = lay
+        return lay
+
+    def _tables(self, dev, items: list):
+        """``items``: (tensors, hyper) per parameter, ``tensors`` = the parameter, its gradient and its state tensors in the kernel's
+        order.  Returns the layout (with the chunk-address table of this step in ``t_ptr``) and the hyper-parameter table."""
+        lay = self._layout(dev, tuple(ts[0].numel() for ts, _ in items))
+        if lay["n"] == 0:
+            return lay, None
+        # per-step tables: the chunk pointers (gradients are re-allocated by every backward pass, so their addresses move)
+        # and the per-tensor hyper-parameters.  Both go through rotating PINNED host buffers and asynchronous copies: a
+        # pageable .to(device) waits for everything queued on the stream (the whole backward pass), which would stop the
+        # host from queueing the next step while this one still runs.
+        base = np.asarray([t.data_ptr() for ts, _ in items for t in ts], dtype=np.int64).reshape(len(items), -1)
+        if lay["base"] is None or not np.array_equal(base, lay["base"]):
+            lay["base"] = base
+            lay["t_ptr"] = self._upload(lay, "ptr", base[lay["owner"]] + lay["offs"][:, None], dev)
+        return lay, self._upload(lay, "hyp", np.asarray([h for _, h in items], dtype=np.float32), dev)
+
+    @staticmethod
+    def _launched(dev, lay: dict, t_hyp: torch.Tensor, written: list) -> None:
+        t_hyp.record_stream(torch.cuda.current_stream(dev))
+        lay["t_ptr"].record_stream(torch.cuda.current_stream(dev))
+        # the kernel wrote the parameters and the state behind torch's back: bump their in-place version counters so
+        # that everything keyed on them (packed / derived weight caches of the inference path, autograd's saved-tensor
+        # checks) sees the update
+        torch.autograd.graph.increment_version(written)
+
+
+class _AdamFamily(_ChunkedOptimizer):
+    """``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter (torch's layout), per-parameter step counts, one launch of ``_ENTRY`` per
+    step and device; a subclass supplies the eight per-tensor numbers of its kernel (``_hyper``)."""
+    _ENTRY = ""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        self._count = {}                # parameter -> number of updates so far (mirrored into state[p]["step"] on demand)
+
+    def _sync_steps(self) -> None:
+        for p, k in self._count.items():
+            st = self.state.get(p)
+            if st:
+                st["step"].fill_(float(k))
+
+    def state_dict(self):
+        self._sync_steps()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._count = {}                # re-read from the loaded ``step`` tensors at the next update
+
+    def _hyper(self, group: dict, k: int) -> tuple:
+        raise NotImplementedError
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -69,7 +129,6 @@ class AdamW(torch.optim.Optimizer):
         by_dev: Dict[torch.device, list] = {}
         count, hyper_of = self._count, {}
         for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
             for p in group["params"]:
                 g = p.grad
                 if g is None:
@@ -77,10 +136,7 @@ class AdamW(torch.optim.Optimizer):
                 st = self.state[p]
                 k = count.get(p)
                 if k is None:                                   # first update of this parameter (or the first after a load)
-                    if g.is_sparse or p.dtype != torch.float32 or not p.is_cuda:
-                        raise RuntimeError("madrigal_amd.optim.AdamW: dense fp32 parameters on the GPU only")
-                    if not p.is_contiguous():
-                        raise RuntimeError("madrigal_amd.optim.AdamW: parameters must be contiguous")
+                    self._refuse(p, g)
                     if not st:
                         st["step"] = torch.tensor(0.0)
                         st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
@@ -94,46 +150,117 @@ class AdamW(torch.optim.Optimizer):
                     g = g.contiguous()
                 hyper = hyper_of.get((gi, k))
                 if hyper is None:
-                    hyper = hyper_of[(gi, k)] = (group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 / (1.0 - b1 ** k),
-                                                 1.0 / math.sqrt(1.0 - b2 ** k), 0.0)
-                by_dev.setdefault(p.device, []).append((p, g, st["exp_avg"], st["exp_avg_sq"], hyper))
+                    hyper = hyper_of[(gi, k)] = self._hyper(group, k)
+                by_dev.setdefault(p.device, []).append(((p, g, st["exp_avg"], st["exp_avg_sq"]), hyper))
+        entry = getattr(lib(), self._ENTRY)
         for dev, items in by_dev.items():
-            # chunk layout (offsets / lengths / owning tensor) depends only on the tensor sizes: built once, vectorised
-            sizes = tuple(p.numel() for p, *_ in items)
-            lay = self._layouts.get((dev, sizes))
-            if lay is None:
-                offs, lens, owner = [], [], []
-                for ti, n in enumerate(sizes):
-                    o = np.arange(0, n, self._chunk, dtype=np.int64)
-                    offs.append(o * 4)
-                    lens.append(np.minimum(self._chunk, n - o).astype(np.int32))
-                    owner.append(np.full(o.shape, ti, dtype=np.int32))
-                offs, lens, owner = (np.concatenate(a) if a else np.zeros(0, dtype=np.int64) for a in (offs, lens, owner))
-                lay = {"offs": offs, "owner": owner, "n": int(offs.shape[0]), "t_len": torch.from_numpy(lens).to(dev),
-                       "t_own": torch.from_numpy(owner).to(dev), "base": None, "t_ptr": None}
-                self._layouts[(dev, sizes)] = lay
+            lay, t_hyp = self._tables(dev, items)
             if lay["n"] == 0:
                 continue
-            # per-step tables: the chunk pointers (gradients are re-allocated by every backward pass, so their addresses move)
-            # and the per-tensor hyper-parameters.  Both go through rotating PINNED host buffers and asynchronous copies: a
-            # pageable .to(device) waits for everything queued on the stream (the whole backward pass), which would stop the
-            # host from queueing the next step while this one still runs.
-            base = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()) for p, g, m, v, _ in items], dtype=np.int64)
-            if lay["base"] is None or not np.array_equal(base, lay["base"]):
-                lay["base"] = base
-                lay["t_ptr"] = self._upload(lay, "ptr", base[lay["owner"]] + lay["offs"][:, None], dev)
-            t_hyp = self._upload(lay, "hyp", np.asarray([h for *_, h in items], dtype=np.float32), dev)
             with torch.cuda.device(dev):
-                check(lib().mdg_adamw_multi(ctypes.c_void_p(lay["t_ptr"].data_ptr()), ctypes.c_void_p(lay["t_len"].data_ptr()),
-                                            ctypes.c_void_p(lay["t_own"].data_ptr()), ctypes.c_void_p(t_hyp.data_ptr()),
-                                            ctypes.c_int64(lay["n"]), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                      "mdg_adamw_multi")
-            t_hyp.record_stream(torch.cuda.current_stream(dev))
-            lay["t_ptr"].record_stream(torch.cuda.current_stream(dev))
-            # the kernel wrote the parameters and the moments behind torch's back: bump their in-place version counters so
-            # that everything keyed on them (packed / derived weight caches of the inference path, autograd's saved-tensor
-            # checks) sees the update
-            torch.autograd.graph.increment_version([t for p, _, m, v, _ in items for t in (p, m, v)])
+                check(entry(ctypes.c_void_p(lay["t_ptr"].data_ptr()), ctypes.c_void_p(lay["t_len"].data_ptr()),
+                            ctypes.c_void_p(lay["t_own"].data_ptr()), ctypes.c_void_p(t_hyp.data_ptr()),
+                            ctypes.c_int64(lay["n"]), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), self._ENTRY)
+            self._launched(dev, lay, t_hyp, [t for (p, _, m, v), _ in items for t in (p, m, v)])
+        return loss
+
+
+class AdamW(_AdamFamily):
+    _ENTRY = "mdg_adamw_multi"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
+        if amsgrad:
+            raise NotImplementedError("amsgrad is not used by the reference")
+        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
+            raise ValueError("invalid AdamW hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+
+    def _hyper(self, group: dict, k: int) -> tuple:
+        b1, b2 = group["betas"]
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 / (1.0 - b1 ** k), 1.0 / math.sqrt(1.0 - b2 ** k), 0.0)
+
+
+class RAdam(_AdamFamily):
+    """``torch.optim.RAdam`` (the reference's ``--optimizer radam``, madrigal/utils.py:602) in one launch per step: its state layout,
+    its L2 weight decay by default and the decoupled one on request.  The rectification term depends on the step count alone, so the
+    host works it out per tensor: while rho_t <= 5 the kernel takes the unrectified branch."""
+    _ENTRY = "mdg_radam_multi"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, decoupled_weight_decay=False):
+        if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
+            raise ValueError("invalid RAdam hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay))
+
+    def _hyper(self, group: dict, k: int) -> tuple:
+        b1, b2 = group["betas"]
+        bc2 = 1.0 - b2 ** k
+        rho_inf = 2.0 / (1.0 - b2) - 1.0
+        rho_t = rho_inf - 2.0 * k * (b2 ** k) / bc2
+        rect = 0.0
+        if rho_t > 5.0:
+            rect = math.sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t)) * math.sqrt(bc2)
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 / (1.0 - b1 ** k), rect,
+                1.0 if group.get("decoupled_weight_decay", False) else 0.0)
+
+
+class LARS(_ChunkedOptimizer):
+    """The reference's LARS (madrigal/utils.py:628-662, ``--pretrain_optimizer lars``): its defaults, its param-group keys and its
+    state (``mu`` per parameter), so a ``state_dict`` written by either side loads on the other.  Tensors with more than one dimension
+    take weight decay and the trust ratio q = trust_coefficient |p| / |g + wd p|; the others plain momentum.  ``step()`` is three
+    launches for all tensors (mdg_lars_multi): chunk norms, per-tensor q, update; nothing comes back to the host."""
+
+    def __init__(self, params, lr=0, weight_decay=0, momentum=0.9, trust_coefficient=0.001):
+        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum, trust_coefficient=trust_coefficient))
+        self._checked = set()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._checked = set()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        by_dev: Dict[torch.device, list] = {}
+        for group in self.param_groups:
+            hyper = (group["lr"], group["weight_decay"], group["momentum"], group["trust_coefficient"])
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                st = self.state[p]
+                if p not in self._checked:                      # first update of this parameter (or the first after a load)
+                    self._refuse(p, g)
+                    if "mu" not in st:
+                        st["mu"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    elif not st["mu"].is_contiguous():
+                        st["mu"] = st["mu"].contiguous()
+                    self._checked.add(p)
+                if p.numel() == 0:                              # nothing to update (every tensor of the tables owns a chunk)
+                    continue
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                by_dev.setdefault(p.device, []).append(((p, g, st["mu"]), hyper + (1.0 if p.ndim > 1 else 0.0,)))
+        for dev, items in by_dev.items():
+            lay, t_hyp = self._tables(dev, items)
+            if lay["n"] == 0:
+                continue
+            if "t_first" not in lay:                            # a tensor's chunks are consecutive: where they start, how many
+                cnt = np.bincount(lay["owner"], minlength=len(items)).astype(np.int32)
+                lay["t_first"] = torch.from_numpy((np.cumsum(cnt) - cnt).astype(np.int32)).to(dev)
+                lay["t_cnt"] = torch.from_numpy(cnt).to(dev)
+                lay["ws"] = torch.empty(int(lib().mdg_lars_multi_workspace_bytes(ctypes.c_int64(lay["n"]), ctypes.c_int64(len(items)))),
+                                        dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(lib().mdg_lars_multi(ctypes.c_void_p(lay["t_ptr"].data_ptr()), ctypes.c_void_p(lay["t_len"].data_ptr()),
+                                           ctypes.c_void_p(lay["t_own"].data_ptr()), ctypes.c_void_p(t_hyp.data_ptr()),
+                                           ctypes.c_void_p(lay["t_first"].data_ptr()), ctypes.c_void_p(lay["t_cnt"].data_ptr()),
+                                           ctypes.c_int64(lay["n"]), ctypes.c_int64(len(items)), ctypes.c_void_p(lay["ws"].data_ptr()),
+                                           ctypes.c_size_t(lay["ws"].numel()), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                      "mdg_lars_multi")
+            self._launched(dev, lay, t_hyp, [t for (p, _, mu), _ in items for t in (p, mu)])
         return loss
 
 
@@ -245,8 +372,23 @@ def parameter_groups(model: nn.Module, hparams: dict, include_learned_tokens: bo
     return [{"params": ps, "weight_decay": wd, "lr": lrs[kind]} for (kind, wd), ps in buckets.items() if ps]
 
 
-def create_optimizer(model: nn.Module, hparams: dict, include_learned_tokens: bool = False) -> AdamW:
-    """AdamW on the HIP path over ``parameter_groups`` (the reference's create_optimizer, madrigal/utils.py:463-613)."""
-    if hparams.get("optimizer", "adamw") != "adamw":
-        raise NotImplementedError("only AdamW runs on the HIP path (the reference's default, parse_args.py:135)")
-    return AdamW(parameter_groups(model, hparams, include_learned_tokens), betas=(hparams["beta1"], hparams["beta2"]), eps=hparams["eps"])
+def create_optimizer(model: nn.Module, hparams: dict, include_learned_tokens: bool = False):
+    """AdamW or RAdam on the HIP path over ``parameter_groups`` (the reference's create_optimizer, madrigal/utils.py:463-613: its
+    OPTIMIZER_CLASSES, both built from the groups, the betas and eps alone)."""
+    classes = {"adamw": AdamW, "radam": RAdam}
+    name = hparams.get("optimizer", "adamw")
+    if name not in classes:
+        raise NotImplementedError(f"optimizer {name!r}: the reference's create_optimizer knows 'adamw' (parse_args.py:135) and 'radam'")
+    return classes[name](parameter_groups(model, hparams, include_learned_tokens), betas=(hparams["beta1"], hparams["beta2"]), eps=hparams["eps"])
+
+
+def create_pretrain_optimizer(model: nn.Module, hparams: dict, name: str):
+    """pretrain.py:175-178: the contrastive stage's optimizer over ALL parameters of the SimCLR model in one group -- 'lars' with the
+    rate, decay and momentum of the pretraining flags, 'adamw' with the rate and decay (pretrain.py:173 has scaled the rate by
+    batch / 512 before; ``PretrainSchedule`` then drives it per iteration)."""
+    if name == "lars":
+        return LARS(model.parameters(), lr=hparams["pretrain_lr"], weight_decay=hparams["pretrain_wd"], momentum=hparams["pretrain_momentum"])
+    if name == "adamw":
+        return AdamW(model.parameters(), lr=hparams["pretrain_lr"], weight_decay=hparams["pretrain_wd"], eps=hparams["pretrain_eps"],
+                     betas=(hparams["pretrain_beta1"], 0.999))
+    raise NotImplementedError(f"pretraining optimizer {name!r}: the reference's drivers offer 'lars' and 'adamw'")
