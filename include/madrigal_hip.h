@@ -246,6 +246,23 @@ int mdg_assemble_tokens(const float* str_emb, const float* kg_emb, const float* 
 int mdg_fusion_attention(const float* qkv, int64_t ld, float* out, int64_t ldo, const uint32_t* kpm_bits,
                          const uint32_t* src_bits, float* probs, const int64_t* row_start, const uint32_t* row_bits, int64_t n,
                          int S, int H, int dh, void* stream);
+/* The same forward pass with q, k and v as operands of their own (ABI 13; no weights out): each with its row stride and a column step
+ * from one head to the next (hq / hk / hv; 0 = one block of columns shared by every head), ds columns in the score product and dv
+ * in the value product (multiples of 4, at most 1024; a partial last 64-column piece is zero-filled), out with its own row stride
+ * ldo and head step ho >= dv.  Masks and compact mode as above.  With q = qkv, k = qkv + d, v = qkv + 2d, steps dh and
+ * qscale = 1/sqrt(dh) the result is mdg_fusion_attention's bit for bit.
+ * Layer 0 of a pre-norm fusion transformer in token space (TransformerFusion._layer0_tokenspace): h = T W_e^T + b_e has rank
+ * <= D, so with x_j = r_j [T_j; 1] (r = norm1's per-row factor) the logits are x_j . u_h,i and the head outputs V~_h sum_j P x_j:
+ * k = v = X [R, Dp] shared by the heads, q = U [R, H*Dp] from mdg_linear_rowscaled, qscale = 1, and out_proj runs on [O | T].
+ * mdg_token_scaled_rows makes X, r and the T columns behind O from the token rows (D = 128, Dp = 132):
+ *   r[i] = 1 / sqrt(|R_f [T_i; 1]|^2 / d + eps)   (rf [nr <= Dp, Dp] row-major: |R_f [T;1]| = |W_c T + b_c|, W_c / b_c centred)
+ *   X[i] = r[i] [T_i, 1, 0, 0, 0]   (ldx >= Dp),   tail[i] = T_i   (ldtail >= D; all row strides multiples of 4, 16-byte aligned). */
+int mdg_fusion_attention_qkv(const float* q, int64_t ldq, int hq, const float* k, int64_t ldk, int hk, const float* v, int64_t ldv,
+                             int hv, float* out, int64_t ldo, int ho, const uint32_t* kpm_bits, const uint32_t* src_bits,
+                             const int64_t* row_start, const uint32_t* row_bits, int64_t n, int S, int H, int ds, int dv,
+                             float qscale, void* stream);
+int mdg_token_scaled_rows(const float* tokens, int64_t ldt, const float* rf, int nr, int64_t D, int64_t d, float eps, float* X,
+                          int64_t ldx, float* tail, int64_t ldtail, float* rstd, int64_t rows, void* stream);
 
 /* Cross-attention pooling with one learned query shared by all drugs: out[i,h,:] = softmax_j(q_h . K_ijh / sqrt(dh)) V_ijh.
  * q_proj [H*dh] (already projected), kv_proj [n*Tk, 2*H*dh] = K|V of the Tk allowed key tokens of each drug.

@@ -105,6 +105,8 @@ __device__ __forceinline__ void write_rows(const f32x4 (&r)[8], float* tile, int
 // pass.  m is staged 64 columns at a time, the next piece in flight (in registers) while the current one feeds the MFMAs from
 // LDS; with the weights as the A operand the result comes out with the lane on the column, so every store is a 128-byte
 // row piece.
+// kTrim: dh need not be a multiple of 64; the 32-column halves of the last piece that lie wholly past dh are skipped.
+template <bool kTrim = false>
 __device__ __forceinline__ void weights_rows_product(const f32x16& w, const float* m, int64_t ldm, float* out, int64_t ldo, int T, int dh,
                                                      float* ta, float* tb, int x, int half, int lane) {
   f32x4 pre[8];
@@ -117,6 +119,7 @@ __device__ __forceinline__ void weights_rows_product(const f32x16& w, const floa
     if (more) load_rows(m, ldm, T, c0 + 64, dh, lane, pre);
 #pragma unroll
     for (int hc = 0; hc < 2; ++hc) {
+      if (kTrim && c0 + hc * 32 >= dh) break;
       const int col = hc * 32 + x;
       f32x16 o;
 #pragma unroll
@@ -140,6 +143,8 @@ __device__ __forceinline__ void weights_rows_product(const f32x16& w, const floa
 
 // acc += B^T-style product of the swapped layout: acc[v] (lane x) += sum_k a[j_v][k] * b[x][k] over the dh columns of two
 // row-major operands a (rows -> accumulator registers) and b (rows -> lanes), b scaled by `bscale`.
+// kTrim: the 8-column steps of the last piece that lie wholly past dh (zero on both sides) are skipped.
+template <bool kTrim = false>
 __device__ __forceinline__ void rows_product(const float* a, int64_t lda, const float* b, int64_t ldb, int T, int dh, float bscale, float* ta,
                                              float* tb, int x, int half, int lane, f32x16& acc) {
   f32x4 ra[8], rb[8];
@@ -154,6 +159,7 @@ __device__ __forceinline__ void rows_product(const float* a, int64_t lda, const 
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
+      if (kTrim && k0 + 8 * q >= dh) break;
       const f32x4 af = *reinterpret_cast<const f32x4*>(ta + tile_off(x, 2 * q + half));
       const f32x4 bf = *reinterpret_cast<const f32x4*>(tb + tile_off(x, 2 * q + half));
 #pragma unroll
@@ -162,16 +168,14 @@ __device__ __forceinline__ void rows_product(const float* a, int64_t lda, const 
   }
 }
 
-// Scores -> attention weights of one (tile, head) wave, in the swapped layout: lane (x = query, half) holds
-// acc[v] = P[x][j], j = (v&3) + 8(v>>2) + 4*half.  Shared by the forward and the backward kernel.  qmat / kmat: the tile's
-// first row of q / k at this head's columns; ta / tb: the wave's two staging tiles.
-__device__ __forceinline__ void attn_weights(const AttnArgs& p, const float* qmat, const float* kmat, int64_t drug, int64_t base, int x, int xr, int T,
-                                             int half, int lane, float* ta, float* tb, f32x16& acc) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-  rows_product(kmat, p.ld, qmat, p.ld, T, p.dh, p.qscale, ta, tb, x, half, lane, acc);
-  const uint32_t blocked = p.row_start ? (p.row_bits ? p.row_bits[base + xr] : 0u)
-                                       : ((p.kpm_bits ? p.kpm_bits[drug] : 0u) | (p.src_bits ? p.src_bits[xr] : 0u));
+// bit j set = key j of the tile is not allowed for query row xr (compact: the row's own bits; dense: key padding | source mask)
+__device__ __forceinline__ uint32_t attn_blocked(const int64_t* row_start, const uint32_t* row_bits, const uint32_t* kpm_bits,
+                                                 const uint32_t* src_bits, int64_t drug, int64_t base, int xr) {
+  return row_start ? (row_bits ? row_bits[base + xr] : 0u) : ((kpm_bits ? kpm_bits[drug] : 0u) | (src_bits ? src_bits[xr] : 0u));
+}
+
+// scores -> softmax over the allowed keys, in place, in the swapped layout (lane (x, half) holds keys j = (v&3) + 8(v>>2) + 4*half)
+__device__ __forceinline__ void masked_softmax(f32x16& acc, uint32_t blocked, int T, int half) {
   float m = -INFINITY;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
@@ -190,6 +194,17 @@ __device__ __forceinline__ void attn_weights(const AttnArgs& p, const float* qma
   const float inv = 1.0f / sum;
 #pragma unroll
   for (int v = 0; v < 16; ++v) acc[v] *= inv;
+}
+
+// Scores -> attention weights of one (tile, head) wave, in the swapped layout: lane (x = query, half) holds
+// acc[v] = P[x][j], j = (v&3) + 8(v>>2) + 4*half.  Shared by the forward and the backward kernel.  qmat / kmat: the tile's
+// first row of q / k at this head's columns; ta / tb: the wave's two staging tiles.
+__device__ __forceinline__ void attn_weights(const AttnArgs& p, const float* qmat, const float* kmat, int64_t drug, int64_t base, int x, int xr, int T,
+                                             int half, int lane, float* ta, float* tb, f32x16& acc) {
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  rows_product(kmat, p.ld, qmat, p.ld, T, p.dh, p.qscale, ta, tb, x, half, lane, acc);
+  masked_softmax(acc, attn_blocked(p.row_start, p.row_bits, p.kpm_bits, p.src_bits, drug, base, xr), T, half);
 }
 
 // keep / (1-p) factor of attention weight (wave gw, query x, key j)
@@ -232,6 +247,114 @@ __global__ __launch_bounds__(256) void fusion_attention_kernel(const AttnArgs p)
   }
 
   weights_rows_product(acc, qmat + 2 * d, p.ld, p.out + base * p.ldo + head * p.dh, p.ldo, T, p.dh, stage[wave][0], stage[wave][1], x, half, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same forward pass with q, k and v as three operands of their own: each has its row stride and a per-head column step
+// (0: one block of columns shared by every head), the score product runs over ds columns and the value product over dv, and the
+// output has its own row stride and per-head step.  ds / dv are multiples of 4; the last 64-column piece may be partial.
+// No attention weights out, no dropout.  Layer 0 in token space (TransformerFusion._layer0_tokenspace): k = v = the scaled
+// augmented token rows X [R, Dp] shared by all heads, q = the per-head rows U [R, H*Dp], qscale = 1.
+// ---------------------------------------------------------------------------------------------
+struct AttnQkvArgs {
+  const float* q; const float* k; const float* v;
+  int64_t ldq, ldk, ldv;
+  int hq, hk, hv;                    // column step from one head to the next
+  float* out; int64_t ldo; int ho;
+  const uint32_t* kpm_bits; const uint32_t* src_bits; const int64_t* row_start; const uint32_t* row_bits;   // as AttnArgs
+  int64_t n;
+  int S, H, ds, dv;
+  float qscale;
+};
+
+__global__ __launch_bounds__(256) void fusion_attention_qkv_kernel(const AttnQkvArgs p) {
+  __shared__ __attribute__((aligned(16))) float stage[4][2][kTileFloats];
+  const int lane = threadIdx.x & 63, x = lane & 31, half = lane >> 5, wave = threadIdx.x >> 6;
+  const int64_t gw = static_cast<int64_t>(blockIdx.x) * 4 + wave;
+  if (gw >= p.n * p.H) return;
+  const int64_t drug = gw / p.H;
+  const int head = static_cast<int>(gw % p.H);
+  const int64_t base = p.row_start ? p.row_start[drug] : drug * p.S;
+  const int T = p.row_start ? static_cast<int>(p.row_start[drug + 1] - base) : p.S;
+  if (T <= 0) return;
+  const int xr = x < T ? x : T - 1;
+  float* const ta = stage[wave][0];
+  float* const tb = stage[wave][1];
+
+  f32x16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  rows_product<true>(p.k + base * p.ldk + head * p.hk, p.ldk, p.q + base * p.ldq + head * p.hq, p.ldq, T, p.ds, p.qscale, ta, tb, x, half,
+                     lane, acc);
+  masked_softmax(acc, attn_blocked(p.row_start, p.row_bits, p.kpm_bits, p.src_bits, drug, base, xr), T, half);
+  weights_rows_product<true>(acc, p.v + base * p.ldv + head * p.hv, p.ldv, p.out + base * p.ldo + head * p.ho, p.ldo, T, p.dv, ta, tb, x,
+                             half, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Layer 0 in token space, the rows it starts from.  Per token row T_i (D = 128 wide):
+//   r_i = 1 / sqrt(|R_f [T_i; 1]|^2 / d + eps)     R_f [nr, Dp]: |R_f [T;1]| = |W_c T + b_c|, the centred embed2latent (a QR factor)
+//   X[i] = r_i * [T_i, 1, 0...]  [Dp]              the scaled augmented row: key and value operand of the attention
+//   tail[i] = T_i                                   copied behind the attention's output columns (the out_proj block reads [O | T])
+// 64 rows per workgroup, one lane per row with its row in registers; R_f is uniform across the wave (scalar loads), its rows dealt
+// round-robin to the eight waves (the scalar loads are what a wave waits for: more waves, not more work per wave), whose partial
+// sums of squares meet in LDS.
+// ---------------------------------------------------------------------------------------------
+constexpr int kTokD = 128, kTokDp = 132, kTokWaves = 8;
+
+__global__ __launch_bounds__(64 * kTokWaves) void token_scaled_rows_kernel(const float* __restrict__ tok, int64_t ldt, const float* __restrict__ rf, int nr,
+                                                                float inv_d, float eps, float* __restrict__ X, int64_t ldx,
+                                                                float* __restrict__ tail, int64_t ldtail, float* __restrict__ rstd,
+                                                                int64_t rows) {
+  __shared__ __attribute__((aligned(16))) float rowsT[64][kTokDp];
+  __shared__ float part[kTokWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * 64;
+  const int nrow = rows - row0 < 64 ? static_cast<int>(rows - row0) : 64;
+  // coalesced copy of the 64 token rows into LDS (rows past the end: zeros), and on to the tail columns
+  for (int i = threadIdx.x; i < 64 * (kTokD / 4); i += 64 * kTokWaves) {
+    const int r = i / (kTokD / 4), c = 4 * (i % (kTokD / 4));
+    f32x4 v{0.f, 0.f, 0.f, 0.f};
+    if (r < nrow) {
+      v = *reinterpret_cast<const f32x4*>(tok + (row0 + r) * ldt + c);
+      *reinterpret_cast<f32x4*>(tail + (row0 + r) * ldtail + c) = v;
+    }
+    *reinterpret_cast<f32x4*>(&rowsT[r][c]) = v;
+  }
+  __syncthreads();
+  f32x4 t[kTokD / 4];
+#pragma unroll
+  for (int c = 0; c < kTokD / 4; ++c) t[c] = *reinterpret_cast<const f32x4*>(&rowsT[lane][4 * c]);
+  float ss = 0.f;
+  for (int k = wave; k < nr; k += kTokWaves) {
+    const float* rk = rf + static_cast<int64_t>(k) * kTokDp;
+    float y = rk[kTokD];                                         // the column of the appended 1
+#pragma unroll
+    for (int c = 0; c < kTokD / 4; ++c) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y = __builtin_fmaf(rk[4 * c + e], t[c][e], y);
+    }
+    ss = __builtin_fmaf(y, y, ss);
+  }
+  part[wave][lane] = ss;
+  __syncthreads();
+  if (wave == 0) {
+    float sum = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < kTokWaves; ++w) sum += part[w][lane];
+    const float r = 1.0f / sqrtf(sum * inv_d + eps);
+    part[0][lane] = r;
+    if (lane < nrow) rstd[row0 + lane] = r;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * (kTokDp / 4); i += 64 * kTokWaves) {
+    const int r = i / (kTokDp / 4), c = 4 * (i % (kTokDp / 4));
+    if (r >= nrow) continue;
+    const float s = part[0][r];
+    f32x4 v = c < kTokD ? *reinterpret_cast<const f32x4*>(&rowsT[r][c]) : f32x4{1.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(X + (row0 + r) * ldx + c) = v * s;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -664,6 +787,43 @@ extern "C" int mdg_fusion_attention(const float* qkv, int64_t ld, float* out, in
                                     const uint32_t* src_bits, float* probs, const int64_t* row_start, const uint32_t* row_bits,
                                     int64_t n, int S, int H, int dh, void* stream) {
   return mdg_fusion_attention_dropout(qkv, ld, out, ldo, kpm_bits, src_bits, probs, row_start, row_bits, n, S, H, dh, 0.f, 0, stream);
+}
+
+extern "C" int mdg_fusion_attention_qkv(const float* q, int64_t ldq, int hq, const float* k, int64_t ldk, int hk, const float* v, int64_t ldv,
+                                        int hv, float* out, int64_t ldo, int ho, const uint32_t* kpm_bits, const uint32_t* src_bits,
+                                        const int64_t* row_start, const uint32_t* row_bits, int64_t n, int S, int H, int ds, int dv,
+                                        float qscale, void* stream) {
+  const char* who = "mdg_fusion_attention_qkv";
+  MDG_CHECK_ARG(n >= 0 && S >= 1 && S <= 32, "%s: S must be in [1,32] (got %d)", who, S);
+  MDG_CHECK_ARG(H >= 1 && ds >= 4 && ds % 4 == 0 && ds <= 1024 && dv >= 4 && dv % 4 == 0 && dv <= 1024,
+                "%s: the score and value widths must be multiples of 4 in [4,1024] (got %d, %d)", who, ds, dv);
+  if (n == 0) return MDG_OK;
+  MDG_CHECK_ARG(q && k && v && out, "%s: null pointer", who);
+  const auto span = [H](int step, int w) { return static_cast<int64_t>(H - 1) * step + w; };
+  MDG_CHECK_ARG(hq >= 0 && hk >= 0 && hv >= 0 && hq % 4 == 0 && hk % 4 == 0 && hv % 4 == 0 && ho % 4 == 0 && (H == 1 || ho >= dv),
+                "%s: head steps must be multiples of 4, the output's at least the value width", who);
+  MDG_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldq >= span(hq, ds) && ldk >= span(hk, ds) &&
+                    ldv >= span(hv, dv) && ldo >= span(ho, dv) && mdg_aligned16(q) && mdg_aligned16(k) && mdg_aligned16(v) && mdg_aligned16(out),
+                "%s: bad strides / alignment", who);
+  AttnQkvArgs a{q, k, v, ldq, ldk, ldv, hq, hk, hv, out, ldo, ho, kpm_bits, src_bits, row_start, row_bits, n, S, H, ds, dv, qscale};
+  hipLaunchKernelGGL(fusion_attention_qkv_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n * H, 4))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a);
+  MDG_CHECK_LAUNCH(who);
+  return MDG_OK;
+}
+
+extern "C" int mdg_token_scaled_rows(const float* tokens, int64_t ldt, const float* rf, int nr, int64_t D, int64_t d, float eps, float* X,
+                                     int64_t ldx, float* tail, int64_t ldtail, float* rstd, int64_t rows, void* stream) {
+  MDG_CHECK_ARG(D == kTokD, "mdg_token_scaled_rows: token rows must be %d wide (got %lld)", kTokD, static_cast<long long>(D));
+  MDG_CHECK_ARG(rows >= 0 && d >= 1 && nr >= 1 && nr <= kTokDp && eps >= 0.f, "mdg_token_scaled_rows: bad sizes");
+  if (rows == 0) return MDG_OK;
+  MDG_CHECK_ARG(tokens && rf && X && tail && rstd, "mdg_token_scaled_rows: null pointer");
+  MDG_CHECK_ARG(ldt % 4 == 0 && ldt >= kTokD && ldx % 4 == 0 && ldx >= kTokDp && ldtail % 4 == 0 && ldtail >= kTokD && mdg_aligned16(tokens) &&
+                    mdg_aligned16(X) && mdg_aligned16(tail), "mdg_token_scaled_rows: bad strides / alignment");
+  hipLaunchKernelGGL(token_scaled_rows_kernel, dim3(static_cast<unsigned>(mdg_cdiv(rows, 64))), dim3(64 * kTokWaves), 0,
+                     static_cast<hipStream_t>(stream), tokens, ldt, rf, nr, 1.0f / static_cast<float>(d), eps, X, ldx, tail, ldtail, rstd, rows);
+  MDG_CHECK_LAUNCH("mdg_token_scaled_rows");
+  return MDG_OK;
 }
 
 extern "C" int mdg_fusion_attention_bwd(const float* qkv, int64_t ld, const float* dout, int64_t lddo, float* dqkv, int64_t lddq,

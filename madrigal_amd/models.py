@@ -1125,6 +1125,43 @@ def compose_qkv0(We, be, Wq, bq, norm=None):
     return Wg @ (We - We.mean(0, keepdim=True)), Wg @ (be - be.mean()), Wq @ b1 + bq
 
 
+def compose_layer0_tokenspace(We, be, Wi, bi, Wo, bo, g1, b1, H: int):
+    """fp64 fold of layer 0's whole attention block (pre-norm, eval mode) into the D-wide token space.  h = T We^T + be has rank <= D, so
+    with t~ = [T; 1], r = 1 / sqrt(var(h) + eps) and x_j = r_j t~_j (compose_qkv0's M, c, c2 split per head into Q~_h = [M_q,h | c_q,h],
+    K~_h, V~_h [dh, D+1] and d_q,h, d_v,h; s = 1 / sqrt(dh)):
+        logit_h[i, j] = x_j . u_h,i + (terms without j: they cancel in the softmax),   u_h,i = r_i (A_h t~_i) + a_h,
+        A_h = s K~_h^T Q~_h  [(D+1), (D+1)],   a_h = s K~_h^T d_q,h
+        att_h,i = V~_h O_h,i + d_v,h,   O_h,i = sum_j P_h[i, j] x_j                  (a head's weights sum to one)
+        out_proj(att_i) + h_i = [O_1,i | ... | O_H,i | T_i] C_ext^T + c_out,   C_ext = [Wo[:, 1] V~_1 | ... | Wo[:, H] V~_H | We],
+        c_out = Wo d_v + bo + be
+    Each head's D+1 columns are padded with zeros to Dp = D+1 rounded up to 4.  Returns (A_stack [H*Dp, D], bias_pre [H*Dp], a [H*Dp],
+    C_ext [d, H*Dp + D], c_out [d], R_f [(D+1), (D+1)]): u = r (T A_stack^T + bias_pre) + a is ops.linear_rowscaled's form, and R_f is the
+    triangular factor of [W_c | b_c] (We, be centred over the d outputs), |R_f t~| = |W_c T + b_c| = sqrt(d var(h)): a sum of D+1
+    squares, nothing of mixed sign beyond the dot products themselves."""
+    f8 = torch.float64
+    M, c, c2 = compose_qkv0(We, be, Wi, bi, (g1, b1))
+    We, be, Wo, bo = (t.detach().to(f8) for t in (We, be, Wo, bo))
+    d, D = We.shape
+    dh, D1 = d // H, D + 1
+    Dp = (D1 + 3) // 4 * 4
+    s = 1.0 / math.sqrt(dh)
+    Mt = torch.cat([M, c[:, None]], 1)                                              # [3d, D+1]
+    Qt, Kt, Vt = (Mt[i * d:(i + 1) * d].reshape(H, dh, D1) for i in range(3))
+    dq, dv = c2[:d].reshape(H, dh, 1), c2[2 * d:]
+    A = torch.zeros(H, Dp, D1, dtype=f8, device=We.device)
+    A[:, :D1] = s * (Kt.transpose(1, 2) @ Qt)
+    a = torch.zeros(H, Dp, dtype=f8, device=We.device)
+    a[:, :D1] = s * (Kt.transpose(1, 2) @ dq)[..., 0]
+    C = torch.zeros(d, H, Dp, dtype=f8, device=We.device)
+    C[:, :, :D1] = torch.einsum("ohk,hkc->ohc", Wo.reshape(d, H, dh), Vt)
+    C_ext = torch.cat([C.reshape(d, H * Dp), We], 1)
+    Wb = torch.cat([We - We.mean(0, keepdim=True), (be - be.mean())[:, None]], 1)   # [d, D+1]
+    Rq = torch.linalg.qr(Wb.cpu(), mode="r").R                                      # [min(d, D+1), D+1] (host LAPACK: once per parameter version)
+    R_f = torch.zeros(D1, D1, dtype=f8, device=We.device)
+    R_f[:Rq.shape[0]] = Rq.to(We.device)
+    return (A[:, :, :D].reshape(H * Dp, D).contiguous(), A[:, :, D].reshape(-1).contiguous(), a.reshape(-1), C_ext, Wo @ dv + bo + be, R_f)
+
+
 def compose_xattn_pool(query, q_norm, Wi, bi, Wo, bo, Wle, ble, H: int):
     """fp64 fold of the eval-mode cross-attention pooling (models.py:422-443, pre-norm) through V, out_proj, the query residual and
     latent2embed.  query [1, d], q_norm = (gamma, beta, eps) of x_attn_query_norm or None, in_proj (Wi [3d, d], bi), out_proj (Wo, bo),
@@ -1186,6 +1223,8 @@ class TransformerFusion(nn.Module):
         self.last_attention_weights = None
         # eval path: layer 0's QKV block from the token rows through the composed weights (_qkv0); False: norm1 -> in_proj on h
         self.compose_layer0 = True
+        # eval path, pre-norm: layer 0's whole attention block in the 128-wide token space (_layer0_tokenspace); False: the path above
+        self.compose_layer0_attn = True
         # eval path: the x-attn pooling folded through V, out_proj and latent2embed (_x_attn_pool_folded); False: K|V block -> pool
         self.compose_pool = True
 
@@ -1210,11 +1249,46 @@ class TransformerFusion(nn.Module):
             return ops.linear(tokens, M, c2, precision=prec, weight_image=img)
         return ops.linear_rowscaled(tokens, M, ops.row_rstd(h, L.norm1.eps), c, c2, precision=prec, weight_image=img)
 
+    # ---- layer 0's attention block in token space -------------------------------------------------
+    def _tokenspace_ok(self) -> bool:
+        """Whether layer 0 runs its attention block on the D-wide token rows (compose_layer0_tokenspace): the composed path's
+        conditions, a pre-norm layer 0 that is not the last layer, no forward hooks on an attention module, and an out_proj block
+        whose inner length K' = H*Dp + D is shorter than the d it replaces (the rule and its measurements)."""
+        H, D, d = self.num_heads, self.embed2latent.in_features, self.latent_dim
+        layers = self.transformer_encoder.layers
+        return (self.compose_layer0 and self.compose_layer0_attn and self.norm_first and len(layers) > 1 and D == 128
+                and H * ((D + 4) // 4 * 4) + D < d and _state["precision"] in ("f32", "bf16x3", "bf16")
+                and not any(len(L.self_attn._forward_hooks) for L in layers))
+
+    def _layer0_tokenspace(self, L, tokens, attend):
+        """h after layer 0's attention block, out_proj(attention(norm1(h0))) + h0 with h0 = embed2latent(T), from the token rows T alone:
+        one kernel T -> (X = r [T, 1, 0..], r, the T columns of the out_proj input), U = r (T A^T + bias_pre) + a on the 128-tile block
+        (K = 128, N = H*Dp), the attention with X as every head's key and value rows and U as the queries, writing O beside T, and one
+        dense block [O | T] C_ext^T + c_out.  Neither h0 nor a 3d-wide QKV block is ever formed.  ``attend((q, k, v, Dp), None, out)``."""
+        sa, prec, H, d = L.self_attn, _state["precision"], self.num_heads, self.latent_dim
+
+        def build():
+            A, bp, a, C, co, Rf = (t.to(torch.float32).contiguous() for t in compose_layer0_tokenspace(
+                self.embed2latent.weight, self.embed2latent.bias, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
+                L.norm1.weight, L.norm1.bias, H))
+            Rf = torch.nn.functional.pad(Rf, (0, A.shape[0] // H - Rf.shape[1])).contiguous()         # rows [D+1, Dp]
+            return A, bp, a, C, co, Rf, ops.pack_operand(A, prec), ops.pack_operand(C, prec)
+        srcs = (self.embed2latent.weight, self.embed2latent.bias, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
+                L.norm1.weight, L.norm1.bias)
+        A, bp, a, C, co, Rf, A_img, C_img = _cached(self, ("layer0_ts", prec), srcs, build)
+        Dp, R = Rf.shape[1], tokens.shape[0]
+        ot = torch.empty((R, C.shape[1]), dtype=torch.float32, device=tokens.device)               # [O | T]
+        X, r = ops.token_scaled_rows(tokens, Rf, d, L.norm1.eps, ot[:, H * Dp:])
+        U = ops.linear_rowscaled(tokens, A, r, bp, a, precision=prec, weight_image=A_img)
+        attend((U, X, X, Dp), None, ot)
+        return ops.linear(ot, C, co, precision=prec, weight_image=C_img)
+
     # ---- one transformer layer on a set of token rows (dense or compact) --------------------
     def _layer(self, L, h, attend, keep_rows=None, tokens=None):
         """``attend(qkv) -> attention output rows``; ``keep_rows`` (int64 index) prunes the rows that
         continue after the attention (last layer: only the pooled key tokens are ever read again).  ``tokens``: layer 0's input
-        rows ahead of embed2latent, whose QKV block then comes from ``_qkv0`` (``attend`` sees no normalised rows)."""
+        rows ahead of embed2latent, whose QKV block then comes from ``_qkv0`` (``attend`` sees no normalised rows); with ``h`` None the
+        whole attention block comes from them (``_layer0_tokenspace``)."""
         sa = L.self_attn
 
         def norm(x, ln, want_fp32=True):
@@ -1240,14 +1314,17 @@ class TransformerFusion(nn.Module):
             qkv[:, :d].index_copy_(0, keep_rows, _lin(a.index_select(0, keep_rows), w[:d], b[:d]))
             return qkv
         if self.norm_first:
-            if tokens is not None:
-                att = attend(self._qkv0(L, tokens, h), None)
+            if tokens is not None and h is None:
+                h = self._layer0_tokenspace(L, tokens, attend)
             else:
-                a, a_img = norm(h, L.norm1)
-                att = attend(in_proj(a, a_img), a)
-            if keep_rows is not None:
-                att, h = att.index_select(0, keep_rows), h.index_select(0, keep_rows)
-            h = _lin(att, sa.out_proj.weight, sa.out_proj.bias, residual=h)
+                if tokens is not None:
+                    att = attend(self._qkv0(L, tokens, h), None)
+                else:
+                    a, a_img = norm(h, L.norm1)
+                    att = attend(in_proj(a, a_img), a)
+                if keep_rows is not None:
+                    att, h = att.index_select(0, keep_rows), h.index_select(0, keep_rows)
+                h = _lin(att, sa.out_proj.weight, sa.out_proj.bias, residual=h)
             f, f_img = norm(h, L.norm2, want_fp32=False)
             u = lin_of(f, f_img, L.linear1.weight, L.linear1.bias, rows=h.shape[0], act=self.actn)
             return _lin(u, L.linear2.weight, L.linear2.bias, residual=h)
@@ -1407,19 +1484,23 @@ class TransformerFusion(nn.Module):
                 keep, Tk = torch.arange(n, device=dev) * S, None
             return self._forward_train(fusion_sequence.reshape(n * S, D), n, S, attend_t, keep, True, Tk)
         x0 = fusion_sequence.reshape(n * S, D)
-        h = _lin(x0, self.embed2latent.weight, self.embed2latent.bias)
+        ts = self._tokenspace_ok()
+        h = None if ts else _lin(x0, self.embed2latent.weight, self.embed2latent.bias)
         layers = self.transformer_encoder.layers
         for li, L in enumerate(layers):
             want = li == len(layers) - 1
             seen = {}
 
-            def attend(qkv, x_in, want=want, seen=seen):
+            def attend(qkv, x_in, out=None, want=want, seen=seen):
+                if isinstance(qkv, tuple):            # (q, k, v, width): layer 0 in token space, k and v shared by the heads
+                    q, k, v, w = qkv
+                    return ops.fusion_attention_qkv(q, k, v, n, S, H, w, w, hq=w, hk=0, hv=0, out=out, ho=w, kpm_bits=kbits, src_bits=sbits)
                 att, pr = ops.fusion_attention(qkv, n, S, H, dh, kbits, sbits, want_probs=want)
                 seen["att"], seen["pr"], seen["in"] = att, pr, x_in
                 return att
             # the hooks of a last layer 0 are handed its normalised rows: those exist on the uncomposed path only
             compose = li == 0 and self.compose_layer0 and not (want and self.norm_first and len(L.self_attn._forward_hooks))
-            h = self._layer(L, h, attend, tokens=x0 if compose else None)
+            h = self._layer(L, h, attend, tokens=x0 if compose else None)            # (h None: token space, where compose holds)
             if want:
                 self.last_attention_weights = seen["pr"]
                 for hook in list(L.self_attn._forward_hooks.values()):      # analysis hooks expect (attn_out, weights)
@@ -1531,11 +1612,15 @@ class TransformerFusion(nn.Module):
                 return ag.fusion_attention(qkv, plan["n_tiles"], S, H, dh, row_start=plan["tile_start"], row_bits=plan["row_bits"],
                                            p_drop=p_att)
             return self._forward_train(tokens, n, S, attend_t, plan.get("key_rows"), False, plan.get("Tk"))
-        h = _lin(tokens, self.embed2latent.weight, self.embed2latent.bias)
+        h = None if self._tokenspace_ok() else _lin(tokens, self.embed2latent.weight, self.embed2latent.bias)
         layers = self.transformer_encoder.layers
         agg = self.transformer_agg
 
-        def attend(qkv, _x):
+        def attend(qkv, _x, out=None):
+            if isinstance(qkv, tuple):                # (q, k, v, width): layer 0 in token space, k and v shared by the heads
+                q, k, v, w = qkv
+                return ops.fusion_attention_qkv(q, k, v, plan["n_tiles"], S, H, w, w, hq=w, hk=0, hv=0, out=out, ho=w,
+                                                row_start=plan["tile_start"], row_bits=plan["row_bits"])
             return ops.fusion_attention(qkv, plan["n_tiles"], S, H, dh, row_start=plan["tile_start"], row_bits=plan["row_bits"])[0]
         for li, L in enumerate(layers):
             last = li == len(layers) - 1

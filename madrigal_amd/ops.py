@@ -679,6 +679,58 @@ def fusion_attention(qkv: torch.Tensor, n: int, S: int, H: int, dh: int, kpm_bit
     return out, probs
 
 
+def fusion_attention_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: int, S: int, H: int, ds: int, dv: int, *, hq: int, hk: int,
+                         hv: int, out: Optional[torch.Tensor] = None, ho: Optional[int] = None, kpm_bits=None, src_bits=None,
+                         row_start: Optional[torch.Tensor] = None, row_bits: Optional[torch.Tensor] = None,
+                         qscale: float = 1.0) -> torch.Tensor:
+    """``fusion_attention``'s forward pass on three operands of their own (2-D fp32 views with unit inner stride): ``hq`` / ``hk`` /
+    ``hv`` the column step from one head to the next (0: the operand's first columns serve every head), ``ds`` columns in the score
+    product and ``dv`` in the value product.  ``out`` (view, head step ``ho`` >= dv) defaults to a fresh [rows, H*dv]."""
+    forward_only(q, k, v)
+    rows = q.shape[0]
+    for nm, t in (("q", q), ("k", k), ("v", v)) + ((("out", out),) if out is not None else ()):
+        if t.dim() != 2 or t.shape[0] != rows or t.stride(1) != 1 or t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f"{nm}: expected a 2-D fp32 cuda tensor of {rows} rows with unit inner stride")
+    if row_start is None and rows != n * S:
+        raise ValueError(f"q: expected {n * S} rows, got {rows}")
+    if row_start is not None and (row_start.dtype != torch.int64 or row_start.numel() != n + 1):
+        raise ValueError("row_start: int64 [n+1]")
+    for nm, t, step, w in (("q", q, hq, ds), ("k", k, hk, ds), ("v", v, hv, dv)):
+        if t.shape[1] < (H - 1) * step + w:
+            raise ValueError(f"{nm}: {t.shape[1]} columns do not hold {H} heads of step {step} and width {w}")
+    if out is None:
+        ho = dv if ho is None else ho
+        out = torch.empty((rows, (H - 1) * ho + dv), dtype=torch.float32, device=q.device)
+    elif ho is None or out.shape[1] < (H - 1) * ho + dv:
+        raise ValueError("out: give its head step ho, and columns for H heads of it")
+    check(lib().mdg_fusion_attention_qkv(_ptr(q), _c64(q.stride(0)), _c(hq), _ptr(k), _c64(k.stride(0)), _c(hk), _ptr(v), _c64(v.stride(0)),
+                                         _c(hv), _ptr(out), _c64(out.stride(0)), _c(ho), _ptr(kpm_bits), _ptr(src_bits), _ptr(row_start),
+                                         _ptr(row_bits), _c64(n), _c(S), _c(H), _c(ds), _c(dv), _f(qscale), _stream(q)),
+          "mdg_fusion_attention_qkv")
+    return out
+
+
+def token_scaled_rows(tokens: torch.Tensor, rf: torch.Tensor, d: int, eps: float, tail: torch.Tensor):
+    """Token rows T [R, 128] -> (X [R, 132] = r * [T, 1, 0, 0, 0], r [R]) with r = 1 / sqrt(|rf [T; 1]|^2 / d + eps) (``rf`` [nr <= 132, 132]:
+    the triangular factor of the centred embed2latent, so r is norm1's factor of h = embed2latent(T)); T is also copied into
+    ``tail`` (a [R, 128] view, e.g. the last columns of the out_proj block's input)."""
+    forward_only(tokens, rf)
+    t = tokens if (tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.stride(0) % 4 == 0 and tokens.is_cuda
+                   and tokens.dtype == torch.float32) else _f32_cuda(tokens, "tokens", 2)
+    R, D = t.shape
+    rf = _f32_cuda(rf, "rf", 2)
+    Dp = (D + 4) // 4 * 4
+    if rf.shape[1] != Dp or rf.shape[0] > Dp:
+        raise ValueError(f"rf: expected [<= {Dp}, {Dp}], got {tuple(rf.shape)}")
+    if tail.shape != (R, D) or tail.stride(1) != 1 or tail.dtype != torch.float32 or not tail.is_cuda:
+        raise ValueError(f"tail: expected an fp32 cuda [{R},{D}] view with unit inner stride")
+    X = torch.empty((R, Dp), dtype=torch.float32, device=t.device)
+    r = torch.empty(R, dtype=torch.float32, device=t.device)
+    check(lib().mdg_token_scaled_rows(_ptr(t), _c64(t.stride(0)), _ptr(rf), _c(rf.shape[0]), _c64(D), _c64(d), _f(eps), _ptr(X), _c64(Dp),
+                                      _ptr(tail), _c64(tail.stride(0)), _ptr(r), _c64(R), _stream(t)), "mdg_token_scaled_rows")
+    return X, r
+
+
 def fusion_attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, n: int, S: int, H: int, dh: int, kpm_bits=None, src_bits=None,
                          row_start=None, row_bits=None, p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:
     """Gradient of the q|k|v rows given the gradient of the attention output (weights recomputed, mask replayed)."""
