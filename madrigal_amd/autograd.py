@@ -784,8 +784,8 @@ class _InfoNCE(Function):
         labels = torch.empty_like(logits)
         row = torch.empty(2 * B, dtype=torch.float32, device=f.device)
         loss = torch.empty(1, dtype=torch.float32, device=f.device)
-        ops.check(ops.lib().mdg_infonce_finish(ops._ptr(sim), ops._ptr(hard_u8), ops._ptr(logits), ops._ptr(labels), ops._ptr(row), ops._ptr(loss),
-                                               ops._c64(B), ops._f(temperature), ops._stream(f)), "mdg_infonce_finish")
+        ops.call("mdg_infonce_finish", ops._ptr(sim), ops._ptr(hard_u8), ops._ptr(logits), ops._ptr(labels), ops._ptr(row), ops._ptr(loss), B,
+                 temperature, ops._stream(f))
         ctx.save_for_backward(f, sim, hard_u8)
         ctx.temperature, ctx.precision = temperature, precision
         ctx.mark_non_differentiable(logits, labels)

@@ -1,4 +1,5 @@
-"""Python wrappers of the C ABI: validate tensors, pass raw pointers + the current HIP stream.
+"""Python wrappers of the C ABI: validate tensors, pass their addresses, sizes and the current HIP stream as plain values
+(the header types every entry point, see _lib.py; ``call`` checks the returned status).
 
 torch is used for device memory and streams only; all arithmetic is in libmadrigal_hip.so.
 Every wrapper raises ``ValueError`` for bad shapes/dtypes/devices (the reference raises
@@ -12,15 +13,12 @@ from typing import Optional
 
 import torch
 
-from ._lib import check, lib
+from ._lib import call, lib
 
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16 = 0, 1, 2, 3
 PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3, "bf16": PREC_BF16}
 HEAD_PRECISIONS = dict(PRECISIONS, f16=PREC_F16)          # the all-pairs head also runs on the fp16 matrix cores
 EPI_STORE, EPI_STORE_SIGMOID, EPI_ROWSTATS, EPI_TRIKEYS = 0, 1, 2, 3
-
-_c64 = ctypes.c_int64
-_vp = ctypes.c_void_p
 
 
 def _prec(p) -> int:
@@ -39,12 +37,12 @@ def _stream_handle(device) -> int:
     return _raw_stream_of(torch.cuda.current_device() if idx is None else idx)
 
 
-def _stream(t: torch.Tensor) -> _vp:
-    return _vp(_stream_handle(t.device))
+def _stream(t: torch.Tensor) -> int:
+    return _stream_handle(t.device)
 
 
-def _ptr(t: Optional[torch.Tensor]) -> _vp:
-    return _vp(0 if t is None else t.data_ptr())
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
 
 
 def _f32_cuda(t: torch.Tensor, name: str, ndim: Optional[int] = None) -> torch.Tensor:
@@ -79,6 +77,12 @@ def _workspace(nbytes: int, device) -> Optional[torch.Tensor]:
     return buf
 
 
+def _scratch(query: str, device, *dims):
+    """(scratch buffer | None, its size in bytes) for the launch whose ``*_workspace_bytes`` query is ``query(*dims)``."""
+    nbytes = getattr(lib(), query)(*dims)
+    return _workspace(nbytes, device), nbytes
+
+
 # ------------------------------------------------------------------------------- head
 def symmetrize(w_original: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """triu(W) + triu(W,1)^T per outcome (madrigal/models/models.py:522-524)."""
@@ -88,7 +92,7 @@ def symmetrize(w_original: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
     out = torch.empty_like(w) if out is None else _f32_cuda(out, "out", 3)
     if out.shape != w.shape:
         raise ValueError("out: shape mismatch")
-    check(lib().mdg_symmetrize(_ptr(w), _ptr(out), _c64(w.shape[0]), _c64(w.shape[1]), _stream(w)), "mdg_symmetrize")
+    call("mdg_symmetrize", _ptr(w), _ptr(out), w.shape[0], w.shape[1], _stream(w))
     return out
 
 
@@ -121,18 +125,14 @@ def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
     if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
     prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    L_ = lib()
     # the grid's y extent caps one call at 65535 outcomes; chunk above that
     for lo in range(0, max(L, 1), 65535):
         hi = min(L, lo + 65535)
         if hi <= lo:
             break
-        nbytes = L_.mdg_bilinear_allpairs_workspace_bytes(_c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec)
-        ws = _workspace(nbytes, zh.device)
-        check(L_.mdg_bilinear_allpairs_ld(_ptr(zh), _ptr(zt), _vp(w.data_ptr() + lo * D * D * 4),
-                                          _vp(out.data_ptr() + lo * out.stride(0) * 4), _c64(ldo), _c64(Nh), _c64(Nt), _c64(hi - lo),
-                                          _c64(D), prec, int(epilogue), _ptr(ws), ctypes.c_size_t(nbytes), _stream(zh)),
-              "mdg_bilinear_allpairs")
+        ws, nbytes = _scratch("mdg_bilinear_allpairs_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
+        call("mdg_bilinear_allpairs_ld", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt,
+             hi - lo, D, prec, int(epilogue), _ptr(ws), nbytes, _stream(zh), what="mdg_bilinear_allpairs")
     return out
 
 
@@ -141,7 +141,7 @@ TOPK_ELIGIBLE = {"all": 0, "not_self": 1, "lower": 2}
 
 def bilinear_topk_max_k() -> int:
     """Largest ``k`` of ``bilinear_topk`` (at least 32)."""
-    return int(lib().mdg_bilinear_topk_max_k())
+    return lib().mdg_bilinear_topk_max_k()
 
 
 def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, k: int, *, eligible: str = "all",
@@ -166,8 +166,7 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
     prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    L_ = lib()
-    max_k = int(L_.mdg_bilinear_topk_max_k())
+    max_k = bilinear_topk_max_k()
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
         raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
     L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
@@ -191,12 +190,9 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     # the grid's y extent caps one call at 65535 outcomes; chunk above that
     for lo in range(0, L, 65535):
         hi = min(L, lo + 65535)
-        nbytes = L_.mdg_bilinear_topk_workspace_bytes(_c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec, int(k))
-        ws = _workspace(nbytes, zh.device)
-        check(L_.mdg_bilinear_topk(_ptr(zh), _ptr(zt), _vp(w.data_ptr() + lo * D * D * 4), _vp(vals.data_ptr() + lo * Nh * k * 4),
-                                   _vp(idx.data_ptr() + lo * Nh * k * 4), _c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec, int(k),
-                                   TOPK_ELIGIBLE[eligible], _ptr(ws), ctypes.c_size_t(nbytes), _stream(zh)),
-              "mdg_bilinear_topk")
+        ws, nbytes = _scratch("mdg_bilinear_topk_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec, int(k))
+        call("mdg_bilinear_topk", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, vals.data_ptr() + lo * Nh * k * 4,
+             idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, hi - lo, D, prec, int(k), TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
     return vals, idx
 
 
@@ -238,17 +234,14 @@ def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", o
         raise ValueError(f"out: expected a float32 GPU tensor {shape}, contiguous or row-pitched (empty_scores)")
     ldo = out.stride(1) if out.numel() else Nt
     prec = ENSEMBLE_PRECISIONS[precision]
-    L_ = lib()
     arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
     a_h, a_t = arr(zh), arr(zt)
     for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
         hi = min(L, lo + 65535)
-        nbytes = L_.mdg_bilinear_ensemble_sigmoid_workspace_bytes(_c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), ctypes.c_int(K), prec)
-        wsp = _workspace(nbytes, dev)
+        wsp, nbytes = _scratch("mdg_bilinear_ensemble_sigmoid_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
         a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
-        check(L_.mdg_bilinear_ensemble_sigmoid(a_h, a_t, a_w, ctypes.c_int(K), _vp(out.data_ptr() + lo * out.stride(0) * 4), _c64(ldo),
-                                               _c64(Nh), _c64(Nt), _c64(hi - lo), _c64(D), prec, _ptr(wsp), ctypes.c_size_t(nbytes),
-                                               _stream(zh[0])), "mdg_bilinear_ensemble_sigmoid")
+        call("mdg_bilinear_ensemble_sigmoid", a_h, a_t, a_w, K, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt, hi - lo, D, prec, _ptr(wsp),
+             nbytes, _stream(zh[0]))
     return out
 
 
@@ -264,8 +257,6 @@ def empty_scores(L: int, Nh: int, Nt: int, device) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------- dense blocks
 ACTS = {None: 0, "none": 0, "relu": 1, "gelu": 2, "sigmoid": 3, "tanh": 4, "leakyrelu": 5, "softplus": 6, "selu": 7}
-_c = ctypes.c_int
-_f = ctypes.c_float
 
 _pad_cache = {}
 
@@ -310,7 +301,7 @@ _pack_cache = {}
 def packed_weight_image(w: torch.Tensor, prec: int):
     """Operand image of a (padded) nn.Linear weight for mdg_linear, built once per (storage, version, precision)."""
     N, K = w.shape
-    nbytes = lib().mdg_pack_operand_bytes(_c64(N), _c64(K), _c(prec))
+    nbytes = lib().mdg_pack_operand_bytes(N, K, prec)
     if nbytes == 0:
         return None
     k = _wkey(w) + (prec,)
@@ -318,8 +309,7 @@ def packed_weight_image(w: torch.Tensor, prec: int):
     if hit is not None and hit[0] == w._version:
         return hit[1]
     img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    check(lib().mdg_pack_operand(_ptr(w), _c64(w.stride(0)), _c64(N), _c64(K), _c(prec), _ptr(img), ctypes.c_size_t(nbytes),
-                                 _stream(w)), "mdg_pack_operand")
+    call("mdg_pack_operand", _ptr(w), w.stride(0), N, K, prec, _ptr(img), nbytes, _stream(w))
     _pack_cache[k] = (w._version, img, w)
     return img
 
@@ -333,12 +323,11 @@ def pack_operand(x: torch.Tensor, precision="bf16x3") -> Optional[torch.Tensor]:
         x = _pad_last(x).contiguous()
         K = x.shape[1]
     prec = _prec(precision)
-    nbytes = int(lib().mdg_pack_operand_bytes(_c64(M), _c64(K), _c(prec)))
+    nbytes = lib().mdg_pack_operand_bytes(M, K, prec)
     if nbytes == 0:
         return None
     img = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    check(lib().mdg_pack_operand(_ptr(x), _c64(x.stride(0)), _c64(M), _c64(K), _c(prec), _ptr(img), ctypes.c_size_t(nbytes), _stream(x)),
-          "mdg_pack_operand")
+    call("mdg_pack_operand", _ptr(x), x.stride(0), M, K, prec, _ptr(img), nbytes, _stream(x))
     return img
 
 
@@ -412,21 +401,17 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     wimg = weight_image if weight_image is not None else (packed_weight_image(w, prec) if cache_weight else None)
     if w is None and (wimg is None or prec == PREC_F32):
         raise ValueError("linear: a PackedWeight needs its image and a 16-bit arithmetic mode")
-    nbytes = lib().mdg_linear_workspace_bytes(_c64(M), _c64(N), _c64(K), _c(prec), _c(1 if wimg is not None else 0))
-    ws = _workspace(nbytes, x2.device)
+    ws, nbytes = _scratch("mdg_linear_workspace_bytes", x2.device, M, N, K, prec, 1 if wimg is not None else 0)
     if dropout_p > 0.0:
         if scale is not None or shift is not None or alpha != 1.0 or not out.is_contiguous():
             raise ValueError("linear: the dropout epilogue takes no scale / shift / alpha and a contiguous result")
-        check(lib().mdg_linear_dropout(_ptr(x2), _c64(x2.stride(0)), _ptr(w), _c64(w_ld), _ptr(wimg), _ptr(out), _c64(out.stride(0)),
-                                       _c64(M), _c64(N), _c64(K), _ptr(None if bias is None else bias.detach().contiguous()), _c(ACTS[act]),
-                                       _ptr(residual), _c64(ldr), _f(beta), _f(dropout_p), ctypes.c_uint64(dropout_seed & (2 ** 64 - 1)), _c(prec),
-                                       _ptr(ws), ctypes.c_size_t(nbytes), _stream(x2)), "mdg_linear_dropout")
+        call("mdg_linear_dropout", _ptr(x2), x2.stride(0), _ptr(w), w_ld, _ptr(wimg), _ptr(out), out.stride(0), M, N, K,
+             _ptr(None if bias is None else bias.detach().contiguous()), ACTS[act], _ptr(residual), ldr, beta, dropout_p,
+             dropout_seed & (2 ** 64 - 1), prec, _ptr(ws), nbytes, _stream(x2))
         return out.view(*lead, N) if len(lead) != 1 or lead[0] != M else out
-    check(lib().mdg_linear(_ptr(x2), _c64(x2.stride(0)), _ptr(w), _c64(w_ld), _ptr(wimg), _ptr(out), _c64(out.stride(0)),
-                           _c64(M), _c64(N), _c64(K), _ptr(None if bias is None else bias.detach().contiguous()),
-                           _ptr(None if scale is None else scale.contiguous()), _ptr(None if shift is None else shift.contiguous()),
-                           _c(ACTS[act]), _ptr(residual), _c64(ldr), _f(alpha), _f(beta), _c(prec), _ptr(ws),
-                           ctypes.c_size_t(nbytes), _stream(x2)), "mdg_linear")
+    call("mdg_linear", _ptr(x2), x2.stride(0), _ptr(w), w_ld, _ptr(wimg), _ptr(out), out.stride(0), M, N, K,
+         _ptr(None if bias is None else bias.detach().contiguous()), _ptr(None if scale is None else scale.contiguous()),
+         _ptr(None if shift is None else shift.contiguous()), ACTS[act], _ptr(residual), ldr, alpha, beta, prec, _ptr(ws), nbytes, _stream(x2))
     return out.view(*lead, N) if len(lead) != 1 or lead[0] != M else out
 
 
@@ -470,11 +455,9 @@ def linear_chain(x: torch.Tensor, weights, biases, *, edge: Optional[torch.Tenso
         raise ValueError(f"out: expected fp32 cuda [{M},{N}] with unit inner stride")
     imgs = [packed_weight_image(w, prec) if prec != PREC_F32 else None for w in ws] + [None] * (3 - n)
     bs = [None if b is None else b.detach().contiguous() for b in biases] + [None] * (3 - n)
-    check(lib().mdg_linear_chain128(_ptr(x), _c64(x.stride(0)), _c64(K), _ptr(e_ptr), _c64(lde), _c64(k_e), _ptr(we_img), _c(n),
-                                    _ptr(imgs[0]), _ptr(imgs[1]), _ptr(imgs[2]), _ptr(bs[0]), _ptr(bs[1]), _ptr(bs[2]),
-                                    _ptr(None if scale is None else scale.contiguous()), _ptr(None if shift is None else shift.contiguous()),
-                                    _c(ACTS[act]), _ptr(out), _c64(out.stride(0)), _c64(M), _c64(N), _c(prec), _stream(x)),
-          "mdg_linear_chain128")
+    call("mdg_linear_chain128", _ptr(x), x.stride(0), K, _ptr(e_ptr), lde, k_e, _ptr(we_img), n, _ptr(imgs[0]), _ptr(imgs[1]), _ptr(imgs[2]),
+         _ptr(bs[0]), _ptr(bs[1]), _ptr(bs[2]), _ptr(None if scale is None else scale.contiguous()),
+         _ptr(None if shift is None else shift.contiguous()), ACTS[act], _ptr(out), out.stride(0), M, N, prec, _stream(x))
     return out
 
 
@@ -489,11 +472,10 @@ def layernorm_packed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     if prec == PREC_F32 or d % 64 or R == 0:
         return layernorm(x2, weight, bias, eps), None
     y = torch.empty((R, d), dtype=torch.float32, device=x2.device) if want_fp32 else None      # image only: y itself is never written
-    nbytes = int(lib().mdg_pack_operand_bytes(_c64(R), _c64(d), _c(prec)))
+    nbytes = lib().mdg_pack_operand_bytes(R, d, prec)
     img = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
-    check(lib().mdg_layernorm_packed(_ptr(x2), _c64(x2.stride(0)), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), _ptr(y),
-                                     _c64(d), _c64(R), _c64(d), _f(eps), _c(prec), _ptr(img), ctypes.c_size_t(nbytes), _stream(x2)),
-          "mdg_layernorm_packed")
+    call("mdg_layernorm_packed", _ptr(x2), x2.stride(0), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), _ptr(y), d, R, d, eps,
+         prec, _ptr(img), nbytes, _stream(x2))
     return y, img
 
 
@@ -513,13 +495,12 @@ def layernorm_logits(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     if prec == PREC_F32 or d % 64:
         y, img, nbytes = torch.empty((R, d), dtype=torch.float32, device=x2.device), None, 0
     else:
-        nbytes = int(lib().mdg_pack_operand_bytes(_c64(R), _c64(d), _c(prec)))
+        nbytes = lib().mdg_pack_operand_bytes(R, d, prec)
         y, img = None, torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
     if R == 0:
         return y, img, logits
-    check(lib().mdg_layernorm_logits(_ptr(x2), _c64(x2.stride(0)), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), _ptr(y),
-                                     _c64(d), _c64(R), _c64(d), _f(eps), _c(prec), _ptr(img), ctypes.c_size_t(nbytes), _ptr(G), _c(H),
-                                     _ptr(logits), _stream(x2)), "mdg_layernorm_logits")
+    call("mdg_layernorm_logits", _ptr(x2), x2.stride(0), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), _ptr(y), d, R, d, eps,
+         prec, _ptr(img), nbytes, _ptr(G), H, _ptr(logits), _stream(x2))
     return y, img, logits
 
 
@@ -550,11 +531,10 @@ def linear_packed(x_img: torch.Tensor, M: int, weight: torch.Tensor, bias: Optio
                 raise ValueError(f"residual: expected [{M},{N}] or [{N}]")
             ldr = residual.stride(0)
     wimg = weight_image if weight_image is not None else (packed_weight_image(w, prec) if cache_weight else None)
-    nbytes = lib().mdg_linear_packed_x_workspace_bytes(_c64(M), _c64(N), _c64(K), _c(prec), _c(1 if wimg is not None else 0))    # (+ the stream-K slots of the 256-tile kernel)
-    ws = _workspace(nbytes, x_img.device)
-    check(lib().mdg_linear_packed_x(_ptr(x_img), _c64(M), _c64(K), _ptr(w), _c64(w_ld), _ptr(wimg), _ptr(out), _c64(out.stride(0)), _c64(N),
-                                    _ptr(None if bias is None else bias.detach().contiguous()), _c(ACTS[act]), _ptr(residual), _c64(ldr),
-                                    _f(alpha), _f(beta), _c(prec), _ptr(ws), ctypes.c_size_t(nbytes), _stream(x_img)), "mdg_linear_packed_x")
+    ws, nbytes = _scratch("mdg_linear_packed_x_workspace_bytes", x_img.device, M, N, K, prec, 1 if wimg is not None else 0)    # (+ the stream-K slots of the 256-tile kernel)
+    call("mdg_linear_packed_x", _ptr(x_img), M, K, _ptr(w), w_ld, _ptr(wimg), _ptr(out), out.stride(0), N,
+         _ptr(None if bias is None else bias.detach().contiguous()), ACTS[act], _ptr(residual), ldr, alpha, beta, prec, _ptr(ws), nbytes,
+         _stream(x_img))
     return out
 
 
@@ -569,8 +549,8 @@ def layernorm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: fl
     R, d = x2.shape
     if out is None:
         out = torch.empty((R, d), dtype=torch.float32, device=x2.device)
-    check(lib().mdg_layernorm(_ptr(x2), _c64(x2.stride(0)), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()),
-                              _ptr(out), _c64(out.stride(0)), _c64(R), _c64(d), _f(eps), _stream(x2)), "mdg_layernorm")
+    call("mdg_layernorm", _ptr(x2), x2.stride(0), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), _ptr(out), out.stride(0), R,
+         d, eps, _stream(x2))
     return out.view(*lead, d) if lead is not None and out.is_contiguous() else out
 
 
@@ -580,7 +560,7 @@ def row_rstd(x: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     x2 = x if (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.is_cuda and x.dtype == torch.float32) else _rows2d(x, "x")[0]
     R, d = x2.shape
     out = torch.empty(R, dtype=torch.float32, device=x2.device)
-    check(lib().mdg_row_rstd(_ptr(x2), _c64(x2.stride(0)), _ptr(out), _c64(R), _c64(d), _f(eps), _stream(x2)), "mdg_row_rstd")
+    call("mdg_row_rstd", _ptr(x2), x2.stride(0), _ptr(out), R, d, eps, _stream(x2))
     return out
 
 
@@ -608,13 +588,10 @@ def linear_rowscaled(x: torch.Tensor, weight: torch.Tensor, row_scale: torch.Ten
         raise ValueError(f"out: expected fp32 cuda [{M},{N}] with unit inner stride")
     prec = _prec(precision)
     wimg = weight_image if weight_image is not None else packed_weight_image(w, prec)
-    nbytes = lib().mdg_linear_workspace_bytes(_c64(M), _c64(N), _c64(K), _c(prec), _c(1 if wimg is not None else 0))
-    ws = _workspace(nbytes, x2.device)
-    check(lib().mdg_linear_rowscaled(_ptr(x2), _c64(x2.stride(0)), _ptr(w), _c64(w.stride(0)), _ptr(wimg), _ptr(out), _c64(out.stride(0)),
-                                     _c64(M), _c64(N), _c64(K), _ptr(row_scale.contiguous()),
-                                     _ptr(None if bias_pre is None else bias_pre.detach().contiguous()),
-                                     _ptr(None if bias is None else bias.detach().contiguous()), _c(prec), _ptr(ws), ctypes.c_size_t(nbytes),
-                                     _stream(x2)), "mdg_linear_rowscaled")
+    ws, nbytes = _scratch("mdg_linear_workspace_bytes", x2.device, M, N, K, prec, 1 if wimg is not None else 0)
+    call("mdg_linear_rowscaled", _ptr(x2), x2.stride(0), _ptr(w), w.stride(0), _ptr(wimg), _ptr(out), out.stride(0), M, N, K,
+         _ptr(row_scale.contiguous()), _ptr(None if bias_pre is None else bias_pre.detach().contiguous()),
+         _ptr(None if bias is None else bias.detach().contiguous()), prec, _ptr(ws), nbytes, _stream(x2))
     return out.view(*lead, N) if len(lead) != 1 or lead[0] != M else out
 
 
@@ -649,13 +626,10 @@ def assemble_tokens(str_emb, kg_emb, cv_emb, tx_emb, *, bottleneck=None, cls=Non
             raise ValueError("token_index: int64 cuda tensor")
         n_tok = int(token_index.numel())
         seq = torch.empty((n_tok, s.shape[1]), dtype=torch.float32, device=s.device)
-    check(lib().mdg_assemble_tokens(_ptr(s), _ptr(k), _ptr(c), _ptr(t),
-                                    _ptr(None if bottleneck is None else bottleneck.detach().contiguous()),
-                                    _ptr(None if cls is None else cls.detach().contiguous()), _ptr(pe2),
-                                    _ptr(None if rows is None else rows.contiguous()),
-                                    _ptr(None if token_index is None else token_index.contiguous()), _c64(n_tok), _ptr(seq), _c64(n),
-                                    _c64(n_src), _c(nb), _c(0 if cls is None else 1), _c(0 if pe2 is None else pe2.shape[0]),
-                                    _c(1 if normalize else 0), _c64(s.shape[1]), _stream(s)), "mdg_assemble_tokens")
+    call("mdg_assemble_tokens", _ptr(s), _ptr(k), _ptr(c), _ptr(t), _ptr(None if bottleneck is None else bottleneck.detach().contiguous()),
+         _ptr(None if cls is None else cls.detach().contiguous()), _ptr(pe2), _ptr(None if rows is None else rows.contiguous()),
+         _ptr(None if token_index is None else token_index.contiguous()), n_tok, _ptr(seq), n, n_src, nb, 0 if cls is None else 1,
+         0 if pe2 is None else pe2.shape[0], 1 if normalize else 0, s.shape[1], _stream(s))
     return seq
 
 
@@ -673,9 +647,8 @@ def fusion_attention(qkv: torch.Tensor, n: int, S: int, H: int, dh: int, kpm_bit
         raise ValueError("row_start: int64 [n+1]; attention weights need the dense layout")
     out = torch.empty((rows, d), dtype=torch.float32, device=qkv.device)
     probs = torch.empty((n, H, S, S), dtype=torch.float32, device=qkv.device) if want_probs else None
-    check(lib().mdg_fusion_attention_dropout(_ptr(qkv), _c64(qkv.stride(0)), _ptr(out), _c64(d), _ptr(kpm_bits), _ptr(src_bits),
-                                             _ptr(probs), _ptr(row_start), _ptr(row_bits), _c64(n), _c(S), _c(H), _c(dh), _f(p_drop),
-                                             ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(qkv)), "mdg_fusion_attention")
+    call("mdg_fusion_attention_dropout", _ptr(qkv), qkv.stride(0), _ptr(out), d, _ptr(kpm_bits), _ptr(src_bits), _ptr(probs), _ptr(row_start),
+         _ptr(row_bits), n, S, H, dh, p_drop, seed & (2 ** 64 - 1), _stream(qkv), what="mdg_fusion_attention")
     return out, probs
 
 
@@ -703,10 +676,8 @@ def fusion_attention_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: i
         out = torch.empty((rows, (H - 1) * ho + dv), dtype=torch.float32, device=q.device)
     elif ho is None or out.shape[1] < (H - 1) * ho + dv:
         raise ValueError("out: give its head step ho, and columns for H heads of it")
-    check(lib().mdg_fusion_attention_qkv(_ptr(q), _c64(q.stride(0)), _c(hq), _ptr(k), _c64(k.stride(0)), _c(hk), _ptr(v), _c64(v.stride(0)),
-                                         _c(hv), _ptr(out), _c64(out.stride(0)), _c(ho), _ptr(kpm_bits), _ptr(src_bits), _ptr(row_start),
-                                         _ptr(row_bits), _c64(n), _c(S), _c(H), _c(ds), _c(dv), _f(qscale), _stream(q)),
-          "mdg_fusion_attention_qkv")
+    call("mdg_fusion_attention_qkv", _ptr(q), q.stride(0), hq, _ptr(k), k.stride(0), hk, _ptr(v), v.stride(0), hv, _ptr(out), out.stride(0), ho,
+         _ptr(kpm_bits), _ptr(src_bits), _ptr(row_start), _ptr(row_bits), n, S, H, ds, dv, qscale, _stream(q))
     return out
 
 
@@ -726,8 +697,8 @@ def token_scaled_rows(tokens: torch.Tensor, rf: torch.Tensor, d: int, eps: float
         raise ValueError(f"tail: expected an fp32 cuda [{R},{D}] view with unit inner stride")
     X = torch.empty((R, Dp), dtype=torch.float32, device=t.device)
     r = torch.empty(R, dtype=torch.float32, device=t.device)
-    check(lib().mdg_token_scaled_rows(_ptr(t), _c64(t.stride(0)), _ptr(rf), _c(rf.shape[0]), _c64(D), _c64(d), _f(eps), _ptr(X), _c64(Dp),
-                                      _ptr(tail), _c64(tail.stride(0)), _ptr(r), _c64(R), _stream(t)), "mdg_token_scaled_rows")
+    call("mdg_token_scaled_rows", _ptr(t), t.stride(0), _ptr(rf), rf.shape[0], D, d, eps, _ptr(X), Dp, _ptr(tail), tail.stride(0), _ptr(r), R,
+         _stream(t))
     return X, r
 
 
@@ -740,9 +711,8 @@ def fusion_attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, n: int, S: int, 
         raise ValueError("fusion_attention_bwd: shape mismatch")
     # rows outside every tile (none in practice) would stay unwritten: start from zeros only in that case
     dqkv = torch.empty_like(qkv)
-    check(lib().mdg_fusion_attention_bwd(_ptr(qkv), _c64(qkv.stride(0)), _ptr(dout), _c64(d), _ptr(dqkv), _c64(3 * d), _ptr(kpm_bits),
-                                         _ptr(src_bits), _ptr(row_start), _ptr(row_bits), _c64(n), _c(S), _c(H), _c(dh), _f(p_drop),
-                                         ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(qkv)), "mdg_fusion_attention_bwd")
+    call("mdg_fusion_attention_bwd", _ptr(qkv), qkv.stride(0), _ptr(dout), d, _ptr(dqkv), 3 * d, _ptr(kpm_bits), _ptr(src_bits), _ptr(row_start),
+         _ptr(row_bits), n, S, H, dh, p_drop, seed & (2 ** 64 - 1), _stream(qkv))
     return dqkv
 
 
@@ -754,8 +724,8 @@ def xattn_pool(q_proj: torch.Tensor, kv_proj: torch.Tensor, n: int, Tk: int, H: 
     if q.numel() != d or kv.shape != (n * Tk, 2 * d):
         raise ValueError(f"xattn_pool: expected q [{d}] and kv [{n * Tk},{2 * d}]")
     out = torch.empty((n, d), dtype=torch.float32, device=kv.device)
-    check(lib().mdg_xattn_pool_dropout(_ptr(q), _ptr(kv), _c64(kv.stride(0)), _ptr(out), _c64(d), _c64(n), _c(Tk), _c(H), _c(dh),
-                                       _f(p_drop), ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(kv)), "mdg_xattn_pool")
+    call("mdg_xattn_pool_dropout", _ptr(q), _ptr(kv), kv.stride(0), _ptr(out), d, n, Tk, H, dh, p_drop, seed & (2 ** 64 - 1), _stream(kv),
+         what="mdg_xattn_pool")
     return out
 
 
@@ -772,8 +742,7 @@ def xattn_fold_pool(P: torch.Tensor, logits: torch.Tensor, c_z: torch.Tensor, n:
     if P.stride(0) % 2 or P.data_ptr() % 8:
         P = P.contiguous()
     z = torch.empty((n, D), dtype=torch.float32, device=P.device)
-    check(lib().mdg_xattn_fold_pool(_ptr(P), _c64(P.stride(0)), _ptr(logits), _c64(logits.stride(0)), _ptr(c_z), _ptr(z), _c64(D), _c64(n), _c(Tk),
-                                    _c(H), _c(D), _stream(P)), "mdg_xattn_fold_pool")
+    call("mdg_xattn_fold_pool", _ptr(P), P.stride(0), _ptr(logits), logits.stride(0), _ptr(c_z), _ptr(z), D, n, Tk, H, D, _stream(P))
     return z
 
 
@@ -787,9 +756,8 @@ def xattn_pool_bwd(q_proj: torch.Tensor, kv_proj: torch.Tensor, dout: torch.Tens
         raise ValueError("xattn_pool_bwd: shape mismatch")
     dkv = torch.empty_like(kv)
     dq_part = torch.empty((n, d), dtype=torch.float32, device=kv.device)
-    check(lib().mdg_xattn_pool_bwd(_ptr(q), _ptr(kv), _c64(kv.stride(0)), _ptr(dout), _c64(d), _ptr(dkv), _c64(2 * d), _ptr(dq_part),
-                                   _c64(n), _c(Tk), _c(H), _c(dh), _f(p_drop), ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(kv)),
-          "mdg_xattn_pool_bwd")
+    call("mdg_xattn_pool_bwd", _ptr(q), _ptr(kv), kv.stride(0), _ptr(dout), d, _ptr(dkv), 2 * d, _ptr(dq_part), n, Tk, H, dh, p_drop,
+         seed & (2 ** 64 - 1), _stream(kv))
     return colsum(dq_part), dkv
 
 
@@ -803,7 +771,7 @@ def group_tile_table(groups, device) -> torch.Tensor:
     ``device``.  ``groups``: dicts with m_base, rows (the group's rows in the stacked x), n_base, n (its rows in the stacked W),
     y_off, ldy (float offset of its output block in y and that block's row stride) and optionally res_off, ldr, alpha, beta."""
     import struct
-    words = int(lib().mdg_linear_group_tile_words())
+    words = lib().mdg_linear_group_tile_words()
     rows = []
     for g in groups:
         for v in (g["n_base"], g["y_off"], g["ldy"], g.get("res_off", 0) or 0, g.get("ldr", 0)):
@@ -836,12 +804,10 @@ def linear_grouped(x: torch.Tensor, w_all: torch.Tensor, bias_all: Optional[torc
     prec = _prec(precision)
     K = x.shape[1]
     wimg = packed_weight_image(w_all, prec)
-    nbytes = lib().mdg_linear_grouped_workspace_bytes(_c64(x.shape[0]), _c64(K), _c(prec))
-    ws = _workspace(nbytes, x.device)
-    check(lib().mdg_linear_grouped(_ptr(x), _c64(x.stride(0)), _c64(x.shape[0]), _c64(K), _ptr(w_all), _c64(w_all.stride(0)), _ptr(wimg),
-                                   _c64(w_all.shape[0]), _ptr(None if bias_all is None else bias_all.detach().contiguous()), _ptr(tiles),
-                                   _c64(tiles.shape[0]), _ptr(y), _ptr(residual), _c(ACTS[act]), _c(prec), _ptr(ws), ctypes.c_size_t(nbytes),
-                                   _stream(x)), "mdg_linear_grouped")
+    ws, nbytes = _scratch("mdg_linear_grouped_workspace_bytes", x.device, x.shape[0], K, prec)
+    call("mdg_linear_grouped", _ptr(x), x.stride(0), x.shape[0], K, _ptr(w_all), w_all.stride(0), _ptr(wimg), w_all.shape[0],
+         _ptr(None if bias_all is None else bias_all.detach().contiguous()), _ptr(tiles), tiles.shape[0], _ptr(y), _ptr(residual), ACTS[act], prec,
+         _ptr(ws), nbytes, _stream(x))
     return y
 
 
@@ -866,10 +832,9 @@ def csr_aggregate(x: torch.Tensor, rowptr: torch.Tensor, col: Optional[torch.Ten
         if x_self.shape != (n_dst, F):
             raise ValueError("x_self: shape mismatch")
     out = torch.empty((n_dst, F), dtype=torch.float32, device=x.device)
-    check(lib().mdg_csr_aggregate(_ptr(x), _c64(x.stride(0)), _ptr(rowptr.contiguous()), _ptr(None if col is None else col.contiguous()),
-                                  _ptr(None if edge_weight is None else edge_weight.contiguous()), _ptr(x_self),
-                                  _c64(0 if x_self is None else x_self.stride(0)), _ptr(self_coef_dev), _f(self_coef_add),
-                                  _c(1 if mean else 0), _ptr(out), _c64(F), _c64(n_dst), _c64(F), _stream(x)), "mdg_csr_aggregate")
+    call("mdg_csr_aggregate", _ptr(x), x.stride(0), _ptr(rowptr.contiguous()), _ptr(None if col is None else col.contiguous()),
+         _ptr(None if edge_weight is None else edge_weight.contiguous()), _ptr(x_self), 0 if x_self is None else x_self.stride(0),
+         _ptr(self_coef_dev), self_coef_add, 1 if mean else 0, _ptr(out), F, n_dst, F, _stream(x))
     return out
 
 
@@ -886,12 +851,10 @@ def hgt_attention(q: torch.Tensor, kv: torch.Tensor, plan: dict, heads: int, app
     elif tuple(out.shape) != (n_dst, 128) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != q.device:
         raise ValueError("out: expected contiguous fp32 [n_dst,128] on q's device")
     n_items = int(plan["item_dst"].numel())
-    nbytes = lib().mdg_hgt_attention_workspace_bytes(_c64(n_items), _c(heads))
-    ws = _workspace(nbytes, q.device)
-    check(lib().mdg_hgt_attention(_ptr(q), _c64(q.stride(0)), _ptr(kv), _c64(0 if kv is None else kv.stride(0)), _ptr(plan["col"]),
-                                  _ptr(plan["item_dst"]), _ptr(plan["item_begin"]), _ptr(plan["item_end"]), _c64(n_items),
-                                  _ptr(plan["item_ptr"]), _ptr(out), _c64(128), _c64(n_dst), _c(heads), _c64(128),
-                                  _c(1 if apply_gelu else 0), _ptr(ws), ctypes.c_size_t(nbytes), _stream(q)), "mdg_hgt_attention")
+    ws, nbytes = _scratch("mdg_hgt_attention_workspace_bytes", q.device, n_items, heads)
+    call("mdg_hgt_attention", _ptr(q), q.stride(0), _ptr(kv), 0 if kv is None else kv.stride(0), _ptr(plan["col"]), _ptr(plan["item_dst"]),
+         _ptr(plan["item_begin"]), _ptr(plan["item_end"]), n_items, _ptr(plan["item_ptr"]), _ptr(out), 128, n_dst, heads, 128, 1 if apply_gelu else 0,
+         _ptr(ws), nbytes, _stream(q))
     return out
 
 
@@ -903,13 +866,11 @@ def hgt_attention_rows(buf: torch.Tensor, plan_all: dict, heads: int, out: torch
     if tuple(out.shape) != (n_dst, 128) or not out.is_contiguous() or out.dtype != torch.float32 or not buf.is_contiguous():
         raise ValueError("hgt_attention_rows: out must be contiguous fp32 [n_dst,128], buf contiguous")
     n_items = int(plan_all["item_dst"].numel())
-    nbytes = lib().mdg_hgt_attention_workspace_bytes(_c64(n_items), _c(heads))
-    ws = _workspace(nbytes, buf.device)
+    ws, nbytes = _scratch("mdg_hgt_attention_workspace_bytes", buf.device, n_items, heads)
     kv = buf.view(-1, 128)
-    check(lib().mdg_hgt_attention_rows(_ptr(buf), _ptr(plan_all["q_off"]), _ptr(kv), _c64(128), _ptr(plan_all["col"]), _ptr(plan_all["item_dst"]),
-                                       _ptr(plan_all["item_begin"]), _ptr(plan_all["item_end"]), _c64(n_items), _ptr(plan_all["item_ptr"]),
-                                       _ptr(out), _c64(128), _c64(n_dst), _c(heads), _c(1 if apply_gelu else 0), _ptr(ws),
-                                       ctypes.c_size_t(nbytes), _stream(buf)), "mdg_hgt_attention_rows")
+    call("mdg_hgt_attention_rows", _ptr(buf), _ptr(plan_all["q_off"]), _ptr(kv), 128, _ptr(plan_all["col"]), _ptr(plan_all["item_dst"]),
+         _ptr(plan_all["item_begin"]), _ptr(plan_all["item_end"]), n_items, _ptr(plan_all["item_ptr"]), _ptr(out), 128, n_dst, heads,
+         1 if apply_gelu else 0, _ptr(ws), nbytes, _stream(buf))
     return out
 
 
@@ -920,8 +881,7 @@ def l2_normalize(x: torch.Tensor) -> torch.Tensor:
     if x2.shape[1] % 4:
         raise ValueError("l2_normalize: last dim must be a multiple of 4")
     y = torch.empty_like(x2)
-    check(lib().mdg_l2_normalize(_ptr(x2), _c64(x2.stride(0)), _ptr(y), _c64(y.stride(0)), _c64(x2.shape[0]), _c64(x2.shape[1]),
-                                 _stream(x2)), "mdg_l2_normalize")
+    call("mdg_l2_normalize", _ptr(x2), x2.stride(0), _ptr(y), y.stride(0), x2.shape[0], x2.shape[1], _stream(x2))
     return y.view(*lead, x2.shape[1])
 
 
@@ -931,8 +891,7 @@ def token_pool(tokens: torch.Tensor, bits: Optional[torch.Tensor], mode: str) ->
     t = _f32_cuda(tokens, "tokens", 3)
     n, S, D = t.shape
     out = torch.empty((n, D), dtype=torch.float32, device=t.device)
-    check(lib().mdg_token_pool(_ptr(t), _ptr(bits), _ptr(out), _c64(n), _c(S), _c64(D), _c({"mean": 0, "sum": 1, "max": 2}[mode]),
-                               _stream(t)), "mdg_token_pool")
+    call("mdg_token_pool", _ptr(t), _ptr(bits), _ptr(out), n, S, D, {"mean": 0, "sum": 1, "max": 2}[mode], _stream(t))
     return out
 
 
@@ -956,8 +915,7 @@ def info_nce(aug1: torch.Tensor, aug2: torch.Tensor, too_hard_neg: Optional[torc
     labels = torch.empty_like(logits) if want_logits else None
     row = torch.empty(2 * B, dtype=torch.float32, device=a1.device)
     loss = torch.empty(1, dtype=torch.float32, device=a1.device)
-    check(lib().mdg_infonce_finish(_ptr(sim), _ptr(hard), _ptr(logits), _ptr(labels), _ptr(row), _ptr(loss), _c64(B),
-                                   _f(temperature), _stream(a1)), "mdg_infonce_finish")
+    call("mdg_infonce_finish", _ptr(sim), _ptr(hard), _ptr(logits), _ptr(labels), _ptr(row), _ptr(loss), B, temperature, _stream(a1))
     return logits, labels, loss[0]
 
 
@@ -983,9 +941,8 @@ def gather_bce(scores: torch.Tensor, labels: torch.Tensor, heads: torch.Tensor, 
         target = _f32_cuda(target, "target", 1)
         term = torch.empty(n, dtype=torch.float32, device=s.device)
         loss = torch.zeros(1, dtype=torch.float32, device=s.device)
-    check(lib().mdg_gather_bce(_ptr(s), _c64(s.shape[0]), _c64(s.shape[1]), _c64(s.shape[2]), _ptr(labels.contiguous()),
-                               _ptr(heads.contiguous()), _ptr(tails.contiguous()), _ptr(target), _ptr(pred), _ptr(term), _ptr(loss),
-                               _c64(n), _c(1 if apply_sigmoid else 0), _stream(s)), "mdg_gather_bce")
+    call("mdg_gather_bce", _ptr(s), s.shape[0], s.shape[1], s.shape[2], _ptr(labels.contiguous()), _ptr(heads.contiguous()), _ptr(tails.contiguous()),
+         _ptr(target), _ptr(pred), _ptr(term), _ptr(loss), n, 1 if apply_sigmoid else 0, _stream(s))
     return pred, (None if loss is None else loss[0])
 
 
@@ -1032,19 +989,17 @@ def rank_normalize(scores: torch.Tensor, out: Optional[torch.Tensor] = None, max
             raise ValueError("out: an fp32 GPU tensor of the shape of scores (contiguous or row-pitched), not aliasing it")
     if L == 0 or N == 0:
         return out
-    lb = lib()
-    entry = lb.mdg_rank_normalize_keys_ld if from_keys else lb.mdg_rank_normalize_ld
-    per = max(lb.mdg_rank_normalize_workspace_bytes(_c64(1), _c64(N)), 1)
+    entry = "mdg_rank_normalize_keys_ld" if from_keys else "mdg_rank_normalize_ld"
+    per = max(lib().mdg_rank_normalize_workspace_bytes(1, N), 1)
     chunk = int(max(1, min(L, 65535, max_workspace_bytes // per)))
     if chunk > 8:
         chunk -= chunk % 8                   # whole launch groups of the MSD path (8 outcomes each): no ragged group at the end of every chunk
     for lo in range(0, L, chunk):
         hi = min(L, lo + chunk)
-        nbytes = lb.mdg_rank_normalize_workspace_bytes(_c64(hi - lo), _c64(N))
-        ws = _workspace(nbytes, s.device)
-        check(entry(_vp(s.data_ptr() + lo * s.stride(0) * 4), _c64(s.stride(1)), _vp(out.data_ptr() + lo * out.stride(0) * 4),
-                    _c64(out.stride(1)), _c64(hi - lo), _c64(N), _ptr(ws), ctypes.c_size_t(nbytes), _stream(s)), "mdg_rank_normalize")
-        if fallback_flags is not None and lb.mdg_rank_normalize_fast_path(_c64(hi - lo), _c64(N)):
+        ws, nbytes = _scratch("mdg_rank_normalize_workspace_bytes", s.device, hi - lo, N)
+        call(entry, s.data_ptr() + lo * s.stride(0) * 4, s.stride(1), out.data_ptr() + lo * out.stride(0) * 4, out.stride(1), hi - lo, N, _ptr(ws),
+             nbytes, _stream(s), what="mdg_rank_normalize")
+        if fallback_flags is not None and lib().mdg_rank_normalize_fast_path(hi - lo, N):
             fallback_flags.append(ws[: 4 * (hi - lo)].view(torch.int32).clone())
     return out
 
@@ -1052,19 +1007,19 @@ def rank_normalize(scores: torch.Tensor, out: Optional[torch.Tensor] = None, max
 def _hgt_composite_args(ptrs, k_rel, v_rel, meta):
     nt, R = meta["n_types"], meta["n_edge_types"]
     base = ptrs.data_ptr()
-    return (_vp(base), _vp(base + 8 * nt), _ptr(k_rel), _ptr(v_rel), _vp(base + 16 * nt), _ptr(meta["rel_r"]), _ptr(meta["rel_src"]), _ptr(meta["rel_row"]),
-            _c(meta["n_rel"]), _ptr(meta["type_row"]), _c(nt))
+    return (base, base + 8 * nt, _ptr(k_rel), _ptr(v_rel), base + 16 * nt, _ptr(meta["rel_r"]), _ptr(meta["rel_src"]), _ptr(meta["rel_row"]),
+            meta["n_rel"], _ptr(meta["type_row"]), nt)
 
 
 def hgt_composite(ptrs: torch.Tensor, k_rel, v_rel, meta: dict, big_w, big_b) -> None:
     """mdg_hgt_composite_fwd (autograd._HgtComposite): ``ptrs`` = device int64 table [kqv weights | kqv biases | p_rel of every edge type]."""
-    check(lib().mdg_hgt_composite_fwd(*_hgt_composite_args(ptrs, k_rel, v_rel, meta), _ptr(big_w), _ptr(big_b), _c(meta["cin"]), _c(meta["H"]),
-                                      _c(meta["n_edge_types"]), _c(meta["F"]), _stream(big_w)), "mdg_hgt_composite_fwd")
+    call("mdg_hgt_composite_fwd", *_hgt_composite_args(ptrs, k_rel, v_rel, meta), _ptr(big_w), _ptr(big_b), meta["cin"], meta["H"],
+         meta["n_edge_types"], meta["F"], _stream(big_w))
 
 
 def hgt_composite_bwd(ptrs: torch.Tensor, k_rel, v_rel, meta: dict, dbig_w, dbig_b, grads) -> None:
-    check(lib().mdg_hgt_composite_bwd(*_hgt_composite_args(ptrs, k_rel, v_rel, meta), _ptr(dbig_w), _ptr(dbig_b), _ptr(grads), _c(meta["cin"]), _c(meta["H"]),
-                                      _c(meta["n_edge_types"]), _c(meta["F"]), _stream(grads)), "mdg_hgt_composite_bwd")
+    call("mdg_hgt_composite_bwd", *_hgt_composite_args(ptrs, k_rel, v_rel, meta), _ptr(dbig_w), _ptr(dbig_b), _ptr(grads), meta["cin"], meta["H"],
+         meta["n_edge_types"], meta["F"], _stream(grads))
 
 
 def gmean(tensors) -> torch.Tensor:
@@ -1083,12 +1038,12 @@ def gmean(tensors) -> torch.Tensor:
         full = [t.as_strided((L, N, P), (N * P, P, 1)) for t in ts]          # the padded storage itself: contiguous, n % 4 == 0
         out_full = torch.empty((L, N, P), dtype=torch.float32, device=t0.device)
         arr = (ctypes.c_void_p * len(full))(*[t.data_ptr() for t in full])
-        check(lib().mdg_gmean(arr, _c(len(full)), _ptr(out_full), _c64(L * N * P), _stream(out_full)), "mdg_gmean")
+        call("mdg_gmean", arr, len(full), _ptr(out_full), L * N * P, _stream(out_full))
         return out_full[:, :, :t0.shape[2]]
     ts = [_f32_cuda(t, f"tensors[{i}]") for i, t in enumerate(ts)]
     out = torch.empty_like(ts[0])
     arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    check(lib().mdg_gmean(arr, _c(len(ts)), _ptr(out), _c64(ts[0].numel()), _stream(out)), "mdg_gmean")
+    call("mdg_gmean", arr, len(ts), _ptr(out), ts[0].numel(), _stream(out))
     return out
 
 
@@ -1111,7 +1066,7 @@ def transpose(x: torch.Tensor, pad_inner: bool = True) -> torch.Tensor:
     R, C = x.shape
     Rp = _ceil4(R) if pad_inner else R
     out = (torch.zeros if Rp != R else torch.empty)((C, Rp), dtype=torch.float32, device=x.device)
-    check(lib().mdg_transpose(_ptr(x), _c64(x.stride(0)), _ptr(out), _c64(Rp), _c64(R), _c64(C), _stream(x)), "mdg_transpose")
+    call("mdg_transpose", _ptr(x), x.stride(0), _ptr(out), Rp, R, C, _stream(x))
     return out
 
 
@@ -1152,14 +1107,12 @@ def parameter_images(w: torch.Tensor, precision):
     if hit is not None and hit[0] == w._version:
         return hit[1], hit[2]
     N, K = w.shape
-    L_ = lib()
-    rb = int(L_.mdg_linear_backward_pack_bytes(_c64(N), _c64(K), _c(prec), _c(0)))
-    tb = int(L_.mdg_linear_backward_pack_bytes(_c64(N), _c64(K), _c(prec), _c(1)))
+    rb = lib().mdg_linear_backward_pack_bytes(N, K, prec, 0)
+    tb = lib().mdg_linear_backward_pack_bytes(N, K, prec, 1)
     img = torch.empty(rb, dtype=torch.uint8, device=w.device)
     timg = torch.empty(tb, dtype=torch.uint8, device=w.device)
     wd = w.detach()
-    check(L_.mdg_linear_backward_pack(_ptr(wd), _c64(K), _c64(N), _c64(K), _c(prec), _ptr(img), _ptr(timg), _ptr(None), _f(0.0), ctypes.c_uint64(0),
-                                      _ptr(None), ctypes.c_size_t(0), _stream(wd)), "mdg_linear_backward_pack")
+    call("mdg_linear_backward_pack", _ptr(wd), K, N, K, prec, _ptr(img), _ptr(timg), None, 0.0, 0, None, 0, _stream(wd))
     wt = PackedWeight((K, _ceil4(N)), timg)
     _param_img_cache[k] = (w._version, img, wt, w)
     return img, wt
@@ -1182,21 +1135,19 @@ def transposed_weight_image(w: torch.Tensor, precision):
     if prec != PREC_F32 and w.is_contiguous():
         # 16-bit modes: W^T is only ever read as an operand image: one transposing pack of W, no fp32 transpose
         N, K = w.shape
-        nbytes = int(lib().mdg_pack_operand_bytes(_c64(K), _c64(_ceil4(N)), _c(prec)))
+        nbytes = lib().mdg_pack_operand_bytes(K, _ceil4(N), prec)
         img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
         wd = w.detach()
-        check(lib().mdg_pack_operand_transposed(_ptr(wd), _c64(wd.stride(0)), _c64(N), _c64(K), _c(prec), _ptr(img), ctypes.c_size_t(nbytes), _stream(wd)),
-              "mdg_pack_operand_transposed")
+        call("mdg_pack_operand_transposed", _ptr(wd), wd.stride(0), N, K, prec, _ptr(img), nbytes, _stream(wd))
         wt = PackedWeight((K, _ceil4(N)), img)
         _wt_img_cache[k] = (w._version, wt, img, w)
         return wt, img
     wt = weight_transposed(w)
-    nbytes = int(lib().mdg_pack_operand_bytes(_c64(wt.shape[0]), _c64(wt.shape[1]), _c(prec)))
+    nbytes = lib().mdg_pack_operand_bytes(wt.shape[0], wt.shape[1], prec)
     img = None
     if nbytes:
         img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-        check(lib().mdg_pack_operand(_ptr(wt), _c64(wt.stride(0)), _c64(wt.shape[0]), _c64(wt.shape[1]), _c(prec), _ptr(img), ctypes.c_size_t(nbytes),
-                                     _stream(wt)), "mdg_pack_operand")
+        call("mdg_pack_operand", _ptr(wt), wt.stride(0), wt.shape[0], wt.shape[1], prec, _ptr(img), nbytes, _stream(wt))
     _wt_img_cache[k] = (w._version, wt, img, w)
     return wt, img
 
@@ -1215,21 +1166,19 @@ def linear_backward_pack(g: torch.Tensor, precision, want_bias: bool = False, wa
         raise ValueError("linear_backward_pack: g must be a 2-D fp32 cuda tensor with unit inner stride")
     prec = _prec(precision)
     M, N = g.shape
-    L_ = lib()
-    rb = int(L_.mdg_linear_backward_pack_bytes(_c64(M), _c64(N), _c(prec), _c(0)))
-    tb = int(L_.mdg_linear_backward_pack_bytes(_c64(M), _c64(N), _c(prec), _c(1)))
+    rb = lib().mdg_linear_backward_pack_bytes(M, N, prec, 0)
+    tb = lib().mdg_linear_backward_pack_bytes(M, N, prec, 1)
     if tb == 0:
         raise ValueError("linear_backward_pack: a 16-bit operand mode (bf16 / bf16x3) and a non-empty g")
     row_img = torch.empty(rb, dtype=torch.uint8, device=g.device) if want_row_image else None
     t_img = torch.empty(tb, dtype=torch.uint8, device=g.device)
     db = torch.empty(N, dtype=torch.float32, device=g.device) if want_bias else None
-    nbytes = int(L_.mdg_linear_backward_pack_bytes(_c64(M), _c64(N), _c(prec), _c(2))) if want_bias else 0
+    nbytes = lib().mdg_linear_backward_pack_bytes(M, N, prec, 2) if want_bias else 0
     ws = _workspace(nbytes, g.device)
     if dropout_p > 0.0 and g.stride(0) != N:
         raise ValueError("linear_backward_pack: the dropout mask is indexed by the contiguous [M,N] position")
-    check(L_.mdg_linear_backward_pack(_ptr(g), _c64(g.stride(0)), _c64(M), _c64(N), _c(prec), _ptr(row_img), _ptr(t_img), _ptr(db), _f(dropout_p),
-                                      ctypes.c_uint64(dropout_seed & (2 ** 64 - 1)), _ptr(ws), ctypes.c_size_t(nbytes), _stream(g)),
-          "mdg_linear_backward_pack")
+    call("mdg_linear_backward_pack", _ptr(g), g.stride(0), M, N, prec, _ptr(row_img), _ptr(t_img), _ptr(db), dropout_p, dropout_seed & (2 ** 64 - 1),
+         _ptr(ws), nbytes, _stream(g))
     return row_img, t_img, db
 
 
@@ -1242,10 +1191,8 @@ def linear_tn_packed_g(gt_img: torch.Tensor, x: torch.Tensor, N: int, precision,
     dw = torch.empty((N, K), dtype=torch.float32, device=x.device) if out is None else out
     if tuple(dw.shape) != (N, K) or not dw.is_contiguous() or dw.dtype != torch.float32:
         raise ValueError("linear_tn_packed_g: out must be contiguous fp32 [N,K]")
-    nbytes = lib().mdg_linear_tn_packed_g_workspace_bytes(_c64(M), _c64(N), _c64(K), _c(prec))
-    ws = _workspace(nbytes, x.device)
-    check(lib().mdg_linear_tn_packed_g(_ptr(gt_img), _ptr(x), _c64(x.stride(0)), _ptr(dw), _c64(K), _c64(M), _c64(N), _c64(K), _c(prec), _ptr(ws),
-                                       ctypes.c_size_t(nbytes), _stream(x)), "mdg_linear_tn_packed_g")
+    ws, nbytes = _scratch("mdg_linear_tn_packed_g_workspace_bytes", x.device, M, N, K, prec)
+    call("mdg_linear_tn_packed_g", _ptr(gt_img), _ptr(x), x.stride(0), _ptr(dw), K, M, N, K, prec, _ptr(ws), nbytes, _stream(x))
     return dw
 
 
@@ -1256,17 +1203,15 @@ def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, beta: float = 0.
     R, C = x.shape
     if out is None:
         out, beta = torch.empty(C, dtype=torch.float32, device=x.device), 0.0
-    nbytes = lib().mdg_colsum_workspace_bytes(_c64(R), _c64(C))
-    ws = _workspace(nbytes, x.device)
-    check(lib().mdg_colsum(_ptr(x), _c64(x.stride(0)), _ptr(out), _c64(R), _c64(C), _f(beta), _ptr(ws), ctypes.c_size_t(nbytes),
-                           _stream(x)), "mdg_colsum")
+    ws, nbytes = _scratch("mdg_colsum_workspace_bytes", x.device, R, C)
+    call("mdg_colsum", _ptr(x), x.stride(0), _ptr(out), R, C, beta, _ptr(ws), nbytes, _stream(x))
     return out
 
 
 def activation_fwd(pre: torch.Tensor, act) -> torch.Tensor:
     pre = _f32_cuda(pre, "pre")
     y = torch.empty_like(pre)
-    check(lib().mdg_activation_fwd(_ptr(pre), _ptr(y), _c64(pre.numel()), _c(ACTS[act]), _stream(pre)), "mdg_activation_fwd")
+    call("mdg_activation_fwd", _ptr(pre), _ptr(y), pre.numel(), ACTS[act], _stream(pre))
     return y
 
 
@@ -1276,7 +1221,7 @@ def activation_bwd(dy: torch.Tensor, pre: torch.Tensor, act) -> torch.Tensor:
     if dy.shape != pre.shape:
         raise ValueError("activation_bwd: shape mismatch")
     dx = torch.empty_like(dy)
-    check(lib().mdg_activation_bwd(_ptr(dy), _ptr(pre), _ptr(dx), _c64(dy.numel()), _c(ACTS[act]), _stream(dy)), "mdg_activation_bwd")
+    call("mdg_activation_bwd", _ptr(dy), _ptr(pre), _ptr(dx), dy.numel(), ACTS[act], _stream(dy))
     return dx
 
 
@@ -1284,7 +1229,7 @@ def dropout(x: torch.Tensor, p: float, seed: int) -> torch.Tensor:
     """Inverted dropout with a counter-based mask: the same (seed, p) applied to a gradient is the backward pass."""
     x = _f32_cuda(x, "x")
     y = torch.empty_like(x)
-    check(lib().mdg_dropout(_ptr(x), _ptr(y), _c64(x.numel()), _f(p), ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(x)), "mdg_dropout")
+    call("mdg_dropout", _ptr(x), _ptr(y), x.numel(), p, seed & (2 ** 64 - 1), _stream(x))
     return y
 
 
@@ -1292,8 +1237,7 @@ def activation_dropout_fwd(pre: torch.Tensor, act, p: float, seed: int) -> torch
     """dropout(act(pre), p, seed) in one pass (same mask as ``dropout``)."""
     pre = _f32_cuda(pre, "pre")
     y = torch.empty_like(pre)
-    check(lib().mdg_activation_dropout_fwd(_ptr(pre), _ptr(y), _c64(pre.numel()), _c(ACTS[act]), _f(p), ctypes.c_uint64(seed & (2 ** 64 - 1)), _stream(pre)),
-          "mdg_activation_dropout_fwd")
+    call("mdg_activation_dropout_fwd", _ptr(pre), _ptr(y), pre.numel(), ACTS[act], p, seed & (2 ** 64 - 1), _stream(pre))
     return y
 
 
@@ -1303,8 +1247,7 @@ def activation_dropout_bwd(dy: torch.Tensor, pre: torch.Tensor, act, p: float, s
     if dy.shape != pre.shape:
         raise ValueError("activation_dropout_bwd: shape mismatch")
     dx = torch.empty_like(dy)
-    check(lib().mdg_activation_dropout_bwd(_ptr(dy), _ptr(pre), _ptr(dx), _c64(dy.numel()), _c(ACTS[act]), _f(p), ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                           _stream(dy)), "mdg_activation_dropout_bwd")
+    call("mdg_activation_dropout_bwd", _ptr(dy), _ptr(pre), _ptr(dx), dy.numel(), ACTS[act], p, seed & (2 ** 64 - 1), _stream(dy))
     return dx
 
 
@@ -1316,19 +1259,16 @@ def batchnorm_train_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var,
         raise ValueError("Expected more than 1 value per channel when training")      # torch's message
     y = torch.empty_like(x)
     stats = torch.empty(5 * C, dtype=torch.float32, device=x.device)
-    nbytes = lib().mdg_batchnorm_workspace_bytes(_c64(R), _c64(C))
-    ws = _workspace(nbytes, x.device)
-    check(lib().mdg_batchnorm_train_fwd(_ptr(x), _c64(C), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(y),
-                                        _c64(C), _ptr(stats), _c64(R), _c64(C), _f(eps), _f(momentum), _c(ACTS[act]), _ptr(ws),
-                                        ctypes.c_size_t(nbytes), _stream(x)), "mdg_batchnorm_train_fwd")
+    ws, nbytes = _scratch("mdg_batchnorm_workspace_bytes", x.device, R, C)
+    call("mdg_batchnorm_train_fwd", _ptr(x), C, _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(y), C, _ptr(stats), R, C, eps,
+         momentum, ACTS[act], _ptr(ws), nbytes, _stream(x))
     return y, stats
 
 
 def batchnorm_replay_update(stats: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor, rows: int, eps: float, momentum: float) -> None:
     """A further momentum update of the running statistics from the batch statistics of an earlier training-mode forward."""
     C = running_mean.numel()
-    check(lib().mdg_batchnorm_replay_update(_ptr(stats), _ptr(running_mean), _ptr(running_var), _c64(rows), _c64(C), _f(eps), _f(momentum),
-                                            _stream(stats)), "mdg_batchnorm_replay_update")
+    call("mdg_batchnorm_replay_update", _ptr(stats), _ptr(running_mean), _ptr(running_var), rows, C, eps, momentum, _stream(stats))
 
 
 def batchnorm_train_bwd(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor):
@@ -1338,10 +1278,8 @@ def batchnorm_train_bwd(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor):
     dx = torch.empty_like(x)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty_like(dg)
-    nbytes = lib().mdg_batchnorm_workspace_bytes(_c64(R), _c64(C))
-    ws = _workspace(nbytes, x.device)
-    check(lib().mdg_batchnorm_train_bwd(_ptr(dy), _ptr(x), _ptr(stats), _ptr(dx), _ptr(dg), _ptr(db), _c64(R), _c64(C), _ptr(ws),
-                                        ctypes.c_size_t(nbytes), _stream(x)), "mdg_batchnorm_train_bwd")
+    ws, nbytes = _scratch("mdg_batchnorm_workspace_bytes", x.device, R, C)
+    call("mdg_batchnorm_train_bwd", _ptr(dy), _ptr(x), _ptr(stats), _ptr(dx), _ptr(dg), _ptr(db), R, C, _ptr(ws), nbytes, _stream(x))
     return dx, dg, db
 
 
@@ -1355,19 +1293,16 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, eps: 
     dx = torch.empty((R, d), dtype=torch.float32, device=x2.device)
     dg = torch.empty(d, dtype=torch.float32, device=x2.device)
     db = torch.empty_like(dg)
-    nbytes = lib().mdg_layernorm_bwd_workspace_bytes(_c64(R), _c64(d))
-    ws = _workspace(nbytes, x2.device)
+    ws, nbytes = _scratch("mdg_layernorm_bwd_workspace_bytes", x2.device, R, d)
     if extra is not None:
         e2 = extra.reshape(-1, d) if extra.stride(-1) == 1 and extra.dim() == 2 else _f32_cuda(extra, "extra").reshape(-1, d)
         if e2.shape[0] != R:
             raise ValueError("layernorm_bwd: extra must have the shape of x")
-        check(lib().mdg_layernorm_bwd_add(_ptr(dy2), _c64(dy2.stride(0)), _ptr(x2), _c64(x2.stride(0)), _ptr(weight.detach().contiguous()), _ptr(e2),
-                                          _c64(e2.stride(0)), _ptr(dx), _c64(d), _ptr(dg), _ptr(db), _c64(R), _c64(d), _f(eps), _ptr(ws),
-                                          ctypes.c_size_t(nbytes), _stream(x2)), "mdg_layernorm_bwd_add")
+        call("mdg_layernorm_bwd_add", _ptr(dy2), dy2.stride(0), _ptr(x2), x2.stride(0), _ptr(weight.detach().contiguous()), _ptr(e2), e2.stride(0),
+             _ptr(dx), d, _ptr(dg), _ptr(db), R, d, eps, _ptr(ws), nbytes, _stream(x2))
         return dx.view(x.shape), dg, db
-    check(lib().mdg_layernorm_bwd(_ptr(dy2), _c64(dy2.stride(0)), _ptr(x2), _c64(x2.stride(0)), _ptr(weight.detach().contiguous()), _ptr(dx),
-                                  _c64(d), _ptr(dg), _ptr(db), _c64(R), _c64(d), _f(eps), _ptr(ws), ctypes.c_size_t(nbytes), _stream(x2)),
-          "mdg_layernorm_bwd")
+    call("mdg_layernorm_bwd", _ptr(dy2), dy2.stride(0), _ptr(x2), x2.stride(0), _ptr(weight.detach().contiguous()), _ptr(dx), d, _ptr(dg), _ptr(db),
+         R, d, eps, _ptr(ws), nbytes, _stream(x2))
     return dx.view(x.shape), dg, db
 
 
@@ -1375,8 +1310,8 @@ def affine_act(x: torch.Tensor, scale: torch.Tensor, shift: Optional[torch.Tenso
     """act(x * scale + shift) with per-column scale / shift."""
     x = _f32_cuda(x, "x", 2)
     y = torch.empty_like(x)
-    check(lib().mdg_affine_act(_ptr(x), _c64(x.stride(0)), _ptr(scale.contiguous()), _ptr(None if shift is None else shift.contiguous()),
-                               _ptr(y), _c64(y.stride(0)), _c64(x.shape[0]), _c64(x.shape[1]), _c(ACTS[act]), _stream(x)), "mdg_affine_act")
+    call("mdg_affine_act", _ptr(x), x.stride(0), _ptr(scale.contiguous()), _ptr(None if shift is None else shift.contiguous()), _ptr(y), y.stride(0),
+         x.shape[0], x.shape[1], ACTS[act], _stream(x))
     return y
 
 
@@ -1386,7 +1321,7 @@ def axpby(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0, beta: float = 1.
     if a.numel() % max(b.numel(), 1) or (b.numel() != a.numel() and tuple(a.shape[a.dim() - b.dim():]) != tuple(b.shape)):
         raise ValueError(f"axpby: cannot broadcast {tuple(b.shape)} over {tuple(a.shape)}")
     out = torch.empty_like(a)
-    check(lib().mdg_axpby(_ptr(a), _ptr(b), _ptr(out), _c64(a.numel()), _c64(b.numel()), _f(alpha), _f(beta), _stream(a)), "mdg_axpby")
+    call("mdg_axpby", _ptr(a), _ptr(b), _ptr(out), a.numel(), b.numel(), alpha, beta, _stream(a))
     return out
 
 
@@ -1408,12 +1343,10 @@ def assemble_tokens_bwd(dseq: torch.Tensor, str_emb, kg_emb, cv_emb, tx_emb, *, 
     dtx = torch.zeros((16 * n, D), dtype=torch.float32, device=dev)
     dlearned = torch.zeros((n, S, D), dtype=torch.float32, device=dev) if (nb or has_cls) else None
     dpe = torch.zeros((n, S, D), dtype=torch.float32, device=dev) if pe_len else None
-    check(lib().mdg_assemble_tokens_bwd(_ptr(dseq), _ptr(s), _ptr(k), _ptr(c), _ptr(t),
-                                        _ptr(None if bottleneck is None else bottleneck.detach().contiguous()),
-                                        _ptr(None if cls is None else cls.detach().contiguous()),
-                                        _ptr(None if token_index is None else token_index.contiguous()), _c64(n_tok), _ptr(dstr), _ptr(dkg),
-                                        _ptr(dcv), _ptr(dtx), _ptr(dlearned), _ptr(dpe), _c64(n), _c(nb), _c(1 if has_cls else 0),
-                                        _c(pe_len), _c(1 if normalize else 0), _c64(D), _stream(s)), "mdg_assemble_tokens_bwd")
+    call("mdg_assemble_tokens_bwd", _ptr(dseq), _ptr(s), _ptr(k), _ptr(c), _ptr(t),
+         _ptr(None if bottleneck is None else bottleneck.detach().contiguous()), _ptr(None if cls is None else cls.detach().contiguous()),
+         _ptr(None if token_index is None else token_index.contiguous()), n_tok, _ptr(dstr), _ptr(dkg), _ptr(dcv), _ptr(dtx), _ptr(dlearned),
+         _ptr(dpe), n, nb, 1 if has_cls else 0, pe_len, 1 if normalize else 0, D, _stream(s))
     out = {"str": dstr, "kg": dkg, "cv": dcv, "tx": dtx, "bottleneck": None, "cls": None, "pe": None}
     if dlearned is not None:
         tot = colsum(dlearned.view(n, S * D)).view(S, D)
@@ -1432,8 +1365,7 @@ def l2_normalize_bwd(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     if x.shape[1] % 4:
         raise ValueError("l2_normalize_bwd: feature dim must be a multiple of 4")
     dx = torch.empty_like(x)
-    check(lib().mdg_l2_normalize_bwd(_ptr(dy), _c64(dy.stride(0)), _ptr(x), _c64(x.stride(0)), _ptr(dx), _c64(dx.stride(0)),
-                                     _c64(x.shape[0]), _c64(x.shape[1]), _stream(x)), "mdg_l2_normalize_bwd")
+    call("mdg_l2_normalize_bwd", _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dx), dx.stride(0), x.shape[0], x.shape[1], _stream(x))
     return dx
 
 
@@ -1451,14 +1383,13 @@ def triple_plan(labels: torch.Tensor, heads: torch.Tensor, tails: torch.Tensor, 
     for nm, t in (("labels", labels), ("heads", heads), ("tails", tails)):
         if t.dtype != torch.int64 or not t.is_cuda or t.numel() != T or t.dim() != 1:
             raise ValueError(f"{nm}: expected int64 cuda [{T}]")
-    lb, st = lib(), _stream(labels)
+    st = _stream(labels)
     labels, heads, tails = labels.contiguous(), heads.contiguous(), tails.contiguous()
     i64 = lambda n: torch.empty(int(n), dtype=torch.int64, device=dev)
 
     def bounds(vals, n_vals, scale, n_bounds):
         out = i64(n_bounds)
-        check(lb.mdg_plan_lower_bounds(_ptr(vals), _c(vals.element_size()), _c64(n_vals), _c64(scale), _c64(n_bounds), _ptr(out), st),
-              "mdg_plan_lower_bounds")
+        call("mdg_plan_lower_bounds", _ptr(vals), vals.element_size(), n_vals, scale, n_bounds, _ptr(out), st)
         return out
 
     def by_drug(idx, n):
@@ -1469,13 +1400,13 @@ def triple_plan(labels: torch.Tensor, heads: torch.Tensor, tails: torch.Tensor, 
 
     def cut_count(ptr, n, size, totals_row):
         first = i64(n + 1)
-        check(lb.mdg_plan_cut_count(_ptr(ptr), _c64(n), _c64(size), _ptr(first), _ptr(totals_row), st), "mdg_plan_cut_count")
+        call("mdg_plan_cut_count", _ptr(ptr), n, size, _ptr(first), _ptr(totals_row), st)
         return first
 
     def cut_fill(ptr, first, n, size, total, want_which=True):
         which = i64(total) if want_which else None
         start = i64(total + 1)
-        check(lb.mdg_plan_cut_fill(_ptr(ptr), _ptr(first), _c64(n), _c64(size), _c64(total), _ptr(which), _ptr(start), st), "mdg_plan_cut_fill")
+        call("mdg_plan_cut_fill", _ptr(ptr), _ptr(first), n, size, total, _ptr(which), _ptr(start), st)
         return which, start
 
     # ONE sort serves the label order and the (label, head drug) pair order: by label, then by head inside a label (any
@@ -1487,8 +1418,8 @@ def triple_plan(labels: torch.Tensor, heads: torch.Tensor, tails: torch.Tensor, 
     hs, ts, skey, inv = i64(T), i64(T), i64(T), i64(T)
     sizes = torch.zeros((8, 2), dtype=torch.int64, device=dev)          # rows: tiles | chunks | head pieces | tail pieces | P | status
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(lb.mdg_plan_gather(_ptr(perm), _ptr(labels), _ptr(heads), _ptr(tails), _c64(T), _c64(n_labels), _c64(n_head), _c64(n_tail), _ptr(hs),
-                             _ptr(ts), _ptr(skey), _ptr(inv), _ptr(status), st), "mdg_plan_gather")
+    call("mdg_plan_gather", _ptr(perm), _ptr(labels), _ptr(heads), _ptr(tails), T, n_labels, n_head, n_tail, _ptr(hs), _ptr(ts), _ptr(skey),
+         _ptr(inv), _ptr(status), st)
     label_ptr = bounds(skey, T, n_head, n_labels + 1)
     head_ptr, head_rows = by_drug(hs, n_head)
     tail_ptr, tail_rows = by_drug(ts, n_tail)
@@ -1499,7 +1430,7 @@ def triple_plan(labels: torch.Tensor, heads: torch.Tensor, tails: torch.Tensor, 
     pair_of = None
     if T:
         flag = i64(T)
-        check(lb.mdg_plan_pair_flags(_ptr(skey), _c64(T), _ptr(flag), st), "mdg_plan_pair_flags")
+        call("mdg_plan_pair_flags", _ptr(skey), T, _ptr(flag), st)
         pair_of = torch.cumsum(flag, 0)                               # sorted triple -> its pair
         sizes[4, 0].copy_(pair_of[T - 1])
     sizes[5, 0].copy_(status[0])
@@ -1526,10 +1457,9 @@ def triple_plan(labels: torch.Tensor, heads: torch.Tensor, tails: torch.Tensor, 
     if T:
         P = int(host[4, 0]) + 1
         pair_ptr, pair_drug = i64(P + 1), i64(P)
-        check(lb.mdg_plan_pair_table(_ptr(skey), _ptr(pair_of), _c64(T), _c64(n_head), _c64(P), _ptr(pair_ptr), _ptr(pair_drug), st),
-              "mdg_plan_pair_table")
+        call("mdg_plan_pair_table", _ptr(skey), _ptr(pair_of), T, n_head, P, _ptr(pair_ptr), _ptr(pair_drug), st)
         plabel_ptr = i64(n_labels + 1)                                  # first pair of every label (= the pair of its first triple)
-        check(lb.mdg_plan_take(_ptr(pair_of), _ptr(label_ptr), _c64(n_labels + 1), _c64(T), _c64(P), _ptr(plabel_ptr), st), "mdg_plan_take")
+        call("mdg_plan_take", _ptr(pair_of), _ptr(label_ptr), n_labels + 1, T, P, _ptr(plabel_ptr), st)
         psizes = torch.zeros((4, 2), dtype=torch.int64, device=dev)     # rows: pair tiles | pair chunks | drug pieces
         ptile_first = cut_count(plabel_ptr, n_labels, 32, psizes[0])
         pchunk_first = cut_count(plabel_ptr, n_labels, 512, psizes[1])  # (256: 0.82 ms, 512 / 1024: 0.75 ms, 2048: 1.05 ms for the 2.4e6 pairs of the bench step)
@@ -1566,9 +1496,8 @@ def bilinear_gather(z_head: torch.Tensor, z_tail: torch.Tensor, w: torch.Tensor,
     if zh.shape != (plan["n_head"], 128) or zt.shape != (plan["n_tail"], 128) or w.shape != (plan["L"], 128, 128):
         raise ValueError("bilinear_gather: operands disagree with the plan (D must be 128)")
     score = torch.empty(plan["T"], dtype=torch.float32, device=zh.device)
-    check(lib().mdg_bilinear_gather(_ptr(zh), _ptr(zt), _ptr(w), _ptr(plan["heads"]), _ptr(plan["tails"]), _ptr(plan["tile_start"]),
-                                    _ptr(plan["tile_label"]), _c64(plan["n_tiles"]), _ptr(score), _c64(128), _stream(zh)),
-          "mdg_bilinear_gather")
+    call("mdg_bilinear_gather", _ptr(zh), _ptr(zt), _ptr(w), _ptr(plan["heads"]), _ptr(plan["tails"]), _ptr(plan["tile_start"]),
+         _ptr(plan["tile_label"]), plan["n_tiles"], _ptr(score), 128, _stream(zh))
     return score
 
 
@@ -1585,10 +1514,9 @@ def bilinear_gather_bwd(z_head, z_tail, w, plan: dict, dscore: torch.Tensor, w_t
     gt = torch.empty((T, 128), dtype=torch.float32, device=dev)
     dw = torch.empty((L, 128, 128), dtype=torch.float32, device=dev) if need_dw else None
     part = torch.empty((max(plan["n_chunks"], 1), 128, 128), dtype=torch.float32, device=dev) if need_dw else None
-    check(lib().mdg_bilinear_gather_bwd(_ptr(zh), _ptr(zt), _ptr(w), _ptr(wt), _ptr(plan["heads"]), _ptr(plan["tails"]),
-                                        _ptr(plan["tile_start"]), _ptr(plan["tile_label"]), _c64(plan["n_tiles"]), _ptr(plan["chunk_start"]),
-                                        _c64(plan["n_chunks"]), _ptr(plan["label_chunk_ptr"]), _c64(L), _ptr(ds), _ptr(gh), _ptr(gt),
-                                        _ptr(part), _ptr(dw), _c64(128), _stream(zh)), "mdg_bilinear_gather_bwd")
+    call("mdg_bilinear_gather_bwd", _ptr(zh), _ptr(zt), _ptr(w), _ptr(wt), _ptr(plan["heads"]), _ptr(plan["tails"]), _ptr(plan["tile_start"]),
+         _ptr(plan["tile_label"]), plan["n_tiles"], _ptr(plan["chunk_start"]), plan["n_chunks"], _ptr(plan["label_chunk_ptr"]), L, _ptr(ds), _ptr(gh),
+         _ptr(gt), _ptr(part), _ptr(dw), 128, _stream(zh))
     dzh = _sum_rows(gh, plan["head_ptr"], plan["head_rows"], plan.get("head_pieces"))
     dzt = _sum_rows(gt, plan["tail_ptr"], plan["tail_rows"], plan.get("tail_pieces"))
     return dzh, dzt, dw
@@ -1596,13 +1524,10 @@ def bilinear_gather_bwd(z_head, z_tail, w, plan: dict, dscore: torch.Tensor, w_t
 
 def _matvec_rows(z, w, row_index, pp, out, precision):
     """rows[p] = W[label of p] z[row_index[p]] per (label, drug) pair, in the step's arithmetic mode (exact fp32 / split-bf16 matrix cores)."""
-    L_ = lib()
     prec = _prec(precision)
-    nbytes = L_.mdg_bilinear_matvec_rows_workspace_bytes(_c64(w.shape[0]), _c(prec))
-    ws = _workspace(nbytes, z.device)
-    check(L_.mdg_bilinear_matvec_rows_prec(_ptr(z), _ptr(w), _c64(w.shape[0]), _ptr(row_index), _ptr(pp["tile_start"]), _ptr(pp["tile_label"]),
-                                           _c64(pp["n_tiles"]), _ptr(out), _c64(128), _c(prec), _ptr(ws), ctypes.c_size_t(nbytes), _stream(z)),
-          "mdg_bilinear_matvec_rows")
+    ws, nbytes = _scratch("mdg_bilinear_matvec_rows_workspace_bytes", z.device, w.shape[0], prec)
+    call("mdg_bilinear_matvec_rows_prec", _ptr(z), _ptr(w), w.shape[0], _ptr(row_index), _ptr(pp["tile_start"]), _ptr(pp["tile_label"]),
+         pp["n_tiles"], _ptr(out), 128, prec, _ptr(ws), nbytes, _stream(z), what="mdg_bilinear_matvec_rows")
 
 
 def bilinear_gather_pairs(z_head: torch.Tensor, z_tail: torch.Tensor, w: torch.Tensor, plan: dict, w_t: Optional[torch.Tensor] = None,
@@ -1618,10 +1543,8 @@ def bilinear_gather_pairs(z_head: torch.Tensor, z_tail: torch.Tensor, w: torch.T
         return score, torch.empty((0, 128), dtype=torch.float32, device=zh.device)
     wt = w if w_t is None else _f32_cuda(w_t, "w_t", 3)
     V = torch.empty((pp["P"], 128), dtype=torch.float32, device=zh.device)
-    L_ = lib()
     _matvec_rows(zh, wt, pp["drug"], pp, V, precision)
-    check(L_.mdg_gather_rowdot(_ptr(V), _ptr(pp["of_triple"]), _ptr(zt), _ptr(plan["tails"]), _ptr(score), _c64(plan["T"]), _c64(128),
-                               _stream(zh)), "mdg_gather_rowdot")
+    call("mdg_gather_rowdot", _ptr(V), _ptr(pp["of_triple"]), _ptr(zt), _ptr(plan["tails"]), _ptr(score), plan["T"], 128, _stream(zh))
     return score, V
 
 
@@ -1644,17 +1567,15 @@ def bilinear_gather_pairs_bwd(z_head, z_tail, w, plan: dict, dscore: torch.Tenso
     dzt = _sum_rows(V, plan["tail_ptr"], pp["of_triple_by_tail"], plan.get("tail_pieces"), edge_weight=ds.index_select(0, plan["tail_rows"]))
     u = csr_aggregate(zt, pp["ptr"], pp["tails_by_pair"], edge_weight=ds)
     R = torch.empty((pp["P"], 128), dtype=torch.float32, device=dev)
-    L_ = lib()
     _matvec_rows(u, w, None, pp, R, precision)
     dzh = _sum_rows(R, pp["drug_ptr"], pp["drug_rows"], pp.get("drug_pieces"))
     dw = None
     if need_dw:
         dw = torch.empty((L, 128, 128), dtype=torch.float32, device=dev)
         part = torch.empty((max(pp["n_chunks"], 1), 128, 128), dtype=torch.float32, device=dev)
-        check(L_.mdg_bilinear_gather_bwd_prec(_ptr(zh), _ptr(u), _ptr(w), _ptr(w), _ptr(pp["drug"]), _ptr(None), _ptr(None), _ptr(None), _c64(0),
-                                              _ptr(pp["chunk_start"]), _c64(pp["n_chunks"]), _ptr(pp["label_chunk_ptr"]), _c64(L), _ptr(None),
-                                              _ptr(None), _ptr(None), _ptr(part), _ptr(dw), _c64(128), _c(_prec(precision)), _stream(zh)),
-              "mdg_bilinear_gather_bwd")
+        call("mdg_bilinear_gather_bwd_prec", _ptr(zh), _ptr(u), _ptr(w), _ptr(w), _ptr(pp["drug"]), None, None, None, 0,
+             _ptr(pp["chunk_start"]), pp["n_chunks"], _ptr(pp["label_chunk_ptr"]), L, None, None, None, _ptr(part), _ptr(dw), 128,
+             _prec(precision), _stream(zh), what="mdg_bilinear_gather_bwd")
     return dzh[:, :128], dzt[:, :128], dw
 
 
@@ -1665,14 +1586,14 @@ def bce_logits(score: torch.Tensor, target: torch.Tensor, want_term: bool = True
         raise ValueError("bce_logits: shape mismatch")
     term = torch.empty_like(s) if want_term else None
     ds = torch.empty_like(s) if grad_scale is not None else None
-    check(lib().mdg_bce_logits(_ptr(s), _ptr(y), _ptr(term), _ptr(ds), _c64(s.numel()), _f(grad_scale or 0.0), _stream(s)), "mdg_bce_logits")
+    call("mdg_bce_logits", _ptr(s), _ptr(y), _ptr(term), _ptr(ds), s.numel(), grad_scale or 0.0, _stream(s))
     return term, ds
 
 
 def symmetrize_bwd(dw_sym: torch.Tensor) -> torch.Tensor:
     dws = _f32_cuda(dw_sym, "dw_sym", 3)
     out = torch.empty_like(dws)
-    check(lib().mdg_symmetrize_bwd(_ptr(dws), _ptr(out), _c64(dws.shape[0]), _c64(dws.shape[1]), _stream(dws)), "mdg_symmetrize_bwd")
+    call("mdg_symmetrize_bwd", _ptr(dws), _ptr(out), dws.shape[0], dws.shape[1], _stream(dws))
     return out
 
 
@@ -1680,7 +1601,7 @@ def mul_device_scalar(x: torch.Tensor, scalar: torch.Tensor) -> torch.Tensor:
     x = _f32_cuda(x, "x")
     s = _f32_cuda(scalar.reshape(1), "scalar", 1)
     out = torch.empty_like(x)
-    check(lib().mdg_mul_device_scalar(_ptr(x), _ptr(s), _ptr(out), _c64(x.numel()), _stream(x)), "mdg_mul_device_scalar")
+    call("mdg_mul_device_scalar", _ptr(x), _ptr(s), _ptr(out), x.numel(), _stream(x))
     return out
 
 
@@ -1689,7 +1610,7 @@ def f32_to_bf16(x: torch.Tensor) -> torch.Tensor:
     """bf16 mirror (round to nearest even) of a contiguous fp32 tensor whose element count is a multiple of 8 (mdg_f32_to_bf16)."""
     x = _f32_cuda(x, "x")
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-    check(lib().mdg_f32_to_bf16(_ptr(x), _ptr(y), _c64(x.numel()), _stream(x)), "mdg_f32_to_bf16")
+    call("mdg_f32_to_bf16", _ptr(x), _ptr(y), x.numel(), _stream(x))
     return y
 
 
@@ -1709,12 +1630,10 @@ def hgt_attention_stats(q: torch.Tensor, kv: torch.Tensor, plan: dict, heads: in
     out = torch.empty((n_dst, 128), dtype=torch.float32, device=q.device)
     stats = torch.empty((n_dst, heads, 2), dtype=torch.float32, device=q.device)
     n_items = int(plan["item_dst"].numel())
-    nbytes = lib().mdg_hgt_attention_workspace_bytes(_c64(n_items), _c(heads))
-    ws = _workspace(nbytes, q.device)
-    check(lib().mdg_hgt_attention_stats(_ptr(q), _c64(q.stride(0)), _ptr(kv), _c64(0 if kv is None else kv.stride(0)), _ptr(plan["col"]),
-                                        _ptr(plan["item_dst"]), _ptr(plan["item_begin"]), _ptr(plan["item_end"]), _c64(n_items),
-                                        _ptr(plan["item_ptr"]), _ptr(out), _c64(128), _c64(n_dst), _c(heads), _c64(128), _c(0),
-                                        _ptr(stats), _ptr(kv16), _ptr(ws), ctypes.c_size_t(nbytes), _stream(q)), "mdg_hgt_attention_stats")
+    ws, nbytes = _scratch("mdg_hgt_attention_workspace_bytes", q.device, n_items, heads)
+    call("mdg_hgt_attention_stats", _ptr(q), q.stride(0), _ptr(kv), 0 if kv is None else kv.stride(0), _ptr(plan["col"]), _ptr(plan["item_dst"]),
+         _ptr(plan["item_begin"]), _ptr(plan["item_end"]), n_items, _ptr(plan["item_ptr"]), _ptr(out), 128, n_dst, heads, 128, 0, _ptr(stats),
+         _ptr(kv16), _ptr(ws), nbytes, _stream(q))
     return out, stats
 
 
@@ -1736,16 +1655,12 @@ def hgt_attention_bwd(q: torch.Tensor, kv: torch.Tensor, plan: dict, rev: dict, 
         if dq.shape != (n_dst, 128) or dq.stride(1) != 1 or dq.stride(0) % 4 or dq.dtype != torch.float32 or not dq.is_cuda:
             raise ValueError("hgt_attention_bwd: dq_out must be an fp32 cuda [n_dst,128] view with unit inner stride")
     nnz, n_items = int(plan["col"].numel()), int(plan["item_dst"].numel())
-    nbytes = lib().mdg_hgt_attention_bwd_workspace_bytes(_c64(nnz), _c64(n_items), _c64(rev["n_items"]), _c(heads))
-    ws = _workspace(nbytes, q.device)
-    check(lib().mdg_hgt_attention_bwd(_ptr(q), _c64(q.stride(0)), _ptr(kv), _c64(128), _ptr(plan["col"]), _c64(nnz), _ptr(plan["item_dst"]),
-                                      _ptr(plan["item_begin"]), _ptr(plan["item_end"]), _c64(n_items), _ptr(plan["item_ptr"]), _c64(n_dst),
-                                      _ptr(dout), _c64(dout.stride(0)), _ptr(out_pre), _c64(out_pre.stride(0)), _ptr(stats), _c(heads),
-                                      _ptr(rev["t_edge"]), _ptr(rev["t_dst"]), _ptr(rev["item_begin"]), _ptr(rev["item_end"]),
-                                      _c64(rev["n_items"]), _ptr(rev["item_ptr"]), _ptr(rev["rows"]), _c64(rev["n_rows"]), _ptr(rev.get("item_row")),
-                                      _ptr(dq), _c64(dq.stride(0)), _ptr(dkv), _c64(128), _ptr(kv16), _ptr(ws), ctypes.c_size_t(nbytes),
-                                      _stream(q)),
-          "mdg_hgt_attention_bwd")
+    ws, nbytes = _scratch("mdg_hgt_attention_bwd_workspace_bytes", q.device, nnz, n_items, rev["n_items"], heads)
+    call("mdg_hgt_attention_bwd", _ptr(q), q.stride(0), _ptr(kv), 128, _ptr(plan["col"]), nnz, _ptr(plan["item_dst"]), _ptr(plan["item_begin"]),
+         _ptr(plan["item_end"]), n_items, _ptr(plan["item_ptr"]), n_dst, _ptr(dout), dout.stride(0), _ptr(out_pre), out_pre.stride(0), _ptr(stats),
+         heads, _ptr(rev["t_edge"]), _ptr(rev["t_dst"]), _ptr(rev["item_begin"]), _ptr(rev["item_end"]), rev["n_items"], _ptr(rev["item_ptr"]),
+         _ptr(rev["rows"]), rev["n_rows"], _ptr(rev.get("item_row")), _ptr(dq), dq.stride(0), _ptr(dkv), 128, _ptr(kv16), _ptr(ws), nbytes,
+         _stream(q))
     return dq
 
 
@@ -1755,8 +1670,7 @@ def gated_residual(o: torch.Tensor, x: torch.Tensor, skip: torch.Tensor) -> torc
     if o.shape != x.shape:
         raise ValueError("gated_residual: shape mismatch")
     out = torch.empty_like(o)
-    check(lib().mdg_gated_residual(_ptr(o), _ptr(x), _ptr(_f32_cuda(skip.reshape(1), "skip", 1)), _ptr(out), _c64(o.numel()), _stream(o)),
-          "mdg_gated_residual")
+    call("mdg_gated_residual", _ptr(o), _ptr(x), _ptr(_f32_cuda(skip.reshape(1), "skip", 1)), _ptr(out), o.numel(), _stream(o))
     return out
 
 
@@ -1765,8 +1679,8 @@ def gated_residual_bwd(dout: torch.Tensor, o: torch.Tensor, x: torch.Tensor, ski
     dout, o, x = _f32_cuda(dout, "dout", 2), _f32_cuda(o, "o", 2), _f32_cuda(x, "x", 2)
     d_o, d_x = torch.empty_like(o), torch.empty_like(o)
     rowdot = torch.empty(o.shape[0], dtype=torch.float32, device=o.device)
-    check(lib().mdg_gated_residual_bwd(_ptr(dout), _ptr(o), _ptr(x), _ptr(_f32_cuda(skip.reshape(1), "skip", 1)), _ptr(d_o), _ptr(d_x),
-                                       _ptr(rowdot), _c64(o.shape[0]), _c64(o.shape[1]), _stream(o)), "mdg_gated_residual_bwd")
+    call("mdg_gated_residual_bwd", _ptr(dout), _ptr(o), _ptr(x), _ptr(_f32_cuda(skip.reshape(1), "skip", 1)), _ptr(d_o), _ptr(d_x), _ptr(rowdot),
+         o.shape[0], o.shape[1], _stream(o))
     return d_o, d_x, colsum(rowdot.view(-1, 1))
 
 
@@ -1801,10 +1715,8 @@ def grad_weight(g: torch.Tensor, x: torch.Tensor, precision="f32", want_bias: bo
     if _prec(precision) != PREC_F32 and wide_weight_gradient(N, K):
         prec = _prec(precision)
         dw = torch.empty((N, K), dtype=torch.float32, device=g.device) if out is None else out[0]
-        nbytes = lib().mdg_linear_tn_workspace_bytes(_c64(M), _c64(N), _c64(K), _c(prec))
-        ws = _workspace(nbytes, g.device)
-        check(lib().mdg_linear_tn(_ptr(g), _c64(g.stride(0)), _ptr(x), _c64(x.stride(0)), _ptr(dw), _c64(K), _c64(M), _c64(N), _c64(K),
-                                  _c(prec), _ptr(ws), ctypes.c_size_t(nbytes), _stream(g)), "mdg_linear_tn")
+        ws, nbytes = _scratch("mdg_linear_tn_workspace_bytes", g.device, M, N, K, prec)
+        call("mdg_linear_tn", _ptr(g), g.stride(0), _ptr(x), x.stride(0), _ptr(dw), K, M, N, K, prec, _ptr(ws), nbytes, _stream(g))
         if not want_bias:
             return dw
         if out is None:
@@ -1813,10 +1725,9 @@ def grad_weight(g: torch.Tensor, x: torch.Tensor, precision="f32", want_bias: bo
         return dw, out[1]
     dw = torch.empty((N, K), dtype=torch.float32, device=g.device) if out is None else out[0]
     db = (torch.empty(N, dtype=torch.float32, device=g.device) if out is None else out[1]) if want_bias else None
-    nbytes = lib().mdg_grad_weight_workspace_bytes(_c64(M), _c64(N), _c64(K))
-    ws = _workspace(nbytes, g.device)
-    check(lib().mdg_grad_weight_prec(_ptr(g), _c64(g.stride(0)), _ptr(x), _c64(x.stride(0)), _ptr(dw), _ptr(db), _c64(M), _c64(N), _c64(K),
-                                     _c(_prec(precision)), _ptr(ws), ctypes.c_size_t(nbytes), _stream(g)), "mdg_grad_weight")
+    ws, nbytes = _scratch("mdg_grad_weight_workspace_bytes", g.device, M, N, K)
+    call("mdg_grad_weight_prec", _ptr(g), g.stride(0), _ptr(x), x.stride(0), _ptr(dw), _ptr(db), M, N, K, _prec(precision), _ptr(ws), nbytes,
+         _stream(g), what="mdg_grad_weight")
     return (dw, db) if want_bias else dw
 
 
@@ -1826,8 +1737,7 @@ def info_nce_bwd(sim: torch.Tensor, too_hard_neg: Optional[torch.Tensor], dloss:
     B = sim.shape[0] // 2
     hard = None if too_hard_neg is None else too_hard_neg.to(device=sim.device, dtype=torch.uint8).contiguous()
     dsim = torch.empty_like(sim)
-    check(lib().mdg_infonce_bwd(_ptr(sim), _ptr(hard), _ptr(_f32_cuda(dloss.reshape(1), "dloss", 1)), _ptr(dsim), _c64(B), _f(temperature),
-                                _stream(sim)), "mdg_infonce_bwd")
+    call("mdg_infonce_bwd", _ptr(sim), _ptr(hard), _ptr(_f32_cuda(dloss.reshape(1), "dloss", 1)), _ptr(dsim), B, temperature, _stream(sim))
     return dsim
 
 
@@ -1835,10 +1745,9 @@ def info_nce_bwd(sim: torch.Tensor, too_hard_neg: Optional[torch.Tensor], dloss:
 def _col_reduce(x, y, center, rstd, mode: int) -> torch.Tensor:
     R, C = x.shape
     out = torch.empty(C, dtype=torch.float32, device=x.device)
-    nbytes = lib().mdg_batchnorm_workspace_bytes(_c64(max(R, 1)), _c64(C))
-    ws = _workspace(nbytes, x.device)
-    check(lib().mdg_col_reduce(_ptr(x), _c64(x.stride(0)), _ptr(y), _c64(0 if y is None else y.stride(0)), _ptr(center), _ptr(rstd), _ptr(out),
-                               _c64(R), _c64(C), _c(mode), _ptr(ws), ctypes.c_size_t(nbytes), _stream(x)), "mdg_col_reduce")
+    ws, nbytes = _scratch("mdg_batchnorm_workspace_bytes", x.device, max(R, 1), C)
+    call("mdg_col_reduce", _ptr(x), x.stride(0), _ptr(y), 0 if y is None else y.stride(0), _ptr(center), _ptr(rstd), _ptr(out), R, C, mode, _ptr(ws),
+         nbytes, _stream(x))
     return out
 
 
@@ -1852,13 +1761,11 @@ def sync_batchnorm_train_fwd(x: torch.Tensor, gamma, beta, running_mean, running
     reduce_(s)
     reduce_(cnt)
     stats = torch.empty(5 * C, dtype=torch.float32, device=x.device)
-    fin = lib().mdg_batchnorm_finalize
-    check(fin(_ptr(s), _ptr(None), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(stats), ctypes.c_double(0.0), _ptr(cnt),
-              _c64(C), _f(eps), _f(momentum), _c(0), _stream(x)), "mdg_batchnorm_finalize")
+    tail = (_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(stats), 0.0, _ptr(cnt), C, eps, momentum)
+    call("mdg_batchnorm_finalize", _ptr(s), None, *tail, 0, _stream(x))
     q = _col_reduce(x, None, stats, None, 1)
     reduce_(q)
-    check(fin(_ptr(s), _ptr(q), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(stats), ctypes.c_double(0.0), _ptr(cnt),
-              _c64(C), _f(eps), _f(momentum), _c(1), _stream(x)), "mdg_batchnorm_finalize")
+    call("mdg_batchnorm_finalize", _ptr(s), _ptr(q), *tail, 1, _stream(x))
     y = affine_act(x, stats[2 * C:3 * C], stats[3 * C:4 * C], act)
     return y, stats, cnt
 
@@ -1873,8 +1780,8 @@ def sync_batchnorm_train_bwd(dy: torch.Tensor, x: torch.Tensor, stats: torch.Ten
     both = torch.cat([db, dg])
     reduce_(both)
     dx = torch.empty_like(x)
-    check(lib().mdg_batchnorm_bwd_apply(_ptr(dy), _ptr(x), _ptr(stats), _ptr(both[:C].contiguous()), _ptr(both[C:].contiguous()), _ptr(dx),
-                                        _c64(R), _c64(C), ctypes.c_double(0.0), _ptr(count), _stream(x)), "mdg_batchnorm_bwd_apply")
+    call("mdg_batchnorm_bwd_apply", _ptr(dy), _ptr(x), _ptr(stats), _ptr(both[:C].contiguous()), _ptr(both[C:].contiguous()), _ptr(dx), R, C, 0.0,
+         _ptr(count), _stream(x))
     return dx, dg, db
 
 
@@ -1918,12 +1825,9 @@ def label_metrics(pred: torch.Tensor, target: torch.Tensor, label: torch.Tensor,
     values = torch.empty(13, L, dtype=torch.float64, device=dev)
     count, pos, k_eff = (torch.empty(L, dtype=torch.int64, device=dev) for _ in range(3))
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    lb = lib()
-    nbytes = lb.mdg_label_metrics_workspace_bytes(_c64(T), _c64(L))
-    ws = _workspace(nbytes, dev)
-    check(lb.mdg_label_metrics(_ptr(pred), _ptr(target), _ptr(label), _c64(T), _c64(L), _c64(k_int), ctypes.c_double(k_frac),
-                               ctypes.c_float(threshold), _ptr(values), _ptr(count), _ptr(pos), _ptr(k_eff), _ptr(status), _ptr(ws),
-                               ctypes.c_size_t(nbytes), _stream(pred)), "mdg_label_metrics")
+    ws, nbytes = _scratch("mdg_label_metrics_workspace_bytes", dev, T, L)
+    call("mdg_label_metrics", _ptr(pred), _ptr(target), _ptr(label), T, L, k_int, k_frac, threshold, _ptr(values), _ptr(count), _ptr(pos),
+         _ptr(k_eff), _ptr(status), _ptr(ws), nbytes, _stream(pred))
     st = int(status.item())
     if st:
         raise ValueError("label_metrics: " + "; ".join(msg for bit, msg in _LABEL_METRIC_STATUS if st & bit))
@@ -1980,13 +1884,10 @@ def group_metrics(pred: torch.Tensor, target: torch.Tensor, group: torch.Tensor,
         n_outer = -(-n_groups // inner)
         outer_values = torch.empty(13, n_outer, dtype=torch.float64, device=dev)
         outer_groups = torch.empty(n_outer, dtype=torch.int64, device=dev)
-    lb = lib()
-    nbytes = lb.mdg_group_metrics_workspace_bytes(_c64(T), _c64(n_groups))
-    ws = _workspace(nbytes, dev)
-    check(lb.mdg_group_metrics(_ptr(pred), _ptr(target), _ptr(group), _c64(T), _c64(n_groups), _c64(k_int), ctypes.c_double(k_frac),
-                               ctypes.c_float(threshold), _c64(inner or 0), _ptr(group_id), _ptr(values), _ptr(count), _ptr(pos),
-                               _ptr(k_eff), _vp(meta.data_ptr() + 8), _ptr(outer_values), _ptr(outer_groups), _ptr(meta), _ptr(ws),
-                               ctypes.c_size_t(nbytes), _stream(pred)), "mdg_group_metrics")
+    ws, nbytes = _scratch("mdg_group_metrics_workspace_bytes", dev, T, n_groups)
+    call("mdg_group_metrics", _ptr(pred), _ptr(target), _ptr(group), T, n_groups, k_int, k_frac, threshold, inner or 0, _ptr(group_id), _ptr(values),
+         _ptr(count), _ptr(pos), _ptr(k_eff), meta.data_ptr() + 8, _ptr(outer_values), _ptr(outer_groups), _ptr(meta), _ptr(ws), nbytes,
+         _stream(pred))
     m = meta.cpu()
     st, n_present = int(m.view(torch.int32)[0]), int(m[1])
     if st:
@@ -2035,11 +1936,9 @@ def pair_match_counts(x: torch.Tensor, y: torch.Tensor) -> dict:
     out = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in PAIR_MATCH_COUNT_NAMES}
     out["align"] = torch.empty(n, dtype=torch.float32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    lb = lib()
-    nbytes = lb.mdg_pair_match_counts_workspace_bytes(_c64(n))
-    ws = _workspace(nbytes, dev)
-    check(lb.mdg_pair_match_counts(_ptr(x), _ptr(y), _c64(n), _c64(128), *(_ptr(out[k]) for k in PAIR_MATCH_COUNT_NAMES), _ptr(out["align"]),
-                                   _ptr(status), _ptr(ws), ctypes.c_size_t(nbytes), _stream(x)), "mdg_pair_match_counts")
+    ws, nbytes = _scratch("mdg_pair_match_counts_workspace_bytes", dev, n)
+    call("mdg_pair_match_counts", _ptr(x), _ptr(y), n, 128, *(_ptr(out[k]) for k in PAIR_MATCH_COUNT_NAMES), _ptr(out["align"]), _ptr(status),
+         _ptr(ws), nbytes, _stream(x))
     _pair_status(status, "pair_match_counts")
     return out
 
@@ -2059,10 +1958,7 @@ def pair_uniformity(x: torch.Tensor, t: float = 2.0) -> torch.Tensor:
     dev = x.device
     out = torch.empty((), dtype=torch.float32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    lb = lib()
-    nbytes = lb.mdg_pair_uniformity_workspace_bytes(_c64(m))
-    ws = _workspace(nbytes, dev)
-    check(lb.mdg_pair_uniformity(_ptr(x), _c64(m), _c64(128), ctypes.c_float(t), _ptr(out), _ptr(status), _ptr(ws), ctypes.c_size_t(nbytes),
-                                 _stream(x)), "mdg_pair_uniformity")
+    ws, nbytes = _scratch("mdg_pair_uniformity_workspace_bytes", dev, m)
+    call("mdg_pair_uniformity", _ptr(x), m, 128, t, _ptr(out), _ptr(status), _ptr(ws), nbytes, _stream(x))
     _pair_status(status, "pair_uniformity")
     return out

@@ -7,7 +7,6 @@ every parameter in ONE kernel launch (mdg_adamw_multi) instead of torch's per-te
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Dict, List
 
@@ -15,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ._lib import check, lib
+from ._lib import call, lib
 
 
 class _ChunkedOptimizer(torch.optim.Optimizer):
@@ -152,15 +151,13 @@ class _AdamFamily(_ChunkedOptimizer):
                 if hyper is None:
                     hyper = hyper_of[(gi, k)] = self._hyper(group, k)
                 by_dev.setdefault(p.device, []).append(((p, g, st["exp_avg"], st["exp_avg_sq"]), hyper))
-        entry = getattr(lib(), self._ENTRY)
         for dev, items in by_dev.items():
             lay, t_hyp = self._tables(dev, items)
             if lay["n"] == 0:
                 continue
             with torch.cuda.device(dev):
-                check(entry(ctypes.c_void_p(lay["t_ptr"].data_ptr()), ctypes.c_void_p(lay["t_len"].data_ptr()),
-                            ctypes.c_void_p(lay["t_own"].data_ptr()), ctypes.c_void_p(t_hyp.data_ptr()),
-                            ctypes.c_int64(lay["n"]), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), self._ENTRY)
+                call(self._ENTRY, lay["t_ptr"].data_ptr(), lay["t_len"].data_ptr(), lay["t_own"].data_ptr(), t_hyp.data_ptr(), lay["n"],
+                     torch.cuda.current_stream(dev).cuda_stream)
             self._launched(dev, lay, t_hyp, [t for (p, _, m, v), _ in items for t in (p, m, v)])
         return loss
 
@@ -251,15 +248,11 @@ class LARS(_ChunkedOptimizer):
                 cnt = np.bincount(lay["owner"], minlength=len(items)).astype(np.int32)
                 lay["t_first"] = torch.from_numpy((np.cumsum(cnt) - cnt).astype(np.int32)).to(dev)
                 lay["t_cnt"] = torch.from_numpy(cnt).to(dev)
-                lay["ws"] = torch.empty(int(lib().mdg_lars_multi_workspace_bytes(ctypes.c_int64(lay["n"]), ctypes.c_int64(len(items)))),
-                                        dtype=torch.uint8, device=dev)
+                lay["ws"] = torch.empty(lib().mdg_lars_multi_workspace_bytes(lay["n"], len(items)), dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                check(lib().mdg_lars_multi(ctypes.c_void_p(lay["t_ptr"].data_ptr()), ctypes.c_void_p(lay["t_len"].data_ptr()),
-                                           ctypes.c_void_p(lay["t_own"].data_ptr()), ctypes.c_void_p(t_hyp.data_ptr()),
-                                           ctypes.c_void_p(lay["t_first"].data_ptr()), ctypes.c_void_p(lay["t_cnt"].data_ptr()),
-                                           ctypes.c_int64(lay["n"]), ctypes.c_int64(len(items)), ctypes.c_void_p(lay["ws"].data_ptr()),
-                                           ctypes.c_size_t(lay["ws"].numel()), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                      "mdg_lars_multi")
+                call("mdg_lars_multi", lay["t_ptr"].data_ptr(), lay["t_len"].data_ptr(), lay["t_own"].data_ptr(), t_hyp.data_ptr(),
+                     lay["t_first"].data_ptr(), lay["t_cnt"].data_ptr(), lay["n"], len(items), lay["ws"].data_ptr(), lay["ws"].numel(),
+                     torch.cuda.current_stream(dev).cuda_stream)
             self._launched(dev, lay, t_hyp, [t for (p, _, mu), _ in items for t in (p, mu)])
         return loss
 

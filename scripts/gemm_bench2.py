@@ -1,11 +1,11 @@
 """Dense-block timing with the phases separated (HIP events on the launch stream): operand pack of x alone, the GEMM kernel
 alone on a packed x (ops.linear_packed), and the whole ops.linear call; plus a check of the 256-tile kernel against fp64 on
 sampled rows / columns and bit-identity with the 128-tile kernel on ragged shapes.   python scripts/gemm_bench2.py [bf16|bf16x3] [check]"""
-import ctypes, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from madrigal_amd import ops
-from madrigal_amd._lib import lib
+from madrigal_amd._lib import call, lib
 
 prec = sys.argv[1] if len(sys.argv) > 1 else "bf16"
 P = ops._prec(prec)
@@ -13,10 +13,9 @@ P = ops._prec(prec)
 
 def pack(x):
     M, K = x.shape
-    nb = int(lib().mdg_pack_operand_bytes(ctypes.c_int64(M), ctypes.c_int64(K), ctypes.c_int(P)))
+    nb = lib().mdg_pack_operand_bytes(M, K, P)
     img = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    ops.check(lib().mdg_pack_operand(ops._ptr(x), ctypes.c_int64(x.stride(0)), ctypes.c_int64(M), ctypes.c_int64(K), ctypes.c_int(P), ops._ptr(img),
-                                     ctypes.c_size_t(nb), ops._stream(x)), "pack")
+    call("mdg_pack_operand", x.data_ptr(), x.stride(0), M, K, P, img.data_ptr(), nb, ops._stream(x), what="pack")
     return img
 
 

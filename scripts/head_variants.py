@@ -17,9 +17,8 @@ z = torch.randn(a.n, 128, generator=g).cuda()
 w = ops.symmetrize((torch.randn(a.labels, 128, 128, generator=g) / 128 ** 0.5).cuda())
 out = torch.empty(a.labels, a.n, a.n, device="cuda")
 stamps = torch.zeros(2 * a.labels * ((a.n + 255) // 256), dtype=torch.int64, device="cuda")       # in-kernel clock stamps (diagnostics)
-import ctypes
 from madrigal_amd._lib import lib
-lib().mdg_debug_bilinear_stamps(ctypes.c_void_p(stamps.data_ptr()), ctypes.c_int64(stamps.numel()))
+lib().mdg_debug_bilinear_stamps(stamps.data_ptr(), stamps.numel())
 res = {}
 for prec in a.precisions.split(","):
     ref = None

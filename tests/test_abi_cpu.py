@@ -41,3 +41,78 @@ def test_missing_library_is_loud(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "LIB_PATH", os.path.join(tmp_path, "nope.so"))
     with pytest.raises(_lib.MadrigalHipError):
         _lib.lib()
+
+
+def test_prototypes_cover_every_declared_symbol():
+    from madrigal_amd import _lib
+    protos = _lib.declared_prototypes()
+    assert sorted(protos) == _lib.declared_symbols()
+    L = _lib.lib()
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == argtypes, name
+    assert protos["mdg_last_error"] == (ctypes.c_char_p, []) and protos["mdg_tuning_reload"] == (None, [])
+    assert protos["mdg_symmetrize"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p])
+    assert protos["mdg_gmean"][1][0] is ctypes.c_void_p                       # const float* const*
+    assert protos["mdg_pack_operand_bytes"] == (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int])
+
+
+@pytest.mark.parametrize("proto", ["int mdg_x(int64_t n, long flags, void* stream);", "unsigned mdg_x(int64_t n);",
+                                   "int mdg_x(unsigned int n);", "struct mdg_s mdg_x(void);", "float* mdg_x(void);"])
+def test_unknown_type_spelling_raises(proto):
+    from madrigal_amd import _lib
+    with pytest.raises(_lib.MadrigalHipError, match="mdg_x"):
+        _lib.parse_prototypes(proto)
+
+
+def test_size_queries_are_full_width():
+    """Host-only size queries with bare Python ints: results above 2^32 and one argument above 2^31 arrive whole."""
+    from madrigal_amd import _lib, ops
+    L = _lib.lib()
+    image = 8_000_000 * 256 * 4
+    assert image > 2 ** 32
+    assert L.mdg_pack_operand_bytes(8_000_000, 256, ops.PREC_BF16X3) >= image
+    assert L.mdg_linear_backward_pack_bytes(8_000_000, 256, ops.PREC_BF16X3, 0) >= image
+    assert L.mdg_label_metrics_workspace_bytes(3_000_000_000, 896) >= 16 * 3_000_000_000
+
+
+def test_typed_calls_reject_wrong_arguments():
+    from madrigal_amd import _lib
+    L = _lib.lib()
+    with pytest.raises(TypeError):
+        L.mdg_pack_operand_bytes(1024, 256)                                   # one argument too few
+    with pytest.raises(ctypes.ArgumentError):
+        L.mdg_pack_operand_bytes(1024.0, 256, 1)                              # a float for an int64_t
+    with pytest.raises(ctypes.ArgumentError):
+        L.mdg_symmetrize(3.5, None, 1, 128, None)                             # a float for a pointer
+
+
+def test_checked_call_honours_a_patched_symbol(monkeypatch):
+    from madrigal_amd import _lib
+    L = _lib.lib()
+    seen = []
+
+    def refusing(*args):
+        seen.append(args)
+        return -1
+    monkeypatch.setattr(L, "mdg_symmetrize", refusing)
+    with pytest.raises(ValueError, match="^mdg_symmetrize: "):
+        _lib.call("mdg_symmetrize", None, None, 1, 128, None)
+    with pytest.raises(ValueError, match="^some label: "):
+        _lib.call("mdg_symmetrize", None, None, 1, 128, None, what="some label")
+    assert seen == [(None, None, 1, 128, None)] * 2
+    monkeypatch.setattr(L, "mdg_symmetrize", lambda *args: -3)
+    with pytest.raises(_lib.MadrigalHipError, match=r"mdg_symmetrize failed \(code -3\)"):
+        _lib.call("mdg_symmetrize", None, None, 1, 128, None)
+    assert _lib.call("mdg_lars_multi", None, None, None, None, None, None, 0, 0, None, 0, None) is None    # status 0: no device touched
+
+
+def test_no_hand_marshalling_outside_the_binding():
+    import re
+    from madrigal_amd import _lib
+    spelling = re.compile(r"_c64\(|_vp\(|ctypes\.c_size_t\(|ctypes\.c_int64\(|ctypes\.c_void_p\(")
+    for f in sorted(os.listdir(_lib.HERE)):
+        if f.endswith(".py") and f != "_lib.py":
+            hits = [ln for ln in open(os.path.join(_lib.HERE, f)) if spelling.search(ln)]
+            assert not hits, (f, hits)
