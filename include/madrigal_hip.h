@@ -149,6 +149,28 @@ int mdg_bilinear_topk(const float* z_head, const float* z_tail, const float* w_s
                       int64_t n_tail, int64_t n_labels, int64_t D, int precision, int k, int eligible, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Per-outcome score counts of the all-pairs sweep: for every outcome l, given n_edges ascending finite fp32 edges e[l,0..B-1],
+ *   counts[l,b] = #{eligible (i,j) : e[l,b-1] <= S[l,i,j] < e[l,b]},   e[l,-1] = -inf, e[l,B] = +inf        (b = 0..B)
+ * -- torch.bucketize(S, e[l], right=True) followed by a bincount, without materialising [L,N,N].  The counting product of the head:
+ * with the edges at the scores of screened hits, the cumulative counts give the hits' exact normalised ranks,
+ * (1 + #{i>j : S[l,i,j] < s}) / (N (N-1) / 2), the value the reference computes by ranking the whole lower triangle
+ * (notebooks/normalize_scores.py:36-74); with evenly spaced edges they are per-outcome score histograms.
+ *   edges [n_labels,n_edges] fp32; counts [n_labels,n_edges+1] int64, zeroed by the call on `stream`; every row of counts sums
+ *   to the number of eligible pairs.  Equal neighbouring edges give an empty bin.  Edges must be ascending within an outcome: the
+ *   kernel cannot check that cheaply, and unsorted edges give unspecified counts (no out-of-bounds access).
+ *   Scores and `eligible` (enum mdg_topk_eligible; LOWER skips the column tiles wholly on or above the diagonal) are those of
+ *   mdg_bilinear_topk: bit for bit the general sweep's in F32 / BF16X3, <= 2e-6 of the scale off in the 16-bit modes.
+ *   1 <= n_edges <= mdg_bilinear_bincount_max_edges() (1024); n_labels <= 65535 per call; D == 128; NOT_SELF / LOWER need
+ *   n_head == n_tail.  n_tail < 2^23: a workgroup counts its up to 512 x n_tail scores in 32-bit counters; more is refused (MDG_EINVAL).
+ * Scores must be finite (a NaN is counted nowhere).  Workspace: the operand images of mdg_bilinear_allpairs (0 for F32).
+ * Deterministic: the workgroups add their counts into `counts` with integer atomics, so the sums are bit-identical from launch
+ * to launch. */
+int mdg_bilinear_bincount_max_edges(void);
+size_t mdg_bilinear_bincount_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_edges, int precision);
+int mdg_bilinear_bincount(const float* z_head, const float* z_tail, const float* w_sym, const float* edges, int64_t* counts,
+                          int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_edges, int precision, int eligible,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ dense blocks ---- */
 
 /* Y = alpha * act( (X W^T + bias) * scale + shift ) + beta * R      X [M,K] ldx, W [N,K] ldw (nn.Linear

@@ -1,0 +1,487 @@
+// Per-outcome score counts of the all-pairs bilinear sweep for gfx950 (mdg_bilinear_bincount).
+//
+//   for every outcome l, given B ascending edges e[l,0..B-1]:
+//     counts[l,b] = #{eligible (i,j) : e[l,b-1] <= S[l,i,j] < e[l,b]},  e[l,-1] = -inf, e[l,B] = +inf     (B + 1 int64 per outcome)
+//   = torch.bucketize(S, e[l], right=True) followed by a bincount, S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j].
+//
+// The histogram part of the reducing epilogue (top-k is topk.hip): nothing of [L,N,N] is materialised.  With the edges at the
+// scores of screened hits, the cumulative counts are the hits' exact ranks among all pairs (notebooks/normalize_scores.py:36-74);
+// with evenly spaced edges they are a score histogram.  The score arithmetic is the sweep's own -- the two kernels below are
+// the row-statistics sweeps of bilinear.hip exactly as topk.hip carries them (same prologue, same staging, same MFMA sequence
+// per accumulator element), with the epilogue replaced, so every counted score equals the general sweep's bit for bit in
+// f32 / bf16x3 (bf16 / f16: the 16x16x32 regrouping, <= 2e-6 of the scale, as for top-k).
+//
+// Epilogue.  One workgroup = one outcome (blockIdx.y), so the edge table is workgroup-uniform: the B edges and B + 1 u32
+// counters sit in LDS behind the three stage buffers (96 KB + 8 KB + 16 B of 160 KB).
+//   fast path: every accumulator element is compared with e[0] and e[B-1]; "below all" and "at or above all" are counted by
+//              ballot + popcount into two wave-uniform registers -- two compares per element, no memory traffic.  With the
+//              edges in the extreme tail (ranks of hits) nearly every score ends here.
+//   slow path: elements inside [e[0], e[B-1]) -- taken per group of 8 accumulator elements and only when some lane of the wave has
+//              one (wave-uniform branch): a branch-free binary search over the LDS edges, the 8 searches of a group level by
+//              level so that their LDS reads overlap (ceil(log2 B) + 1 reads each), then a non-returning LDS add on the bin.
+//   end:       the waves add their two fast-path counts to counters 0 and B; the workgroup adds its non-zero counters to the global
+//              int64 result with device-scope integer atomics (the entry point zeroes the result on the stream).  Integer sums:
+//              the result is bit-identical from launch to launch whatever the order.
+// Counter width: a workgroup sees at most BM * n_tail scores (BM = 256, or 512 in the 16-bit sweep), so its u32 counters
+// cannot overflow while n_tail < 2^23; the entry point refuses more.  Ineligible elements (and rows past n_head) become -inf
+// and are taken out of the "below all" count again; scores are finite by contract (a NaN is counted nowhere).
+#include "bilinear_tiles.h"
+
+namespace {
+
+constexpr int BINCOUNT_MAX_EDGES = 1024;
+constexpr int BINCOUNT_LDS_BYTES = 3 * STAGE_BYTES + BINCOUNT_MAX_EDGES * 4 + (BINCOUNT_MAX_EDGES + 4) * 4;
+
+struct BincountArgs {
+  const float* z_head;
+  TileSrc zt;
+  TileSrc w;            // W_sym (this call's labels); nrows = D
+  const float* edges;   // [n_labels, n_edges] ascending per outcome
+  unsigned long long* counts;   // [n_labels, n_edges + 1], zeroed on the stream before the launch
+  int64_t n_head, n_tail;
+  int n_edges;
+  int eligible;         // mdg_topk_eligible
+};
+
+__device__ __forceinline__ bool bincount_eligible(int mode, int64_t row, int64_t col, int64_t n_head, int64_t n_tail) {
+  const bool pair = mode == MDG_TOPK_NOT_SELF ? col != row : col < row;                 // (bitwise: selects, no branches)
+  return (row < n_head) & (col < n_tail) & ((mode == MDG_TOPK_ALL) | pair);
+}
+
+// column tiles a workgroup with head rows [row0, row0 + BM) has to visit: LOWER needs columns j <= last row - 1 only
+__device__ __forceinline__ int bincount_tiles(const BincountArgs& p, int64_t row0, int BM) {
+  const int nst = static_cast<int>((p.n_tail + BN - 1) / BN);
+  if (p.eligible != MDG_TOPK_LOWER) return nst;
+  const int64_t last = (row0 + BM < p.n_head ? row0 + BM : p.n_head) - 1;      // columns [0, last) are eligible for some row
+  const int need = static_cast<int>((last + BN - 1) / BN);
+  return need < 1 ? 1 : (need < nst ? need : nst);
+}
+
+// The wave's two fast-path counts and the edge / counter tables in LDS.
+struct BinState {
+  const float* eds;     // LDS: the outcome's B edges
+  unsigned* cnt;        // LDS: B + 1 counters
+  float e0, elast;      // e[0], e[B-1]
+  int B;
+  unsigned below, above;       // wave-uniform: scores < e[0], scores >= e[B-1]
+};
+
+// Fast path of NE accumulator elements: counts below / above, returns whether any lane holds a score inside [e0, elast).
+// An ineligible element arrives as -inf: it lands in `below`, and bincount_mask took it out of `below` beforehand.
+template <int NE>
+__device__ __forceinline__ bool bincount_classify(BinState& b, const float (&x)[NE]) {
+  unsigned long long outside = ~0ull;
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const unsigned long long lo = __ballot(x[e] < b.e0), hi = __ballot(x[e] >= b.elast);
+    b.below += __builtin_popcountll(lo);
+    b.above += __builtin_popcountll(hi);
+    outside &= lo | hi;
+  }
+  return (~outside & __ballot(true)) != 0;
+}
+
+// An element of a tile that is not wholly eligible: the score, or -inf (and one off `below`, where -inf will be counted).
+__device__ __forceinline__ float bincount_mask(BinState& b, bool ok, float x) {
+  b.below -= __builtin_popcountll(__ballot(!ok));
+  return ok ? x : -INFINITY;
+}
+
+// Slow path of a group of NE elements (wave-uniform call): bin = #{edges <= x} by a branch-free binary search, all NE
+// searches level by level; lanes whose element is outside [e0, elast) (or NaN) search along and add nothing.
+template <int NE>
+__device__ __forceinline__ void bincount_search(const BinState& b, const float (&x)[NE]) {
+  int base[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) base[e] = 0;
+  int len = b.B;
+  while (len > 1) {                                  // invariant: the bin of x[e] lies in [base[e], base[e] + len], base[e] + len <= B
+    const int half = len >> 1;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) base[e] += b.eds[base[e] + half - 1] <= x[e] ? half : 0;
+    len -= half;
+  }
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const int bin = base[e] + (b.eds[base[e]] <= x[e] ? 1 : 0);
+    if (x[e] >= b.e0 && x[e] < b.elast) __hip_atomic_fetch_add(b.cnt + bin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+}
+
+// Kernel start: the outcome's edges into LDS, the counters to zero.  The prologue's barriers order this before the sweep.
+__device__ __forceinline__ void bincount_begin(BinState& b, const BincountArgs& p, char* smem, int64_t l, int tid) {
+  float* eds = reinterpret_cast<float*>(smem + 3 * STAGE_BYTES);
+  unsigned* cnt = reinterpret_cast<unsigned*>(smem + 3 * STAGE_BYTES + BINCOUNT_MAX_EDGES * 4);
+  const float* ge = p.edges + l * p.n_edges;
+  for (int i = tid; i < p.n_edges; i += 512) eds[i] = ge[i];
+  for (int i = tid; i <= p.n_edges; i += 512) cnt[i] = 0u;
+  b.eds = eds;
+  b.cnt = cnt;
+  b.B = p.n_edges;
+  b.e0 = ge[0];
+  b.elast = ge[p.n_edges - 1];
+  b.below = 0u;
+  b.above = 0u;
+}
+
+// Kernel end: the waves' fast-path counts into counters 0 and B, the workgroup's non-zero counters into the global result.
+__device__ __forceinline__ void bincount_end(const BinState& b, const BincountArgs& p, int64_t l, int tid) {
+  if ((tid & 63) == 0) {
+    if (b.below) __hip_atomic_fetch_add(b.cnt, b.below, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (b.above) __hip_atomic_fetch_add(b.cnt + b.B, b.above, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  unsigned long long* out = p.counts + l * (p.n_edges + 1);
+  for (int i = tid; i <= b.B; i += 512) {
+    const unsigned c = b.cnt[i];
+    if (c) __hip_atomic_fetch_add(out + i, static_cast<unsigned long long>(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the counting epilogue ---------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(512, 1) void bilinear_bincount_kernel(const BincountArgs p) {
+  static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "32x32 sweep of the fp32-grade modes");
+  constexpr int NW = 8, BM = 32 * NW;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const buf0 = smem;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int64_t l = blockIdx.y;
+  // LOWER: the last row block sweeps the most column tiles -- it goes first
+  const int64_t rbk = p.eligible == MDG_TOPK_LOWER ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const int64_t row0 = rbk * BM;
+  BinState bs;
+  bincount_begin(bs, p, smem, l, tid);
+
+  // ---------------- prologue: T = z_head[rows] . W_sym[l], kept as the A operand (as in bilinear.hip) -------------
+  AFrag<MODE> At;
+  {
+    AFrag<MODE> Az;
+    int64_t zr = row0 + wave * 32 + r;
+    zr = zr < p.n_head ? zr : p.n_head - 1;
+    afrag_from_global<MODE>(Az, p.z_head + zr * D, h);
+    TileSrc ws = p.w;
+    if constexpr (MODE == MDG_PREC_F32) ws.f32 += l * D * D;
+    else { ws.hi += l * D * D; ws.lo += l * D * D; }
+    char* const slab = smem + wave * 8192;       // [32 rows][64 cols] fp32, chunk-swizzled
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      u32x4 regs[32 / NW];
+      stage_load<MODE, NW>(ws, 64 * st, tid, regs);
+      __syncthreads();                            // slabs of the previous half are consumed
+      stage_write<MODE, NW>(buf0, tid, regs);
+      __syncthreads();
+      f32x16 acc[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+      compute_tile<MODE>(Az, buf0, r, h, acc);
+      __syncthreads();                            // every wave is done reading buf0
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int row = acc_row(v, h), n = 32 * t + r;
+          *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[t][v];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      afrag_from_slab<MODE>(At, slab, st, r, h);
+    }
+    __syncthreads();
+  }
+
+  // ---------------- sweep: three stage buffers, prefetch distance two, ascending column tiles -------------
+  const int nst = bincount_tiles(p, row0, BM);
+  const int64_t wrow0 = row0 + wave * 32;        // this wave's rows: wrow0 .. wrow0 + 31
+  const int mode = p.eligible;
+  constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
+  static_assert(NDMA == 4, "vmcnt immediate below");
+  stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  int cur = 0;
+  for (int s = 0; s < nst; ++s) {
+    const int64_t tcol0 = static_cast<int64_t>(s) * BN;
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = NDMA: tile s landed, tile s+1 stays in flight
+    __builtin_amdgcn_s_barrier();      // tile s landed for every wave; every wave finished reading tile s-1
+    const int nxt2 = cur == 0 ? 2 : cur - 1;                           // (cur + 2) % 3 = buffer of tile s-1
+    const int s2 = s + 2 < nst ? s + 2 : nst - 1;                      // past the end: a copy nobody consumes
+    stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    const char* lds = smem + cur * STAGE_BYTES;
+    cur = cur == 2 ? 0 : cur + 1;
+    if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 31) continue;       // wave-uniform: no column of this tile is below any of my rows
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+    compute_tile<MODE>(At, lds, r, h, acc);
+    // whole tile eligible for every row of the wave (wave-uniform): no per-element masking
+    const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 32 <= p.n_head &&
+                       (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 31));
+    if (!plain) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          acc[t][v] = bincount_mask(bs, bincount_eligible(mode, wrow0 + acc_row(v, h), tcol0 + 32 * t + r, p.n_head, p.n_tail), acc[t][v]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = acc[t][8 * g + e];
+        if (bincount_classify<8>(bs, x)) bincount_search<8>(bs, x);
+      }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  bincount_end(bs, p, l, tid);
+}
+
+// ---- bf16 / f16: bilinear_rowstats16_kernel (v_mfma_f32_16x16x32, 64 rows per wave) with the counting epilogue -----------------
+typedef __attribute__((ext_vector_type(4))) float f32x4v;
+
+template <int MODE>
+__device__ __forceinline__ f32x4v bincount_mma16x16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
+  if constexpr (MODE == MDG_PREC_F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(512, 1) void bilinear_bincount16_kernel(const BincountArgs p) {
+  static_assert(kSingle16<MODE>, "one rounded 16-bit product per k step");
+  constexpr int NW = 8, BM = 512;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const buf0 = smem;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5, c16 = lane & 15, g4 = lane >> 4;
+  const int64_t l = blockIdx.y;
+  const int64_t rbk = p.eligible == MDG_TOPK_LOWER ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const int64_t row0 = rbk * BM;
+  BinState bs;
+  bincount_begin(bs, p, smem, l, tid);
+  // ---- prologue: T = z_head[rows] . W_sym[l] (32x32x16 products, as every other path), re-laid out for 16x16x32 ----
+  bf16x8 A16[4][4];                                  // [row tile of 16][k step of 32]: lane (c16, g4) holds row c16, k = 32 ks + 8 g4 ..+7
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb) {
+    AFrag<MODE> Az;
+    int64_t zr = row0 + (wave * 2 + rb) * 32 + r;
+    zr = zr < p.n_head ? zr : p.n_head - 1;
+    afrag_from_global<MODE>(Az, p.z_head + zr * D, h);
+    TileSrc ws = p.w;
+    ws.hi += l * D * D;
+    char* const slab = smem + wave * 8192;             // [32 rows][64 cols] fp32, chunk-swizzled
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      u32x4 regs[32 / NW];
+      stage_load<MODE, NW>(ws, 64 * st, tid, regs);
+      __syncthreads();
+      stage_write<MODE, NW>(buf0, tid, regs);
+      __syncthreads();
+      f32x16 acc[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+      compute_tile<MODE>(Az, buf0, r, h, acc);
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int row = acc_row(v, h), n = 32 * t + r;
+          *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[t][v];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int rt2 = 0; rt2 < 2; ++rt2)
+#pragma unroll
+        for (int ksl = 0; ksl < 2; ++ksl) {
+          const int row = 16 * rt2 + c16, chunk = (32 * ksl + 8 * g4) >> 2;         // 4-float chunks of the 64-column half
+          const float4 v0 = *reinterpret_cast<const float4*>(slab + tile_off<256>(row, chunk));
+          const float4 v1 = *reinterpret_cast<const float4*>(slab + tile_off<256>(row, chunk + 1));
+          bf16x8 hi, lo;
+          split8<MODE>(v0, v1, hi, lo);
+          A16[2 * rb + rt2][2 * st + ksl] = hi;
+        }
+    }
+    __syncthreads();
+  }
+  // ---- sweep ----
+  const int nst = bincount_tiles(p, row0, BM);
+  const int64_t wrow0 = row0 + wave * 64;            // this wave's rows: wrow0 .. wrow0 + 63
+  const int mode = p.eligible;
+  stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  int cur = 0;
+  for (int s = 0; s < nst; ++s) {
+    const int64_t tcol0 = static_cast<int64_t>(s) * BN;
+    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // = LDS-DMA instructions per wave and tile: tile s landed, tile s+1 stays in flight
+    __builtin_amdgcn_s_barrier();
+    const int nxt2 = cur == 0 ? 2 : cur - 1;
+    const int s2 = s + 2 < nst ? s + 2 : nst - 1;
+    stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    const char* lds = smem + cur * STAGE_BYTES;
+    cur = cur == 2 ? 0 : cur + 1;
+    if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 63) continue;       // wave-uniform: nothing below the diagonal for my rows
+    const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 64 <= p.n_head &&
+                       (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 63));
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      f32x4v acc[4];
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8 b = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(16 * ct + c16, 4 * ks + g4));
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = bincount_mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
+      }
+      const int64_t col = tcol0 + 16 * ct + c16;
+      if (!plain) {
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            acc[rt][i] = bincount_mask(bs, bincount_eligible(mode, wrow0 + 16 * rt + 4 * g4 + i, col, p.n_head, p.n_tail), acc[rt][i]);
+      }
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = acc[2 * g + (e >> 2)][e & 3];
+        if (bincount_classify<8>(bs, x)) bincount_search<8>(bs, x);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  bincount_end(bs, p, l, tid);
+}
+
+// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
+template <int MODE>
+__global__ void bincount_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float4 v = reinterpret_cast<const float4*>(x)[i];
+  const float f[4] = {v.x, v.y, v.z, v.w};
+  if constexpr (MODE == MDG_PREC_F16) {
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+    f16x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
+    reinterpret_cast<f16x4*>(hi)[i] = o;
+  } else {
+    bf16x4 hv, lw;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      __bf16 a, b;
+      mdg_split_bf16(f[c], a, b);
+      hv[c] = a;
+      lw[c] = b;
+    }
+    reinterpret_cast<bf16x4*>(hi)[i] = hv;
+    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
+  }
+}
+
+inline size_t bincount_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+template <int MODE>
+int launch_bincount(BincountArgs& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st) {
+  if constexpr (MODE == MDG_PREC_F32) {
+    a.zt.f32 = z_tail;
+    a.w.f32 = w_sym;
+  } else {
+    const size_t zb = bincount_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = bincount_align256(static_cast<size_t>(n_labels) * D * D * 2);
+    const bool x3 = MODE == MDG_PREC_BF16X3;
+    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
+    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
+    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
+    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
+    const int64_t z4 = a.n_tail * D / 4, w4 = n_labels * D * D / 4;
+    hipLaunchKernelGGL(bincount_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
+    hipLaunchKernelGGL(bincount_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
+    MDG_CHECK_LAUNCH("mdg_bilinear_bincount(operand images)");
+    a.zt.hi = zhi; a.zt.lo = zlo;
+    a.w.hi = whi; a.w.lo = wlo;
+  }
+  if constexpr (kSingle16<MODE>) {
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
+    hipLaunchKernelGGL(bilinear_bincount16_kernel<MODE>, grid, dim3(512), BINCOUNT_LDS_BYTES, st, a);
+  } else {
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
+    hipLaunchKernelGGL(bilinear_bincount_kernel<MODE>, grid, dim3(512), BINCOUNT_LDS_BYTES, st, a);
+  }
+  MDG_CHECK_LAUNCH("mdg_bilinear_bincount");
+  return MDG_OK;
+}
+
+}  // namespace
+
+extern "C" int mdg_bilinear_bincount_max_edges(void) { return BINCOUNT_MAX_EDGES; }
+
+extern "C" size_t mdg_bilinear_bincount_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_edges, int precision) {
+  (void)n_head; (void)n_edges;
+  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
+  const size_t z = bincount_align256(static_cast<size_t>(n_tail) * D_ * 2), w = bincount_align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
+  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+}
+
+extern "C" int mdg_bilinear_bincount(const float* z_head, const float* z_tail, const float* w_sym, const float* edges, int64_t* counts,
+                                     int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_edges, int precision, int eligible,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  MDG_CHECK_ARG(D_ == D, "mdg_bilinear_bincount: D must be %d (got %lld)", D, (long long)D_);
+  MDG_CHECK_ARG(n_edges >= 1 && n_edges <= BINCOUNT_MAX_EDGES, "mdg_bilinear_bincount: n_edges must be in 1..%d (got %d)", BINCOUNT_MAX_EDGES,
+                n_edges);
+  MDG_CHECK_ARG(n_head >= 0 && n_tail >= 0 && n_labels >= 0, "mdg_bilinear_bincount: negative size");
+  MDG_CHECK_ARG(n_tail < (int64_t(1) << 23), "mdg_bilinear_bincount: n_tail %lld does not fit the 32-bit workgroup counters (< 2^23)",
+                (long long)n_tail);
+  MDG_CHECK_ARG(n_labels <= 65535, "mdg_bilinear_bincount: n_labels %lld > 65535 per call", (long long)n_labels);
+  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || eligible == MDG_TOPK_NOT_SELF || eligible == MDG_TOPK_LOWER,
+                "mdg_bilinear_bincount: unknown eligible mode %d", eligible);
+  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail,
+                "mdg_bilinear_bincount: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)", (long long)n_head,
+                (long long)n_tail);
+  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16 || precision == MDG_PREC_F16,
+                "mdg_bilinear_bincount: unknown precision %d", precision);
+  if (n_labels == 0) return MDG_OK;
+  MDG_CHECK_ARG(edges && counts, "mdg_bilinear_bincount: null pointer");
+  const bool empty = n_head == 0 || n_tail == 0;          // no pair at all: every count is 0
+  MDG_CHECK_ARG(empty || (z_head && z_tail && w_sym), "mdg_bilinear_bincount: null pointer");
+  MDG_CHECK_ARG(empty || (mdg_aligned16(z_head) && mdg_aligned16(z_tail) && mdg_aligned16(w_sym)),
+                "mdg_bilinear_bincount: z_head, z_tail and w_sym must be 16-byte aligned");
+  const size_t need = empty ? 0 : mdg_bilinear_bincount_workspace_bytes(n_head, n_tail, n_labels, D_, n_edges, precision);
+  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
+    mdg_set_error("mdg_bilinear_bincount: workspace of %zu bytes (16-byte aligned) required, got %zu", need, workspace_bytes);
+    return MDG_EWORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(counts, 0, static_cast<size_t>(n_labels) * (n_edges + 1) * sizeof(int64_t), st) != hipSuccess) {
+    (void)hipGetLastError();
+    mdg_set_error("mdg_bilinear_bincount: zeroing the counts failed");
+    return MDG_ELAUNCH;
+  }
+  if (empty) return MDG_OK;
+  BincountArgs a{};
+  a.z_head = z_head;
+  a.edges = edges;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.n_head = n_head; a.n_tail = n_tail;
+  a.n_edges = n_edges;
+  a.eligible = eligible;
+  a.zt.nrows = n_tail;
+  a.w.nrows = D;
+  char* ws = static_cast<char*>(workspace);
+  switch (precision) {
+    case MDG_PREC_F32: return launch_bincount<MDG_PREC_F32>(a, z_tail, w_sym, n_labels, ws, st);
+    case MDG_PREC_BF16X3: return launch_bincount<MDG_PREC_BF16X3>(a, z_tail, w_sym, n_labels, ws, st);
+    case MDG_PREC_BF16: return launch_bincount<MDG_PREC_BF16>(a, z_tail, w_sym, n_labels, ws, st);
+    default: return launch_bincount<MDG_PREC_F16>(a, z_tail, w_sym, n_labels, ws, st);
+  }
+}

@@ -1686,6 +1686,17 @@ class BilinearDDIScorer(nn.Bilinear):
             w = w[label_range[0]:label_range[1]]
         return ops.bilinear_topk(input1, input2, w, k, eligible=eligible, precision=_state["precision"])
 
+    def bincount(self, input1, input2, edges, label_range: tuple = None, eligible: str = "all"):
+        """Extension (screening): int64 [L', B+1] -- per outcome the number of eligible scores of ``forward(input1, input2,
+        label_range)`` between the ascending ``edges`` [L', B] (``torch.bucketize(right=True)`` + bincount), in the precision
+        ``forward`` uses; nothing of [L', n1, n2] is materialised (``ops.bilinear_bincount``).  Inference only."""
+        ops.forward_only(input1, input2)
+        w = self.symmetric_weight()
+        if label_range is not None:
+            assert len(label_range) == 2
+            w = w[label_range[0]:label_range[1]]
+        return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"])
+
     def score_triples(self, input1, input2, plan: dict) -> torch.Tensor:
         """Extension (finetune step): scores of the plan's (label, head, tail) triples only, in the plan's
         label-sorted order, differentiable w.r.t. both embeddings and the weight (train_ddi_batch.py:285-286

@@ -196,6 +196,62 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     return vals, idx
 
 
+def bilinear_bincount_max_edges() -> int:
+    """Largest number of edges per outcome of ``bilinear_bincount`` (at least 1024)."""
+    return lib().mdg_bilinear_bincount_max_edges()
+
+
+def bilinear_bincount(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, edges: torch.Tensor, *, eligible: str = "all",
+                      precision="bf16x3") -> torch.Tensor:
+    """Per-outcome counts of the all-pairs sweep's scores between edges -> int64 [L, B+1]: with ``edges`` [L, B] fp32, finite and
+    ascending per outcome, ``counts[l, b]`` is the number of eligible pairs (i, j) with ``edges[l, b-1] <= S[l,i,j] < edges[l, b]``
+    (``edges[l, -1] = -inf``, ``edges[l, B] = +inf``): ``torch.bucketize(S[l], edges[l], right=True)`` followed by a bincount, with
+    nothing of [L,Nh,Nt] materialised.  Equal neighbouring edges give an empty bin; every row sums to the number of eligible pairs.
+
+    ``eligible`` and the score arithmetic are those of ``bilinear_topk`` ("f32" / "bf16x3": the general sweep's scores bit for bit;
+    "bf16" / "f16": the row-statistics sweep, <= 2e-6 of the scale).  ``1 <= B <= bilinear_bincount_max_edges()``; Nt < 2^23.
+    Integer sums: bit-identical from launch to launch."""
+    # shapes and edge values first (on whatever device the tensors live), then the device: a bad call says what is wrong with it
+    for t, name, nd in ((z_head, "z_head", 2), (z_tail, "z_tail", 2), (w_sym, "w_sym", 3), (edges, "edges", 2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    D = z_head.shape[1]
+    if z_tail.shape[1] != D or w_sym.shape[1] != D or w_sym.shape[2] != D:
+        raise ValueError(f"feature dims disagree: z_head {tuple(z_head.shape)}, z_tail {tuple(z_tail.shape)}, w {tuple(w_sym.shape)}")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
+    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    L, Nh, Nt, B = w_sym.shape[0], z_head.shape[0], z_tail.shape[0], edges.shape[1]
+    max_edges = bilinear_bincount_max_edges()
+    if edges.shape[0] != L:
+        raise ValueError(f"edges: expected [{L}, B] (one row per outcome), got {tuple(edges.shape)}")
+    if not 1 <= B <= max_edges:
+        raise ValueError(f"edges: expected 1..{max_edges} edges per outcome, got {B}")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    if Nt >= 1 << 23:
+        raise ValueError(f"z_tail: {Nt} rows; the 32-bit workgroup counters hold fewer than 2^23")
+    if L and not bool(torch.isfinite(edges).all()):
+        raise ValueError("edges: must be finite")
+    if L and not bool((edges[:, 1:] >= edges[:, :-1]).all()):
+        raise ValueError("edges: must be ascending within every outcome (unsorted edges give unspecified counts)")
+    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
+    e = _f32_cuda(edges, "edges", 2)
+    if zh.device != zt.device or zh.device != w.device or zh.device != e.device:
+        raise ValueError("z_head, z_tail, w_sym and edges must be on the same device")
+    counts = torch.empty((L, B + 1), dtype=torch.int64, device=zh.device)
+    # the grid's y extent caps one call at 65535 outcomes; chunk above that
+    for lo in range(0, L, 65535):
+        hi = min(L, lo + 65535)
+        ws, nbytes = _scratch("mdg_bilinear_bincount_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, B, prec)
+        call("mdg_bilinear_bincount", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, e.data_ptr() + lo * B * 4,
+             counts.data_ptr() + lo * (B + 1) * 8, Nh, Nt, hi - lo, D, B, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+    return counts
+
+
 ENSEMBLE_PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}
 
 

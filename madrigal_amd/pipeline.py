@@ -318,6 +318,130 @@ def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, i
     return out_v, out_h, out_t
 
 
+@torch.no_grad()
+def score_histogram(model, z: torch.Tensor, edges: torch.Tensor, label_range: Optional[Tuple[int, int]] = None,
+                    eligible: str = "lower") -> torch.Tensor:
+    """Per-outcome histogram of the all-pairs scores -> int64 [L', B+1]: ``counts[l, b]`` is the number of eligible pairs whose
+    score lies in ``[edges[l, b-1], edges[l, b])`` (-inf below the first edge, +inf above the last), counted inside the sweep
+    (``decoder.bincount``) -- no [L', N, N] tensor at any N.  ``edges``: ``[B]`` shared by all outcomes or ``[L', B]``, fp32,
+    finite and ascending, 1 <= B <= ``ops.bilinear_bincount_max_edges()``.  ``eligible``: ``"lower"`` (the unordered pairs
+    i > j the rank normalisation reads, the default), ``"not_self"`` or ``"all"``.  Cumulative sums of a row are the
+    distribution function of the outcome's scores at the edges, from which quantiles follow.
+    Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
+    lo, hi = _outcomes(model, label_range)
+    e = torch.as_tensor(edges, dtype=torch.float32, device=z.device)
+    if e.dim() == 1:
+        e = e[None, :].expand(hi - lo, -1)
+    if e.dim() != 2 or e.shape[0] != hi - lo:
+        raise ValueError(f"edges: expected [B] or [{hi - lo}, B], got {tuple(e.shape)}")
+    return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible)
+
+
+@torch.no_grad()
+def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """For every query ``scores[l, q]`` the number of strict-lower-triangle pairs (i > j) of outcome l that score strictly less
+    -> int64 [L', Q].  Any Q; the queries may be unsorted and repeated.  Per outcome they are sorted and deduplicated, the
+    counting sweep (``decoder.bincount``, lower-triangle mode) runs once per chunk of at most ``ops.bilinear_bincount_max_edges()``
+    edges, the cumulative sum of a chunk's counts is the answer for its edges (chunks are independent: bin 0 of every chunk
+    already holds everything below its first edge), and the answers are scattered back to the queries' places.
+    Multi-GPU: pass the rank's outcome shard as ``label_range``."""
+    lo, hi = _outcomes(model, label_range)
+    s = torch.as_tensor(scores, dtype=torch.float32, device=z.device)
+    if s.dim() != 2 or s.shape[0] != hi - lo:
+        raise ValueError(f"scores: expected [{hi - lo}, Q], got {tuple(s.shape)}")
+    L, Q = s.shape
+    less = torch.zeros((L, Q), dtype=torch.int64, device=z.device)
+    if L == 0 or Q == 0:
+        return less
+    if not bool(torch.isfinite(s).all()):
+        raise ValueError("scores: queries must be finite")
+    sv, order = torch.sort(s, dim=1)
+    new = torch.ones_like(sv, dtype=torch.bool)
+    new[:, 1:] = sv[:, 1:] != sv[:, :-1]
+    pos = torch.cumsum(new, 1) - 1                              # place of every sorted query among its outcome's distinct values
+    U = int(pos.max()) + 1
+    uniq = sv[:, -1:].expand(L, U).clone()                      # outcomes with fewer distinct values: the largest one repeated (empty bins)
+    uniq.scatter_(1, pos, sv)
+    below = torch.empty((L, U), dtype=torch.int64, device=z.device)
+    step = ops.bilinear_bincount_max_edges()
+    for c0 in range(0, U, step):
+        c1 = min(U, c0 + step)
+        counts = model.decoder.bincount(z, z, uniq[:, c0:c1].contiguous(), (lo, hi), eligible="lower")
+        below[:, c0:c1] = torch.cumsum(counts, 1)[:, : c1 - c0]
+    less.scatter_(1, order, torch.gather(below, 1, pos))
+    return less
+
+
+def ranks_from_counts(less: torch.Tensor, N: int) -> torch.Tensor:
+    """Normalised rank of a pair with ``less`` pairs of its outcome scoring below it, among the N (N - 1) / 2 pairs of N drugs
+    -> float32: ``(less + 1) / (N (N - 1) / 2)``, divided in float64 and rounded to float32 once -- the arithmetic of
+    notebooks/normalize_scores.py:46-57 (1-based integer rank over a float64 count, stored into a float32 memmap).  A pure
+    tensor function (CPU or GPU); the one place that arithmetic is restated."""
+    return ((less.to(torch.float64) + 1.0) / (N * (N - 1) / 2)).to(torch.float32)
+
+
+@torch.no_grad()
+def normalized_ranks_of(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """The normalised rank of the scores ``scores[l, q]`` within their outcomes -> float32 [L', Q]: the value the reference's
+    rank tensor (notebooks/normalize_scores.py:36-74) holds where the pair scoring ``scores[l, q]`` sits, without the [L', N, N]
+    score tensor, its sort, or any limit on N: ``ranks_from_counts(count_below(...), N)``.
+
+    Tie rule: for a score value shared by several pairs this is the LOWEST rank of the tie group.  ``ops.rank_normalize`` spreads
+    the group over consecutive ranks by its stable tie-break and the reference's order inside a group is arbitrary (argsort is
+    not stable there), so tied pairs agree with either only up to the size of their group."""
+    return ranks_from_counts(count_below(model, z, scores, label_range), z.shape[0])
+
+
+@torch.no_grad()
+def pair_ranks(model, z: torch.Tensor, heads, tails, label_range: Optional[Tuple[int, int]] = None, max_temp_bytes: int = 1 << 30):
+    """Scores and normalised ranks of P given drug pairs -> ``(scores [L', P] fp32, ranks [L', P] fp32)``.  The pair {i, j} is
+    scored as ``S[l, max(i, j), min(i, j)]``, the strict-lower-triangle entry the rank normalisation reads (the dense head is not
+    bit-symmetric: S[l, i, j] and S[l, j, i] may differ in the last bits); i == j is refused.  This is what turns a
+    ``top_partners`` hit list -- whose values are S[l, i, j] with j on either side of i -- into normalised ranks.
+
+    The scores come from the dense general sweep over the rows that occur (``decoder(z[rows].contiguous(), z, ...)``, as
+    ``top_pairs`` re-scores its open rows), in row and outcome chunks whose temporaries stay under ``max_temp_bytes``: in "f32" /
+    "bf16x3" they are bit for bit what the counting sweep sees.  The ranks are ``normalized_ranks_of`` those scores (its tie rule
+    applies).  Multi-GPU: pass the rank's outcome shard as ``label_range``."""
+    lo, hi = _outcomes(model, label_range)
+    N = z.shape[0]
+    h, t = _index(heads, N, "heads", z.device), _index(tails, N, "tails", z.device)
+    if h is None or t is None or h.numel() != t.numel():
+        raise ValueError("heads / tails: two index lists of one length")
+    if bool((h == t).any()):
+        raise ValueError("heads / tails: a drug paired with itself has no rank (the strict lower triangle holds i > j)")
+    big, small = torch.maximum(h, t), torch.minimum(h, t)
+    P = int(big.numel())
+    scores = torch.empty((hi - lo, P), dtype=torch.float32, device=z.device)
+    if P and hi > lo:
+        rows, where = torch.unique(big, return_inverse=True)            # ascending rows; where[p]: the place of pair p's row
+        rb = max(1, min(int(rows.numel()), int(max_temp_bytes) // (N * 4)))
+        chunk = max(1, int(max_temp_bytes) // (rb * N * 4))
+        for r0 in range(0, int(rows.numel()), rb):
+            r1 = min(int(rows.numel()), r0 + rb)
+            mine = ((where >= r0) & (where < r1)).nonzero()[:, 0]
+            zr = z[rows[r0:r1]].contiguous()
+            for s in range(lo, hi, chunk):
+                e = min(hi, s + chunk)
+                dense = model.decoder(zr, z, (s, e))
+                scores[s - lo:e - lo, mine] = dense[:, where[mine] - r0, small[mine]]
+                del dense
+    return scores, normalized_ranks_of(model, z, scores, (lo, hi))
+
+
+@torch.no_grad()
+def ensemble_pair_ranks(models, zs, heads, tails, label_range: Optional[Tuple[int, int]] = None, max_temp_bytes: int = 1 << 30):
+    """Normalised ranks of P given pairs under K checkpoints and their geometric mean -> ``(per_model [K, L', P], gmean [L', P])``:
+    ``pair_ranks`` with every checkpoint's model and embeddings, then ``ops.gmean`` over the K rank matrices (the 5-seed ensembling
+    of the normalisation notebook, cell 18).  The notebook's re-ranking of the ensembled tensor (cell 20) ranks the geometric
+    means of ALL pairs against each other, which needs every pair's value: out of scope here."""
+    K = len(models)
+    if not 1 <= K <= 8 or len(zs) != K:
+        raise ValueError(f"ensemble_pair_ranks: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
+    ranks = [pair_ranks(m, z, heads, tails, label_range, max_temp_bytes)[1] for m, z in zip(models, zs)]
+    return torch.stack(ranks), ops.gmean(ranks)
+
+
 def _ensemble_weight(m) -> torch.Tensor:
     """W_sym [L,128,128] of one checkpoint: a NovelDDIMultilabel, its BilinearDDIScorer, or an original [L,D,D] weight."""
     if isinstance(m, torch.Tensor):
