@@ -171,6 +171,35 @@ int mdg_bilinear_bincount(const float* z_head, const float* z_tail, const float*
                           int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_edges, int precision, int eligible,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Threshold selection inside the all-pairs sweep (ABI 15): for every outcome l with its cut thr[l], ALL eligible pairs (i,j) with
+ *   S[l,i,j] >= thr[l]
+ * as CSR over the n_labels * n_head rows (l,i), without materialising [L,N,N].  The set-valued product of the head -- "every pair
+ * above a cut", the predicted interaction network of an outcome -- whose size is not known beforehand, hence two sweeps:
+ *   mdg_bilinear_select_count: row_counts [n_labels,n_head] int32, the number of selected columns of every row (every entry is
+ *     written, zeros included).  The caller's exclusive prefix sum over the flattened counts is row_ptr.
+ *   mdg_bilinear_select_fill:  row_ptr [n_labels*n_head + 1] int64; cols [T] int32 and vals [T] fp32, T = row_ptr[last]: the
+ *     selected columns of row (l,i) in ASCENDING order and their scores at [row_ptr[l*n_head+i], row_ptr[l*n_head+i+1]) --
+ *     canonical CSR, the order torch.nonzero gives on the dense mask (S >= thr) & eligible.
+ * The reference has no function of this kind: it reads such sets off its stored score / rank tensor; in LOWER mode the pairs
+ * are those of the strict lower triangle notebooks/normalize_scores.py:39-46 ranks.
+ *   The rule is >= (it matches the edges of mdg_bilinear_bincount, e <= S, and a cut at the K-th best value includes that
+ *   value); thr = -inf selects every eligible pair, +inf none; a NaN score is never selected and a NaN cut selects nothing.
+ *   Scores and `eligible` (enum mdg_topk_eligible; LOWER skips the column tiles wholly on or above the diagonal) are those of
+ *   mdg_bilinear_topk: bit for bit the general sweep's in F32 / BF16X3, <= 2e-6 of the scale off in the 16-bit modes (there a
+ *   score within that distance of the cut may fall on either side of it; count and fill agree with each other exactly).
+ *   n_tail >= 1 and < 2^31 - 64; n_labels <= 65535 per call; D == 128; NOT_SELF / LOWER need n_head == n_tail.
+ * Deterministic: every row belongs to one wave that walks the column tiles in ascending order; no atomics; bit-identical from
+ * launch to launch.  Bounded writes: the fill pass stores slot s of row r only if 0 <= row_ptr[r] <= s < row_ptr[r+1]; with a
+ * row_ptr that does not match thr (stale counts) rows are truncated or left partly unwritten, and nothing is stored outside
+ * [row_ptr[r], row_ptr[r+1]).  All slot arithmetic is 64-bit.  Workspace: the operand images of mdg_bilinear_allpairs (0 for F32). */
+size_t mdg_bilinear_select_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision);
+int mdg_bilinear_select_count(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
+                              int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision, int eligible,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mdg_bilinear_select_fill(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const int64_t* row_ptr,
+                             int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D,
+                             int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ dense blocks ---- */
 
 /* Y = alpha * act( (X W^T + bias) * scale + shift ) + beta * R      X [M,K] ldx, W [N,K] ldw (nn.Linear

@@ -1,0 +1,505 @@
+// Threshold selection inside the all-pairs bilinear sweep for gfx950 (mdg_bilinear_select_count / mdg_bilinear_select_fill).
+//
+//   for every outcome l with its cut thr[l]: all eligible pairs (i, j) with S[l,i,j] >= thr[l], S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j],
+//   as CSR over the n_labels * n_head rows (l, i): row_ptr, then per hit its column j and its score.
+//
+// The set-valued product of the head ("every pair above a cut"): nothing of [L,N,N] is materialised.  The score arithmetic is
+// the sweep's own -- the kernels below are the row-statistics sweeps of bilinear.hip exactly as topk.hip and bincount.hip carry
+// them (same prologue, same staging, same MFMA sequence per accumulator element, same `eligible` handling and LOWER tile skipping),
+// with the epilogue replaced, so every compared and stored score equals the general sweep's bit for bit in f32 / bf16x3
+// (bf16 / f16: the 16x16x32 regrouping, <= 2e-6 of the scale, as for top-k).
+//
+// Two passes over the same sweep (FILL = false / true), because the size of the result is not known beforehand:
+//   count: row_counts[l,i] = #{eligible j : S[l,i,j] >= thr[l]}.  The caller's exclusive prefix sum over the flattened counts is
+//          row_ptr (int64, n_labels * n_head + 1 entries).
+//   fill:  the same sweep again; hit number q of row (l,i) in ascending column order goes to slot row_ptr[l * n_head + i] + q.
+// Epilogue.  Every head row belongs to ONE wave, G lanes per row (G = 32 on the 32x32 MFMA, 16 on 16x16x32), each lane holding one
+// column; per accumulator register and lane there is one running u32 `run` = hits of that row in the tiles swept so far
+// (uniform over the G lanes; 16 registers in either layout).
+//   pass-through: one v_cmp per accumulator element (x >= thr), OR-ed into one ballot per tile (per 16-column sub-tile in the
+//                 16-bit sweep): a tile without a hit costs what ROWSTATS' add + max costs;
+//   hit path:     (wave-uniform branch) per accumulator register one ballot; the popcount of the row group's bits is added to `run`;
+//                 FILL: a lane with a hit reads row_ptr[row] and row_ptr[row + 1] there and then (lazily: no per-row state
+//                 besides `run`), its slot is row_ptr[row] + run + popcount(the group's ballot bits on lower lanes), and it
+//                 stores its column and score with two plain vector stores.
+//   end:          count: lane 0 of every group stores `run` -- one store per row, rows without a hit included, so the result
+//                 needs no zeroing.  No atomics, no LDS beyond the stage buffers.
+// Order.  A workgroup walks its column tiles in ascending order (no per-workgroup rotation), and inside a tile the column rises
+// with the lane index inside the row group, in both accumulator layouts:
+//   32x32 (f32 / bf16x3): register v of accumulator t in lane (r, h) is row acc_row(v, h), column tcol0 + 32 t + r; the group is
+//                  the 32 lanes of one h, r is the lane index inside it, and t = 0 (columns 0..31) is taken before t = 1 (32..63);
+//   16x16x32 (bf16 / f16): element i of accumulator rt in lane (c16, g4) is row 16 rt + 4 g4 + i, column tcol0 + 16 ct + c16; the
+//                  group is the 16 lanes of one g4, c16 is the lane index inside it, and the sub-tiles ct = 0..3 are taken in turn.
+// So the hits of a row land in ascending column order and the whole output is canonical CSR: the order torch.nonzero gives on
+// the dense [L, Nh, Nt] mask.  Nothing depends on timing: bit-identical from launch to launch.
+// Bounded writes.  The fill pass writes slot s of row r only if row_ptr[r] >= 0 and row_ptr[r] <= s < row_ptr[r + 1]; a hit past
+// the row's end is dropped.  A stale or wrong row_ptr (counts of another threshold) therefore gives a truncated or partly
+// unwritten result, never a store outside [row_ptr[r], row_ptr[r + 1]) -- inside cols / vals as long as row_ptr's own entries are.
+// All slot arithmetic is 64-bit (row_ptr int64, `run` < n_tail < 2^31 widened before the add).
+// Ineligible elements (and rows past n_head) become NaN, which fails `x >= thr` for every thr, -inf included; for the same
+// reason a NaN score is never selected.
+#include "bilinear_tiles.h"
+
+namespace {
+
+struct SelectArgs {
+  const float* z_head;
+  TileSrc zt;
+  TileSrc w;                  // W_sym (this call's labels); nrows = D
+  const float* thr;           // [n_labels]
+  int* row_counts;            // count pass: [n_labels, n_head]
+  const long long* row_ptr;   // fill pass: [n_labels * n_head + 1]
+  int* cols;                  // fill pass: [row_ptr[last]]
+  float* vals;
+  int64_t n_head, n_tail;
+  int eligible;               // mdg_topk_eligible
+};
+
+// Eligibility of the element in row wrow0 + lr, column tcol0 + lc of a tile (0 <= lr, lc < 64) from the tile's 32-bit distances
+// (wave-uniform, select_clamp-ed): dcr = tcol0 - wrow0, nr = n_head - wrow0, nc = n_tail - tcol0.  The same test as top-k's and
+// bincount's on the 64-bit indices (col - row keeps its sign and its zero through the clamp); a lane's lr and lc differ from
+// element to element by compile-time constants only.
+__device__ __forceinline__ int select_clamp(int64_t x) {
+  return static_cast<int>(x < -(int64_t(1) << 30) ? -(int64_t(1) << 30) : (x > (int64_t(1) << 30) ? (int64_t(1) << 30) : x));
+}
+__device__ __forceinline__ bool select_eligible(int mode, int lr, int lc, int dcr, int nr, int nc) {
+  const int d = dcr + lc - lr;                                                          // column - row
+  const bool pair = mode == MDG_TOPK_NOT_SELF ? d != 0 : d < 0;                         // (bitwise: selects, no branches)
+  return (lr < nr) & (lc < nc) & ((mode == MDG_TOPK_ALL) | pair);
+}
+
+// column tiles a workgroup with head rows [row0, row0 + BM) has to visit: LOWER needs columns j <= last row - 1 only
+__device__ __forceinline__ int select_tiles(const SelectArgs& p, int64_t row0, int BM) {
+  const int nst = static_cast<int>((p.n_tail + BN - 1) / BN);
+  if (p.eligible != MDG_TOPK_LOWER) return nst;
+  const int64_t last = (row0 + BM < p.n_head ? row0 + BM : p.n_head) - 1;      // columns [0, last) are eligible for some row
+  const int need = static_cast<int>((last + BN - 1) / BN);
+  return need < 1 ? 1 : (need < nst ? need : nst);
+}
+
+// Hit path of one accumulator register.  Must be called in wave-uniform control flow.  G lanes share the row whose row_ptr entry is
+// `rp` (FILL; read by lanes with a hit only -- an ineligible element never hits, so rp[0] and rp[1] lie inside row_ptr); `run`: the
+// row's hits so far.
+template <int G, bool FILL>
+__device__ __forceinline__ void select_take(const SelectArgs& p, unsigned& run, bool hit, float x, int col, const long long* rp, int lane) {
+  constexpr unsigned GMASK = G == 32 ? 0xFFFFFFFFu : 0xFFFFu;
+  const unsigned long long m = __ballot(hit);
+  const int c = lane & (G - 1), base = lane & ~(G - 1);
+  const unsigned mine = static_cast<unsigned>(m >> base) & GMASK;    // hits of MY row, one bit per lane of the group
+  if constexpr (FILL) {
+    if (hit) {
+      const int64_t beg = rp[0], end = rp[1];
+      const int64_t slot = beg + static_cast<int64_t>(run) + __builtin_popcount(mine & ((1u << c) - 1u));
+      if (beg >= 0 && slot < end) {
+        p.cols[slot] = col;
+        p.vals[slot] = x;
+      }
+    }
+  }
+  run += __builtin_popcount(mine);
+}
+
+// ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the selecting epilogue ---------------------------------------
+template <int MODE, bool FILL>
+__global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectArgs p) {
+  static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "32x32 sweep of the fp32-grade modes");
+  constexpr int NW = 8, BM = 32 * NW;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const buf0 = smem;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int64_t l = blockIdx.y;
+  // LOWER: the last row block sweeps the most column tiles -- it goes first
+  const int64_t rbk = p.eligible == MDG_TOPK_LOWER ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const int64_t row0 = rbk * BM;
+  const float thr = p.thr[l];
+
+  // ---------------- prologue: T = z_head[rows] . W_sym[l], kept as the A operand (as in bilinear.hip) -------------
+  AFrag<MODE> At;
+  {
+    AFrag<MODE> Az;
+    int64_t zr = row0 + wave * 32 + r;
+    zr = zr < p.n_head ? zr : p.n_head - 1;
+    afrag_from_global<MODE>(Az, p.z_head + zr * D, h);
+    TileSrc ws = p.w;
+    if constexpr (MODE == MDG_PREC_F32) ws.f32 += l * D * D;
+    else { ws.hi += l * D * D; ws.lo += l * D * D; }
+    char* const slab = smem + wave * 8192;       // [32 rows][64 cols] fp32, chunk-swizzled
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      u32x4 regs[32 / NW];
+      stage_load<MODE, NW>(ws, 64 * st, tid, regs);
+      __syncthreads();                            // slabs of the previous half are consumed
+      stage_write<MODE, NW>(buf0, tid, regs);
+      __syncthreads();
+      f32x16 acc[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+      compute_tile<MODE>(Az, buf0, r, h, acc);
+      __syncthreads();                            // every wave is done reading buf0
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int row = acc_row(v, h), n = 32 * t + r;
+          *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[t][v];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      afrag_from_slab<MODE>(At, slab, st, r, h);
+    }
+    __syncthreads();
+  }
+
+  // ---------------- sweep: three stage buffers, prefetch distance two, ascending column tiles -------------
+  const int nst = select_tiles(p, row0, BM);
+  const int64_t wrow0 = row0 + wave * 32;        // this wave's rows: wrow0 .. wrow0 + 31
+  const int mode = p.eligible;
+  unsigned run[16];                              // hits so far of row acc_row(v, h)
+  const long long* const rp = p.row_ptr + (l * p.n_head + wrow0 + 4 * h);      // row acc_row(v, h): rp[(v & 3) + 8 * (v >> 2)]
+#pragma unroll
+  for (int v = 0; v < 16; ++v) run[v] = 0u;
+  constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
+  static_assert(NDMA == 4, "vmcnt immediate below");
+  stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  int cur = 0;
+  for (int s = 0; s < nst; ++s) {
+    const int64_t tcol0 = static_cast<int64_t>(s) * BN;
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = NDMA: tile s landed, tile s+1 stays in flight
+    __builtin_amdgcn_s_barrier();      // tile s landed for every wave; every wave finished reading tile s-1
+    const int nxt2 = cur == 0 ? 2 : cur - 1;                           // (cur + 2) % 3 = buffer of tile s-1
+    const int s2 = s + 2 < nst ? s + 2 : nst - 1;                      // past the end: a copy nobody consumes
+    stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    const char* lds = smem + cur * STAGE_BYTES;
+    cur = cur == 2 ? 0 : cur + 1;
+    if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 31) continue;       // wave-uniform: no column of this tile is below any of my rows
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+    compute_tile<MODE>(At, lds, r, h, acc);
+    // whole tile eligible for every row of the wave (wave-uniform): no per-element masking
+    const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 32 <= p.n_head &&
+                       (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 31));
+    if (!plain) {
+      const int dcr = select_clamp(tcol0 - wrow0), nr = select_clamp(p.n_head - wrow0), nc = select_clamp(p.n_tail - tcol0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          acc[t][v] = select_eligible(mode, acc_row(v, h), 32 * t + r, dcr, nr, nc) ? acc[t][v] : __builtin_nanf("");
+    }
+    bool any = false;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) any |= acc[t][v] >= thr;
+    if (__ballot(any) != 0) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)                                    // columns 0..31 of the tile, then 32..63
+          select_take<32, FILL>(p, run[v], acc[t][v] >= thr, acc[t][v], static_cast<int>(tcol0) + 32 * t + r,
+                                rp + ((v & 3) + 8 * (v >> 2)), lane);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (!FILL) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int64_t row = wrow0 + acc_row(v, h);
+      if (r == 0 && row < p.n_head) p.row_counts[l * p.n_head + row] = static_cast<int>(run[v]);
+    }
+  }
+}
+
+// ---- bf16 / f16: bilinear_rowstats16_kernel (v_mfma_f32_16x16x32, 64 rows per wave) with the selecting epilogue -----------------
+typedef __attribute__((ext_vector_type(4))) float f32x4v;
+
+template <int MODE>
+__device__ __forceinline__ f32x4v select_mma16x16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
+  if constexpr (MODE == MDG_PREC_F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+template <int MODE, bool FILL>
+__global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectArgs p) {
+  static_assert(kSingle16<MODE>, "one rounded 16-bit product per k step");
+  constexpr int NW = 8, BM = 512;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const buf0 = smem;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5, c16 = lane & 15, g4 = lane >> 4;
+  const int64_t l = blockIdx.y;
+  const int64_t rbk = p.eligible == MDG_TOPK_LOWER ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const int64_t row0 = rbk * BM;
+  const float thr = p.thr[l];
+  // ---- prologue: T = z_head[rows] . W_sym[l] (32x32x16 products, as every other path), re-laid out for 16x16x32 ----
+  bf16x8 A16[4][4];                                  // [row tile of 16][k step of 32]: lane (c16, g4) holds row c16, k = 32 ks + 8 g4 ..+7
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb) {
+    AFrag<MODE> Az;
+    int64_t zr = row0 + (wave * 2 + rb) * 32 + r;
+    zr = zr < p.n_head ? zr : p.n_head - 1;
+    afrag_from_global<MODE>(Az, p.z_head + zr * D, h);
+    TileSrc ws = p.w;
+    ws.hi += l * D * D;
+    char* const slab = smem + wave * 8192;             // [32 rows][64 cols] fp32, chunk-swizzled
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      u32x4 regs[32 / NW];
+      stage_load<MODE, NW>(ws, 64 * st, tid, regs);
+      __syncthreads();
+      stage_write<MODE, NW>(buf0, tid, regs);
+      __syncthreads();
+      f32x16 acc[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+      compute_tile<MODE>(Az, buf0, r, h, acc);
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const int row = acc_row(v, h), n = 32 * t + r;
+          *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[t][v];
+        }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int rt2 = 0; rt2 < 2; ++rt2)
+#pragma unroll
+        for (int ksl = 0; ksl < 2; ++ksl) {
+          const int row = 16 * rt2 + c16, chunk = (32 * ksl + 8 * g4) >> 2;         // 4-float chunks of the 64-column half
+          const float4 v0 = *reinterpret_cast<const float4*>(slab + tile_off<256>(row, chunk));
+          const float4 v1 = *reinterpret_cast<const float4*>(slab + tile_off<256>(row, chunk + 1));
+          bf16x8 hi, lo;
+          split8<MODE>(v0, v1, hi, lo);
+          A16[2 * rb + rt2][2 * st + ksl] = hi;
+        }
+    }
+    __syncthreads();
+  }
+  // ---- sweep ----
+  const int nst = select_tiles(p, row0, BM);
+  const int64_t wrow0 = row0 + wave * 64;            // this wave's rows: wrow0 .. wrow0 + 63
+  const int mode = p.eligible;
+  unsigned run[16];                                  // hits so far of row 16 rt + 4 g4 + i: counter 4 rt + i
+  const long long* const rp = p.row_ptr + (l * p.n_head + wrow0 + 4 * g4);     // row 16 rt + 4 g4 + i: rp[16 * rt + i]
+#pragma unroll
+  for (int q = 0; q < 16; ++q) run[q] = 0u;
+  stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  int cur = 0;
+  for (int s = 0; s < nst; ++s) {
+    const int64_t tcol0 = static_cast<int64_t>(s) * BN;
+    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // = LDS-DMA instructions per wave and tile: tile s landed, tile s+1 stays in flight
+    __builtin_amdgcn_s_barrier();
+    const int nxt2 = cur == 0 ? 2 : cur - 1;
+    const int s2 = s + 2 < nst ? s + 2 : nst - 1;
+    stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    const char* lds = smem + cur * STAGE_BYTES;
+    cur = cur == 2 ? 0 : cur + 1;
+    if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 63) continue;       // wave-uniform: nothing below the diagonal for my rows
+    const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 64 <= p.n_head &&
+                       (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 63));
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {                                   // 16-column sub-tiles in ascending order
+      f32x4v acc[4];
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8 b = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(16 * ct + c16, 4 * ks + g4));
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = select_mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
+      }
+      const int col = static_cast<int>(tcol0) + 16 * ct + c16;
+      if (!plain) {
+        const int dcr = select_clamp(tcol0 - wrow0), nr = select_clamp(p.n_head - wrow0), nc = select_clamp(p.n_tail - tcol0);
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            acc[rt][i] = select_eligible(mode, 16 * rt + 4 * g4 + i, 16 * ct + c16, dcr, nr, nc) ? acc[rt][i] : __builtin_nanf("");
+      }
+      bool any = false;
+#pragma unroll
+      for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) any |= acc[rt][i] >= thr;
+      if (__ballot(any) != 0) {
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            select_take<16, FILL>(p, run[4 * rt + i], acc[rt][i] >= thr, acc[rt][i], col, rp + (16 * rt + i), lane);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (!FILL) {
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t row = wrow0 + 16 * rt + 4 * g4 + i;
+        if (c16 == 0 && row < p.n_head) p.row_counts[l * p.n_head + row] = static_cast<int>(run[4 * rt + i]);
+      }
+  }
+}
+
+// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
+template <int MODE>
+__global__ void select_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float4 v = reinterpret_cast<const float4*>(x)[i];
+  const float f[4] = {v.x, v.y, v.z, v.w};
+  if constexpr (MODE == MDG_PREC_F16) {
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+    f16x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
+    reinterpret_cast<f16x4*>(hi)[i] = o;
+  } else {
+    bf16x4 hv, lw;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      __bf16 a, b;
+      mdg_split_bf16(f[c], a, b);
+      hv[c] = a;
+      lw[c] = b;
+    }
+    reinterpret_cast<bf16x4*>(hi)[i] = hv;
+    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
+  }
+}
+
+inline size_t select_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+template <int MODE, bool FILL>
+int launch_select(SelectArgs& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st, const char* fn) {
+  if constexpr (MODE == MDG_PREC_F32) {
+    a.zt.f32 = z_tail;
+    a.w.f32 = w_sym;
+  } else {
+    const size_t zb = select_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = select_align256(static_cast<size_t>(n_labels) * D * D * 2);
+    const bool x3 = MODE == MDG_PREC_BF16X3;
+    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
+    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
+    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
+    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
+    const int64_t z4 = a.n_tail * D / 4, w4 = n_labels * D * D / 4;
+    hipLaunchKernelGGL(select_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
+    hipLaunchKernelGGL(select_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
+    MDG_CHECK_LAUNCH(fn);
+    a.zt.hi = zhi; a.zt.lo = zlo;
+    a.w.hi = whi; a.w.lo = wlo;
+  }
+  if constexpr (kSingle16<MODE>) {
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
+    hipLaunchKernelGGL((bilinear_select16_kernel<MODE, FILL>), grid, dim3(512), 3 * STAGE_BYTES, st, a);
+  } else {
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
+    hipLaunchKernelGGL((bilinear_select_kernel<MODE, FILL>), grid, dim3(512), 3 * STAGE_BYTES, st, a);
+  }
+  MDG_CHECK_LAUNCH(fn);
+  return MDG_OK;
+}
+
+// The checks both entry points share; `outputs`: none of the pass's own pointers is null.  Returns MDG_OK with *launch = false
+// when there is nothing to do.
+int select_check(const char* fn, const float* z_head, const float* z_tail, const float* w_sym, const float* thr, bool outputs, int64_t n_head,
+                 int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible, void* workspace, size_t workspace_bytes,
+                 bool* launch) {
+  *launch = false;
+  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || eligible == MDG_TOPK_NOT_SELF || eligible == MDG_TOPK_LOWER, "%s: unknown eligible mode %d", fn,
+                eligible);
+  MDG_CHECK_ARG(n_head >= 0 && n_tail >= 0 && n_labels >= 0, "%s: negative size", fn);
+  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail,
+                "%s: eligible NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)", fn, (long long)n_head,
+                (long long)n_tail);
+  MDG_CHECK_ARG(D_ == D, "%s: D must be %d (got %lld)", fn, D, (long long)D_);
+  MDG_CHECK_ARG(n_labels <= 65535, "%s: n_labels %lld > 65535 per call", fn, (long long)n_labels);
+  MDG_CHECK_ARG(n_tail < (int64_t(1) << 31) - BN, "%s: n_tail %lld does not fit the int32 column indices", fn, (long long)n_tail);
+  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16 || precision == MDG_PREC_F16,
+                "%s: unknown precision %d", fn, precision);
+  if (n_head == 0 || n_labels == 0) return MDG_OK;
+  MDG_CHECK_ARG(n_tail >= 1, "%s: n_tail must be at least 1", fn);
+  MDG_CHECK_ARG(z_head && z_tail && w_sym && thr && outputs, "%s: null pointer", fn);
+  MDG_CHECK_ARG(mdg_aligned16(z_head) && mdg_aligned16(z_tail) && mdg_aligned16(w_sym), "%s: z_head, z_tail and w_sym must be 16-byte aligned", fn);
+  const size_t need = mdg_bilinear_select_workspace_bytes(n_head, n_tail, n_labels, D_, precision);
+  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
+    mdg_set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", fn, need, workspace_bytes);
+    return MDG_EWORKSPACE;
+  }
+  *launch = true;
+  return MDG_OK;
+}
+
+template <bool FILL>
+int select_dispatch(SelectArgs& a, const float* z_tail, const float* w_sym, int64_t n_labels, int precision, void* workspace, void* stream,
+                    const char* fn) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(workspace);
+  switch (precision) {
+    case MDG_PREC_F32: return launch_select<MDG_PREC_F32, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    case MDG_PREC_BF16X3: return launch_select<MDG_PREC_BF16X3, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    case MDG_PREC_BF16: return launch_select<MDG_PREC_BF16, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    default: return launch_select<MDG_PREC_F16, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
+  }
+}
+
+}  // namespace
+
+extern "C" size_t mdg_bilinear_select_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision) {
+  (void)n_head;
+  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
+  const size_t z = select_align256(static_cast<size_t>(n_tail) * D_ * 2), w = select_align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
+  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+}
+
+extern "C" int mdg_bilinear_select_count(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
+                                         int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  bool launch;
+  const int rc = select_check("mdg_bilinear_select_count", z_head, z_tail, w_sym, thr, row_counts != nullptr, n_head, n_tail, n_labels, D_,
+                              precision, eligible, workspace, workspace_bytes, &launch);
+  if (rc != MDG_OK || !launch) return rc;
+  SelectArgs a{};
+  a.z_head = z_head;
+  a.thr = thr;
+  a.row_counts = row_counts;
+  a.n_head = n_head; a.n_tail = n_tail;
+  a.eligible = eligible;
+  a.zt.nrows = n_tail;
+  a.w.nrows = D;
+  return select_dispatch<false>(a, z_tail, w_sym, n_labels, precision, workspace, stream, "mdg_bilinear_select_count");
+}
+
+extern "C" int mdg_bilinear_select_fill(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const int64_t* row_ptr,
+                                        int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_,
+                                        int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream) {
+  bool launch;
+  const int rc = select_check("mdg_bilinear_select_fill", z_head, z_tail, w_sym, thr, row_ptr && cols && vals, n_head, n_tail, n_labels, D_,
+                              precision, eligible, workspace, workspace_bytes, &launch);
+  if (rc != MDG_OK || !launch) return rc;
+  SelectArgs a{};
+  a.z_head = z_head;
+  a.thr = thr;
+  a.row_ptr = reinterpret_cast<const long long*>(row_ptr);
+  a.cols = cols;
+  a.vals = vals;
+  a.n_head = n_head; a.n_tail = n_tail;
+  a.eligible = eligible;
+  a.zt.nrows = n_tail;
+  a.w.nrows = D;
+  return select_dispatch<true>(a, z_tail, w_sym, n_labels, precision, workspace, stream, "mdg_bilinear_select_fill");
+}

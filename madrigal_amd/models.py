@@ -1697,6 +1697,29 @@ class BilinearDDIScorer(nn.Bilinear):
             w = w[label_range[0]:label_range[1]]
         return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"])
 
+    def select_count(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all"):
+        """Extension (screening): int32 [L', n1] -- per outcome and row of ``input1`` the number of eligible scores of
+        ``forward(input1, input2, label_range)`` at or above ``thresholds`` [L'], in the precision ``forward`` uses; nothing of
+        [L', n1, n2] is materialised (``ops.bilinear_select_count``).  Inference only."""
+        ops.forward_only(input1, input2)
+        w = self.symmetric_weight()
+        if label_range is not None:
+            assert len(label_range) == 2
+            w = w[label_range[0]:label_range[1]]
+        return ops.bilinear_select_count(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"])
+
+    def select(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", max_bytes: int = 1 << 30):
+        """Extension (screening): ``(row_ptr int64 [L' * n1 + 1], cols int32 [T], vals fp32 [T])`` -- every eligible entry of
+        ``forward(input1, input2, label_range)`` at or above ``thresholds`` [L'] as CSR over the rows (outcome, row of ``input1``),
+        columns ascending: ``torch.nonzero`` of the dense mask, in the precision ``forward`` uses; nothing of [L', n1, n2] is
+        materialised (``ops.bilinear_select``).  Inference only."""
+        ops.forward_only(input1, input2)
+        w = self.symmetric_weight()
+        if label_range is not None:
+            assert len(label_range) == 2
+            w = w[label_range[0]:label_range[1]]
+        return ops.bilinear_select(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"], max_bytes=max_bytes)
+
     def score_triples(self, input1, input2, plan: dict) -> torch.Tensor:
         """Extension (finetune step): scores of the plan's (label, head, tail) triples only, in the plan's
         label-sorted order, differentiable w.r.t. both embeddings and the weight (train_ddi_batch.py:285-286

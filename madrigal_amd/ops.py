@@ -252,7 +252,109 @@ def bilinear_bincount(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
     return counts
 
 
-ENSEMBLE_PRECISIONS = {"f32": PREC_F32, "bf16x3": PREC_BF16X3}
+_SELECT_NAN = "thresholds: NaN (use -inf to select every eligible pair, +inf to select none)"
+
+
+def _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=True):
+    """Validation shared by ``bilinear_select_count`` and ``bilinear_select``: shapes and threshold values first (on whatever device the
+    tensors live), then the device -> (zh, zt, w, thr, precision code).  ``nan_check_on_device=False``: the caller reads the NaN flag of
+    GPU thresholds itself, together with another value (one synchronisation instead of two)."""
+    for t, name, nd in ((z_head, "z_head", 2), (z_tail, "z_tail", 2), (w_sym, "w_sym", 3), (thresholds, "thresholds", 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    forward_only(z_head, z_tail, w_sym, thresholds)
+    D = z_head.shape[1]
+    if z_tail.shape[1] != D or w_sym.shape[1] != D or w_sym.shape[2] != D:
+        raise ValueError(f"feature dims disagree: z_head {tuple(z_head.shape)}, z_tail {tuple(z_tail.shape)}, w {tuple(w_sym.shape)}")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
+    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    L, Nh, Nt = w_sym.shape[0], z_head.shape[0], z_tail.shape[0]
+    if thresholds.shape[0] != L:
+        raise ValueError(f"thresholds: expected [{L}] (one cut per outcome), got {tuple(thresholds.shape)}")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    if Nt >= (1 << 31) - 64:
+        raise ValueError(f"z_tail: {Nt} rows do not fit the int32 column indices")
+    if L and (nan_check_on_device or not thresholds.is_cuda) and bool(torch.isnan(thresholds).any()):
+        raise ValueError(_SELECT_NAN)
+    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
+    thr = _f32_cuda(thresholds, "thresholds", 1)
+    if zh.device != zt.device or zh.device != w.device or zh.device != thr.device:
+        raise ValueError("z_head, z_tail, w_sym and thresholds must be on the same device")
+    return zh, zt, w, thr, prec
+
+
+def _select_count(zh, zt, w, thr, prec, eligible) -> torch.Tensor:
+    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
+    counts = torch.empty((L, Nh), dtype=torch.int32, device=zh.device)
+    if counts.numel() == 0:
+        return counts
+    if Nt == 0:                                  # no column at all
+        return counts.zero_()
+    # the grid's y extent caps one call at 65535 outcomes; chunk above that
+    for lo in range(0, L, 65535):
+        hi = min(L, lo + 65535)
+        ws, nbytes = _scratch("mdg_bilinear_select_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
+        call("mdg_bilinear_select_count", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4,
+             counts.data_ptr() + lo * Nh * 4, Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+    return counts
+
+
+def bilinear_select_count(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, thresholds: torch.Tensor, *,
+                          eligible: str = "all", precision="bf16x3") -> torch.Tensor:
+    """Per-row sizes of ``bilinear_select`` -> int32 [L, Nh]: ``counts[l, i]`` is the number of eligible tail columns j with
+    ``S[l,i,j] >= thresholds[l]``, counted inside the all-pairs sweep (nothing of [L,Nh,Nt] is materialised).  With one drug set and
+    ``eligible="not_self"`` this is the degree of drug i in the outcome's predicted network.  ``thresholds``: fp32 [L], no NaN;
+    ``-inf`` counts every eligible column, ``+inf`` none.  ``eligible`` and the score arithmetic are those of ``bilinear_topk``.
+    Deterministic: no atomics."""
+    zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision)
+    return _select_count(zh, zt, w, thr, prec, eligible)
+
+
+def bilinear_select(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, thresholds: torch.Tensor, *, eligible: str = "all",
+                    precision="bf16x3", max_bytes: int = 1 << 30):
+    """Every eligible pair at or above a per-outcome cut, as CSR -> ``(row_ptr int64 [L*Nh + 1], cols int32 [T], vals fp32 [T])``:
+    row ``l * Nh + i`` holds, at ``[row_ptr[r], row_ptr[r + 1])``, the tail columns j with ``S[l,i,j] >= thresholds[l]`` in ascending
+    order and those scores.  This is ``torch.nonzero((S >= thresholds[:, None, None]) & eligible_mask)`` of the dense scores, in that
+    order, with nothing of [L,Nh,Nt] materialised: a counting sweep (``bilinear_select_count``), ``torch.cumsum``, one host read of the
+    total ``T`` to size the result (the thresholds' NaN flag travels with it) -- the only synchronisation -- and a filling sweep.
+
+    ``thresholds``: fp32 [L], no NaN; ``-inf`` selects every eligible pair, ``+inf`` none; the rule is ``>=``, so a cut at the K-th
+    best value (``top_pairs``) includes that value, and an edge of ``score_histogram`` selects the bins at and above it.
+    ``eligible`` and the score arithmetic are those of ``bilinear_topk`` ("f32" / "bf16x3": the general sweep's scores bit for bit;
+    "bf16" / "f16": the row-statistics sweep, <= 2e-6 of the scale).  ``max_bytes``: if the result's 8 T bytes exceed it a ValueError
+    naming ``T`` is raised before anything is allocated or filled.  Deterministic: no atomics; bit-identical from call to call."""
+    zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False)
+    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
+    counts = _select_count(zh, zt, w, thr, prec, eligible)          # (a NaN cut selects nothing: harmless until it is refused below)
+    row_ptr = torch.zeros(L * Nh + 1, dtype=torch.int64, device=zh.device)
+    T = 0
+    if L:
+        row_ptr[1:] = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+        T, bad = torch.stack([row_ptr[-1], torch.isnan(thr).any().to(torch.int64)]).tolist()          # the one host read
+        if bad:
+            raise ValueError(_SELECT_NAN)
+    if 8 * T > int(max_bytes):
+        raise ValueError(f"bilinear_select: T = {T} selected pairs need {8 * T} bytes, more than max_bytes = {int(max_bytes)}; "
+                         "raise the thresholds, pass fewer outcomes per call, or raise max_bytes")
+    cols = torch.empty(T, dtype=torch.int32, device=zh.device)
+    vals = torch.empty(T, dtype=torch.float32, device=zh.device)
+    if T == 0:
+        return row_ptr, cols, vals
+    for lo in range(0, L, 65535):
+        hi = min(L, lo + 65535)
+        ws, nbytes = _scratch("mdg_bilinear_select_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
+        call("mdg_bilinear_select_fill", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4,
+             row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols), _ptr(vals), Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes,
+             _stream(zh))
+    return row_ptr, cols, vals
+
+
+ENSEMBLE_PRECISIONS ={"f32": PREC_F32, "bf16x3": PREC_BF16X3}
 
 
 def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -337,6 +337,79 @@ def score_histogram(model, z: torch.Tensor, edges: torch.Tensor, label_range: Op
     return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible)
 
 
+def _cuts(thresholds, n_out: int, device) -> torch.Tensor:
+    """fp32 [L'] on ``device`` from a number (one cut for every outcome) or one cut per outcome."""
+    t = torch.as_tensor(thresholds, dtype=torch.float32, device=device)
+    if t.dim() == 0:
+        t = t.expand(n_out)
+    if t.dim() != 1 or t.shape[0] != n_out:
+        raise ValueError(f"thresholds: expected a number or [{n_out}] (one cut per outcome), got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def csr_rows(row_ptr: torch.Tensor, n_head: int, total: Optional[int] = None):
+    """The (outcome, head) of every entry of a CSR over ``L * n_head`` rows numbered ``l * n_head + i`` (``ops.bilinear_select``'s
+    ``row_ptr``, int64 [L * n_head + 1]) -> ``(outcome int64 [T], head int64 [T], offsets int64 [L + 1])``; ``offsets[l]`` is where
+    outcome l's entries begin (``row_ptr[l * n_head]``).  Empty rows and empty outcomes contribute nothing.  ``total``: T =
+    ``row_ptr[-1]`` where the caller knows it (on a GPU the expansion then needs no host read).  A pure tensor function (CPU or GPU)."""
+    if row_ptr.dim() != 1 or row_ptr.numel() < 1 or n_head < 0 or (n_head == 0 and row_ptr.numel() != 1) or \
+            (n_head > 0 and (row_ptr.numel() - 1) % n_head):
+        raise ValueError(f"row_ptr: expected [L * {n_head} + 1], got {tuple(row_ptr.shape)}")
+    rp = row_ptr.to(torch.int64)
+    n_rows = rp.numel() - 1
+    rows = torch.repeat_interleave(torch.arange(n_rows, device=rp.device), rp[1:] - rp[:-1], output_size=total)
+    if n_head == 0:
+        return rows, rows.clone(), rp.clone()
+    return rows // n_head, rows % n_head, rp[::n_head].clone()
+
+
+@torch.no_grad()
+def partner_counts(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """How many partners j != i of every drug score at or above the outcome's cut -> int32 [L', N]: ``counts[l, i]`` =
+    #{j != i : S[l, i, j] >= thresholds[l]}, the degree of drug i in outcome l's predicted interaction network, counted inside the
+    sweep (``decoder.select_count``, ``not_self`` mode) -- no [L', N, N] tensor at any N.  ``thresholds``: a number or [L'], no NaN.
+    Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
+    lo, hi = _outcomes(model, label_range)
+    return model.decoder.select_count(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self")
+
+
+@torch.no_grad()
+def partners_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30):
+    """ALL partners of every drug at or above the outcome's cut, as CSR -> ``(row_ptr int64 [L' * N + 1], cols int32 [T], vals fp32
+    [T])``: row ``l * N + i`` lists the j != i with S[l, i, j] >= thresholds[l] in ascending order and those scores (``decoder.select``,
+    ``not_self`` mode; ``csr_rows(row_ptr, N)`` gives every entry's outcome and drug).  Where ``top_partners`` returns the k best of a
+    drug, this returns its whole neighbourhood in the predicted network; every unordered pair appears from both sides, with
+    S[l, i, j] and S[l, j, i] (equal up to the last bits).  The result's size is known only after the counting sweep: more than
+    ``max_bytes`` (8 bytes per entry) raises a ValueError naming the size.  ``thresholds``: a number or [L'], no NaN."""
+    lo, hi = _outcomes(model, label_range)
+    return model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self", max_bytes=max_bytes)
+
+
+@torch.no_grad()
+def pairs_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30):
+    """ALL unordered drug pairs of every outcome that score at or above its cut -- the outcome's predicted interaction network --
+    -> ``(offsets int64 [L' + 1], head int64 [T], tail int64 [T], vals fp32 [T])``: outcome l owns the entries
+    ``offsets[l]:offsets[l + 1]``.  The pair {i, j} is scored as S[l, i, j] with i > j, the strict-lower-triangle entry ``top_pairs``,
+    ``pair_ranks`` and the rank normalisation use (notebooks/normalize_scores.py:39-46), and is selected when that score is
+    ``>= thresholds[l]``; the entries are ordered by (outcome, head, tail) ascending.  Nothing of [L', N, N] is materialised
+    (``decoder.select``, ``lower`` mode: a counting and a filling sweep); ``head`` is expanded from the sweep's row pointers
+    (``csr_rows``).  More than ``max_bytes`` (8 bytes per pair in the sweep's result) raises a ValueError naming the size.
+
+    Where a cut comes from (``thresholds``: a number or [L'], no NaN):
+      * the K-th value of ``top_pairs``: ``pairs_above(model, z, top_pairs(model, z, K)[0][:, -1])`` holds those K pairs and every
+        pair tied with the last of them (the rule is ``>=``);
+      * an edge of ``score_histogram``: the pairs of the bins at and above it, whose number the histogram already told.
+    ``normalized_ranks_of(model, z, vals)`` -- per outcome, e.g. on ``vals[offsets[l]:offsets[l + 1]][None, :]`` with
+    ``label_range=(l, l + 1)`` -- gives the normalised ranks of what was selected.
+    Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
+    lo, hi = _outcomes(model, label_range)
+    row_ptr, cols, vals = model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="lower", max_bytes=max_bytes)
+    _, head, offsets = csr_rows(row_ptr, z.shape[0], total=int(cols.numel()))
+    if z.shape[0] == 0:
+        offsets = torch.zeros(hi - lo + 1, dtype=torch.int64, device=z.device)
+    return offsets, head, cols.long(), vals
+
+
 @torch.no_grad()
 def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """For every query ``scores[l, q]`` the number of strict-lower-triangle pairs (i > j) of outcome l that score strictly less
