@@ -200,6 +200,40 @@ int mdg_bilinear_select_fill(const float* z_head, const float* z_tail, const flo
                              int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D,
                              int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Known-pair exclusion masks for the in-sweep products (ABI 16).  A screening run looks for NEW interactions: the pairs already
+ * in the training network score highest by construction and would fill the 32-entry lists of mdg_bilinear_topk; with the dense
+ * tensor the reference's users index them away, without the tensor the restriction has to act inside the sweep.
+ *   Layout: mask [planes][ceil(n_head / 32)][ld] 32-bit words, ld = mdg_pair_mask_ld(n_tail) = n_tail rounded up to 64; the word at
+ *   [p][i >> 5][j] holds the bit of head row i and tail column j at position i & 31.  A SET bit means "(i, j) is not eligible".
+ *   mdg_pair_mask_plane_words(n_head, n_tail) = ceil(n_head / 32) * ld is the size of one plane.  These two functions are the only
+ *   place the arithmetic lives.  Bits of pad columns [n_tail, ld) and of pad rows [n_head, 32 ceil(n_head / 32)) are ignored.
+ *   mdg_pair_mask_set: ORs the bits of n_pairs listed pairs (heads[q], tails[q]) into plane planes[q] (planes == NULL: plane 0)
+ *   of a mask the CALLER has zeroed (or that already holds bits: the call only adds); symmetric != 0 also sets (tails[q], heads[q])
+ *   and needs n_head == n_tail.  One thread per pair, one integer atomic OR per bit: duplicates and order do not matter, the
+ *   result is deterministic.  A pair with an index outside [0,n_head) x [0,n_tail) x [0,n_planes) is skipped, never stored.
+ *   The *_masked entry points take the arguments of their twins plus `mask` (device, 4-byte aligned) and `plane_stride`, the
+ *   distance in words between the planes of consecutive outcomes of THIS call: 0 shares one plane between all outcomes, otherwise
+ *   >= mdg_pair_mask_plane_words.  An element is eligible when `eligible` allows it AND its bit is clear; an excluded element is
+ *   treated exactly like an ineligible one (top-k: never kept, padding -inf / -1 when fewer than k remain; select: never counted
+ *   or stored), so order, tie rule, CSR order, bounded writes and determinism are those of the twins, and the scores that remain
+ *   are bit for bit the twins'.  mask == NULL forwards to the twin.  The kernels read words [0, ceil(n_head/32)) x [0, ld) of a
+ *   plane and nothing else.  Workspace: the twin's query.  mdg_bilinear_bincount takes no mask: a normalised rank is defined over
+ *   all N (N - 1) / 2 pairs (notebooks/normalize_scores.py:57). */
+int64_t mdg_pair_mask_ld(int64_t n_tail);
+int64_t mdg_pair_mask_plane_words(int64_t n_head, int64_t n_tail);
+int mdg_pair_mask_set(uint32_t* mask, int64_t n_planes, int64_t n_head, int64_t n_tail, const int64_t* heads, const int64_t* tails,
+                      const int64_t* planes, int64_t n_pairs, int symmetric, void* stream);
+int mdg_bilinear_topk_masked(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx, int64_t n_head,
+                             int64_t n_tail, int64_t n_labels, int64_t D, int precision, int k, int eligible, void* workspace,
+                             size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
+int mdg_bilinear_select_count_masked(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
+                                     int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision, int eligible,
+                                     void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
+int mdg_bilinear_select_fill_masked(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const int64_t* row_ptr,
+                                    int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D,
+                                    int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream,
+                                    const uint32_t* mask, int64_t plane_stride);
+
 /* ------------------------------------------------------------------------ dense blocks ---- */
 
 /* Y = alpha * act( (X W^T + bias) * scale + shift ) + beta * R      X [M,K] ldx, W [N,K] ldw (nn.Linear

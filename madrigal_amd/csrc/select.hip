@@ -38,7 +38,11 @@
 // All slot arithmetic is 64-bit (row_ptr int64, `run` < n_tail < 2^31 widened before the add).
 // Ineligible elements (and rows past n_head) become NaN, which fails `x >= thr` for every thr, -inf included; for the same
 // reason a NaN score is never selected.
-#include "bilinear_tiles.h"
+// MASKED instantiations (mdg_bilinear_select_*_masked): a known-pair exclusion bitmap (pairmask.hip) on top of
+// `eligible`; a set bit makes its element NaN like an ineligible one, in both passes alike, so order, bounded writes and
+// determinism are those described above.  The words of a tile reach LDS by one or two more LDS-DMAs in the tile's group
+// (pairmask.h); the MASKED = false kernels are what they were.
+#include "pairmask.h"
 
 namespace {
 
@@ -54,6 +58,15 @@ struct SelectArgs {
   int64_t n_head, n_tail;
   int eligible;               // mdg_topk_eligible
 };
+
+// The kernel argument: SelectArgs itself, plus the exclusion mask in the MASKED instantiations (mdg_bilinear_select_*_masked).
+template <bool MASKED> struct SelectKArgs : SelectArgs {};
+template <> struct SelectKArgs<true> : SelectArgs { PairMask mask; };
+
+// LDS of a MASKED sweep behind the three stage buffers: per stage buffer and wave, NMW slots of 256 bytes -- the mask words of the
+// wave's row block(s) for the 64 columns of that buffer's tile (pairmask.h; the same arrangement as topk.hip).
+template <int NMW> constexpr int select_mask_stage = 8 * NMW * PAIRMASK_SLOT;
+template <bool MASKED, int NMW> constexpr int select_lds_bytes = 3 * STAGE_BYTES + (MASKED ? 3 * select_mask_stage<NMW> : 0);
 
 // Eligibility of the element in row wrow0 + lr, column tcol0 + lc of a tile (0 <= lr, lc < 64) from the tile's 32-bit distances
 // (wave-uniform, select_clamp-ed): dcr = tcol0 - wrow0, nr = n_head - wrow0, nc = n_tail - tcol0.  The same test as top-k's and
@@ -100,8 +113,12 @@ __device__ __forceinline__ void select_take(const SelectArgs& p, unsigned& run, 
 }
 
 // ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the selecting epilogue ---------------------------------------
-template <int MODE, bool FILL>
-__global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectArgs p) {
+// MASKED: an element is eligible when the mode allows it AND its bit of the exclusion mask is clear (it becomes NaN like every
+// ineligible element).  The 64 words [row block of the wave][columns of the tile] ride with the tile: one more LDS-DMA per wave and
+// tile group into a slot of the wave's own, so a group is NDMA + 1 = 5 instructions and the wait keeps 5 in flight.  Lane (r, h)
+// reads words r and 32 + r of the slot (its columns for t = 0, 1); its rows are bits acc_row(v, h) of them.
+template <int MODE, bool FILL, bool MASKED>
+__global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectKArgs<MASKED> p) {
   static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "32x32 sweep of the fp32-grade modes");
   constexpr int NW = 8, BM = 32 * NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -162,19 +179,33 @@ __global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectArg
   for (int v = 0; v < 16; ++v) run[v] = 0u;
   constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
   static_assert(NDMA == 4, "vmcnt immediate below");
+  // MASKED: the wave's mask slot of stage buffer b is mslot + b * select_mask_stage<1>; every group of DMAs below (tile + words) is
+  // issued together, so "the last group in flight" is 5 instructions instead of 4 and nothing else about the chain changes.  (The
+  // fill pass's stores and row_ptr reads are issued after a group and only make a wait stricter, as before.)
+  constexpr int MSTAGE = select_mask_stage<1>;
+  const char* const mslot = smem + 3 * STAGE_BYTES + wave * PAIRMASK_SLOT;
+  const unsigned* mplane = nullptr;
+  if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
   stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  if constexpr (MASKED) pairmask_dma(p.mask, mplane, wrow0 >> 5, 0, lane, lds_addr(mslot));
   stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  if constexpr (MASKED) pairmask_dma(p.mask, mplane, wrow0 >> 5, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, lane, lds_addr(mslot + MSTAGE));
   int cur = 0;
   for (int s = 0; s < nst; ++s) {
     const int64_t tcol0 = static_cast<int64_t>(s) * BN;
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = NDMA: tile s landed, tile s+1 stays in flight
+    if constexpr (MASKED) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");       // = NDMA + 1 mask DMA: group s landed, group s+1 stays in flight
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = NDMA: tile s landed, tile s+1 stays in flight
     __builtin_amdgcn_s_barrier();      // tile s landed for every wave; every wave finished reading tile s-1
     const int nxt2 = cur == 0 ? 2 : cur - 1;                           // (cur + 2) % 3 = buffer of tile s-1
     const int s2 = s + 2 < nst ? s + 2 : nst - 1;                      // past the end: a copy nobody consumes
     stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    if constexpr (MASKED) pairmask_dma(p.mask, mplane, wrow0 >> 5, static_cast<int64_t>(s2) * BN, lane, lds_addr(mslot + nxt2 * MSTAGE));
     const char* lds = smem + cur * STAGE_BYTES;
+    const char* const mcur = mslot + cur * MSTAGE;                     // this wave's words of tile s (its own DMA: landed with the wait above)
     cur = cur == 2 ? 0 : cur + 1;
     if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 31) continue;       // wave-uniform: no column of this tile is below any of my rows
+    unsigned w0 = 0u, w1 = 0u;                                          // MASKED: read ahead of the MFMAs, whose issue hides the LDS latency
+    if constexpr (MASKED) { w0 = pairmask_word(mcur, r); w1 = pairmask_word(mcur, 32 + r); }
     f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -191,6 +222,15 @@ __global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectArg
 #pragma unroll
         for (int v = 0; v < 16; ++v)
           acc[t][v] = select_eligible(mode, acc_row(v, h), 32 * t + r, dcr, nr, nc) ? acc[t][v] : __builtin_nanf("");
+    }
+    if constexpr (MASKED) {
+      if (__ballot((w0 | w1) != 0u) != 0) {                            // wave-uniform: a tile without a known pair costs two reads and this ballot
+        const unsigned mw[2] = {w0 >> (4 * h), w1 >> (4 * h)};         // bit acc_row(v, 0) of mw[t] <-> row acc_row(v, h)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[t][v] = pairmask_nan_if(acc[t][v], mw[t], acc_row(v, 0));
+      }
     }
     bool any = false;
 #pragma unroll
@@ -227,8 +267,11 @@ __device__ __forceinline__ f32x4v select_mma16x16(const bf16x8& a, const bf16x8&
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int MODE, bool FILL>
-__global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectArgs p) {
+// MASKED: as above; the wave's 64 rows are two row blocks of the mask, so two mask DMAs per tile group (2 + 2 = 4 in flight) and
+// two slots: lane (c16, g4) reads word 16 ct + c16 of each for sub-tile ct; row 16 rt + 4 g4 + i is bit 16 (rt & 1) + 4 g4 + i
+// of the word of row block rt >> 1.
+template <int MODE, bool FILL, bool MASKED>
+__global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectKArgs<MASKED> p) {
   static_assert(kSingle16<MODE>, "one rounded 16-bit product per k step");
   constexpr int NW = 8, BM = 512;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -294,21 +337,42 @@ __global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectA
   const long long* const rp = p.row_ptr + (l * p.n_head + wrow0 + 4 * g4);     // row 16 rt + 4 g4 + i: rp[16 * rt + i]
 #pragma unroll
   for (int q = 0; q < 16; ++q) run[q] = 0u;
+  constexpr int MSTAGE = select_mask_stage<2>;
+  const char* const mslot = smem + 3 * STAGE_BYTES + wave * 2 * PAIRMASK_SLOT;
+  const unsigned* mplane = nullptr;
+  if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
+  auto mask_dma = [&](int64_t col0, const char* slot) {               // the group's two mask DMAs: row blocks wrow0 / 32 and + 1
+    if constexpr (MASKED) {
+      pairmask_dma(p.mask, mplane, wrow0 >> 5, col0, lane, lds_addr(slot));
+      pairmask_dma(p.mask, mplane, (wrow0 >> 5) + 1, col0, lane, lds_addr(slot + PAIRMASK_SLOT));
+    }
+  };
   stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  if constexpr (MASKED) mask_dma(0, mslot);
   stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  if constexpr (MASKED) mask_dma(static_cast<int64_t>(1 < nst ? 1 : 0) * BN, mslot + MSTAGE);
   int cur = 0;
   for (int s = 0; s < nst; ++s) {
     const int64_t tcol0 = static_cast<int64_t>(s) * BN;
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // = LDS-DMA instructions per wave and tile: tile s landed, tile s+1 stays in flight
+    if constexpr (MASKED) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = 2 tile + 2 mask DMAs per group: group s landed, group s+1 stays in flight
+    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // = LDS-DMA instructions per wave and tile: tile s landed, tile s+1 stays in flight
     __builtin_amdgcn_s_barrier();
     const int nxt2 = cur == 0 ? 2 : cur - 1;
     const int s2 = s + 2 < nst ? s + 2 : nst - 1;
     stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    if constexpr (MASKED) mask_dma(static_cast<int64_t>(s2) * BN, mslot + nxt2 * MSTAGE);
     const char* lds = smem + cur * STAGE_BYTES;
+    const char* const mcur = mslot + cur * MSTAGE;                     // this wave's words of tile s (its own DMAs: landed with the wait above)
     cur = cur == 2 ? 0 : cur + 1;
     if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 63) continue;       // wave-uniform: nothing below the diagonal for my rows
     const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 64 <= p.n_head &&
                        (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 63));
+    unsigned mwd[4][2];                                                // MASKED: the tile's eight words, read ahead of the MFMAs that hide the LDS latency
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      mwd[ct][0] = mwd[ct][1] = 0u;
+      if constexpr (MASKED) { mwd[ct][0] = pairmask_word(mcur, 16 * ct + c16); mwd[ct][1] = pairmask_word(mcur + PAIRMASK_SLOT, 16 * ct + c16); }
+    }
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {                                   // 16-column sub-tiles in ascending order
       f32x4v acc[4];
@@ -328,6 +392,15 @@ __global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectA
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             acc[rt][i] = select_eligible(mode, 16 * rt + 4 * g4 + i, 16 * ct + c16, dcr, nr, nc) ? acc[rt][i] : __builtin_nanf("");
+      }
+      if constexpr (MASKED) {
+        if (__ballot((mwd[ct][0] | mwd[ct][1]) != 0u) != 0) {           // wave-uniform, per 16-column sub-tile
+          const unsigned mw[2] = {mwd[ct][0] >> (4 * g4), mwd[ct][1] >> (4 * g4)};
+#pragma unroll
+          for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[rt][i] = pairmask_nan_if(acc[rt][i], mw[rt >> 1], 16 * (rt & 1) + i);
+        }
       }
       bool any = false;
 #pragma unroll
@@ -384,8 +457,8 @@ __global__ void select_images_kernel(const float* __restrict__ x, __bf16* __rest
 
 inline size_t select_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
-template <int MODE, bool FILL>
-int launch_select(SelectArgs& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st, const char* fn) {
+template <int MODE, bool FILL, bool MASKED>
+int launch_select(SelectKArgs<MASKED>& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st, const char* fn) {
   if constexpr (MODE == MDG_PREC_F32) {
     a.zt.f32 = z_tail;
     a.w.f32 = w_sym;
@@ -403,12 +476,22 @@ int launch_select(SelectArgs& a, const float* z_tail, const float* w_sym, int64_
     a.zt.hi = zhi; a.zt.lo = zlo;
     a.w.hi = whi; a.w.lo = wlo;
   }
+  if constexpr (MASKED) {                         // more dynamic LDS than the unmasked sweeps use: raise the kernel's limit once
+    static bool attr_done = false;
+    if (!attr_done) {
+      if constexpr (kSingle16<MODE>)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_select16_kernel<MODE, FILL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, select_lds_bytes<true, 2>);
+      else
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_select_kernel<MODE, FILL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, select_lds_bytes<true, 1>);
+      attr_done = true;
+    }
+  }
   if constexpr (kSingle16<MODE>) {
     const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_select16_kernel<MODE, FILL>), grid, dim3(512), 3 * STAGE_BYTES, st, a);
+    hipLaunchKernelGGL((bilinear_select16_kernel<MODE, FILL, MASKED>), grid, dim3(512), (select_lds_bytes<MASKED, 2>), st, a);
   } else {
     const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_select_kernel<MODE, FILL>), grid, dim3(512), 3 * STAGE_BYTES, st, a);
+    hipLaunchKernelGGL((bilinear_select_kernel<MODE, FILL, MASKED>), grid, dim3(512), (select_lds_bytes<MASKED, 1>), st, a);
   }
   MDG_CHECK_LAUNCH(fn);
   return MDG_OK;
@@ -444,16 +527,16 @@ int select_check(const char* fn, const float* z_head, const float* z_tail, const
   return MDG_OK;
 }
 
-template <bool FILL>
-int select_dispatch(SelectArgs& a, const float* z_tail, const float* w_sym, int64_t n_labels, int precision, void* workspace, void* stream,
+template <bool FILL, bool MASKED>
+int select_dispatch(SelectKArgs<MASKED>& a, const float* z_tail, const float* w_sym, int64_t n_labels, int precision, void* workspace, void* stream,
                     const char* fn) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(workspace);
   switch (precision) {
-    case MDG_PREC_F32: return launch_select<MDG_PREC_F32, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
-    case MDG_PREC_BF16X3: return launch_select<MDG_PREC_BF16X3, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
-    case MDG_PREC_BF16: return launch_select<MDG_PREC_BF16, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
-    default: return launch_select<MDG_PREC_F16, FILL>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    case MDG_PREC_F32: return launch_select<MDG_PREC_F32, FILL, MASKED>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    case MDG_PREC_BF16X3: return launch_select<MDG_PREC_BF16X3, FILL, MASKED>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    case MDG_PREC_BF16: return launch_select<MDG_PREC_BF16, FILL, MASKED>(a, z_tail, w_sym, n_labels, ws, st, fn);
+    default: return launch_select<MDG_PREC_F16, FILL, MASKED>(a, z_tail, w_sym, n_labels, ws, st, fn);
   }
 }
 
@@ -466,14 +549,34 @@ extern "C" size_t mdg_bilinear_select_workspace_bytes(int64_t n_head, int64_t n_
   return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
 }
 
-extern "C" int mdg_bilinear_select_count(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
-                                         int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+// The mask arguments of the *_masked entry points, checked and put into the kernel argument.
+int select_mask_args(const char* fn, PairMask& m, const uint32_t* mask, int64_t plane_stride, int64_t n_head, int64_t n_tail) {
+  MDG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, "%s: mask must be 4-byte aligned", fn);
+  MDG_CHECK_ARG(plane_stride == 0 || plane_stride >= mdg_pair_mask_plane_words(n_head, n_tail),
+                "%s: plane_stride %lld is neither 0 (shared plane) nor >= the %lld words of a plane", fn, (long long)plane_stride,
+                (long long)mdg_pair_mask_plane_words(n_head, n_tail));
+  m.words = mask;
+  m.plane_stride = plane_stride;
+  m.ld = mdg_pair_mask_ld(n_tail);
+  m.nrb = mdg_cdiv(n_head, 32);
+  return MDG_OK;
+}
+
+template <bool MASKED>
+int select_count_run(const char* fn, const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
+                     int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible, void* workspace,
+                     size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride) {
   bool launch;
-  const int rc = select_check("mdg_bilinear_select_count", z_head, z_tail, w_sym, thr, row_counts != nullptr, n_head, n_tail, n_labels, D_,
-                              precision, eligible, workspace, workspace_bytes, &launch);
+  const int rc = select_check(fn, z_head, z_tail, w_sym, thr, row_counts != nullptr, n_head, n_tail, n_labels, D_, precision, eligible,
+                              workspace, workspace_bytes, &launch);
   if (rc != MDG_OK || !launch) return rc;
-  SelectArgs a{};
+  SelectKArgs<MASKED> a{};
+  if constexpr (MASKED) {
+    const int mrc = select_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
+    if (mrc != MDG_OK) return mrc;
+  }
   a.z_head = z_head;
   a.thr = thr;
   a.row_counts = row_counts;
@@ -481,17 +584,22 @@ extern "C" int mdg_bilinear_select_count(const float* z_head, const float* z_tai
   a.eligible = eligible;
   a.zt.nrows = n_tail;
   a.w.nrows = D;
-  return select_dispatch<false>(a, z_tail, w_sym, n_labels, precision, workspace, stream, "mdg_bilinear_select_count");
+  return select_dispatch<false, MASKED>(a, z_tail, w_sym, n_labels, precision, workspace, stream, fn);
 }
 
-extern "C" int mdg_bilinear_select_fill(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const int64_t* row_ptr,
-                                        int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_,
-                                        int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream) {
+template <bool MASKED>
+int select_fill_run(const char* fn, const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const int64_t* row_ptr,
+                    int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible,
+                    void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride) {
   bool launch;
-  const int rc = select_check("mdg_bilinear_select_fill", z_head, z_tail, w_sym, thr, row_ptr && cols && vals, n_head, n_tail, n_labels, D_,
-                              precision, eligible, workspace, workspace_bytes, &launch);
+  const int rc = select_check(fn, z_head, z_tail, w_sym, thr, row_ptr && cols && vals, n_head, n_tail, n_labels, D_, precision, eligible,
+                              workspace, workspace_bytes, &launch);
   if (rc != MDG_OK || !launch) return rc;
-  SelectArgs a{};
+  SelectKArgs<MASKED> a{};
+  if constexpr (MASKED) {
+    const int mrc = select_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
+    if (mrc != MDG_OK) return mrc;
+  }
   a.z_head = z_head;
   a.thr = thr;
   a.row_ptr = reinterpret_cast<const long long*>(row_ptr);
@@ -501,5 +609,43 @@ extern "C" int mdg_bilinear_select_fill(const float* z_head, const float* z_tail
   a.eligible = eligible;
   a.zt.nrows = n_tail;
   a.w.nrows = D;
-  return select_dispatch<true>(a, z_tail, w_sym, n_labels, precision, workspace, stream, "mdg_bilinear_select_fill");
+  return select_dispatch<true, MASKED>(a, z_tail, w_sym, n_labels, precision, workspace, stream, fn);
+}
+
+}  // namespace
+
+extern "C" int mdg_bilinear_select_count(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
+                                         int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return select_count_run<false>("mdg_bilinear_select_count", z_head, z_tail, w_sym, thr, row_counts, n_head, n_tail, n_labels, D_, precision,
+                                 eligible, workspace, workspace_bytes, stream, nullptr, 0);
+}
+
+extern "C" int mdg_bilinear_select_fill(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const int64_t* row_ptr,
+                                        int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_,
+                                        int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream) {
+  return select_fill_run<false>("mdg_bilinear_select_fill", z_head, z_tail, w_sym, thr, row_ptr, cols, vals, n_head, n_tail, n_labels, D_,
+                                precision, eligible, workspace, workspace_bytes, stream, nullptr, 0);
+}
+
+extern "C" int mdg_bilinear_select_count_masked(const float* z_head, const float* z_tail, const float* w_sym, const float* thr,
+                                                int32_t* row_counts, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision,
+                                                int eligible, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask,
+                                                int64_t plane_stride) {
+  if (!mask)
+    return select_count_run<false>("mdg_bilinear_select_count_masked", z_head, z_tail, w_sym, thr, row_counts, n_head, n_tail, n_labels, D_,
+                                   precision, eligible, workspace, workspace_bytes, stream, nullptr, 0);
+  return select_count_run<true>("mdg_bilinear_select_count_masked", z_head, z_tail, w_sym, thr, row_counts, n_head, n_tail, n_labels, D_,
+                                precision, eligible, workspace, workspace_bytes, stream, mask, plane_stride);
+}
+
+extern "C" int mdg_bilinear_select_fill_masked(const float* z_head, const float* z_tail, const float* w_sym, const float* thr,
+                                               const int64_t* row_ptr, int32_t* cols, float* vals, int64_t n_head, int64_t n_tail,
+                                               int64_t n_labels, int64_t D_, int precision, int eligible, void* workspace, size_t workspace_bytes,
+                                               void* stream, const uint32_t* mask, int64_t plane_stride) {
+  if (!mask)
+    return select_fill_run<false>("mdg_bilinear_select_fill_masked", z_head, z_tail, w_sym, thr, row_ptr, cols, vals, n_head, n_tail, n_labels,
+                                  D_, precision, eligible, workspace, workspace_bytes, stream, nullptr, 0);
+  return select_fill_run<true>("mdg_bilinear_select_fill_masked", z_head, z_tail, w_sym, thr, row_ptr, cols, vals, n_head, n_tail, n_labels, D_,
+                               precision, eligible, workspace, workspace_bytes, stream, mask, plane_stride);
 }

@@ -26,7 +26,11 @@
 //
 // LDS: the three stage buffers of the row-statistics sweeps (96 KB, one workgroup per CU -- as ROWSTATS); registers: the
 // workgroup may use 256 per lane (launch bound 1), see DESIGN.md 4m for the measured budget of every instantiation.
-#include "bilinear_tiles.h"
+//
+// MASKED instantiations (mdg_bilinear_topk_masked): a known-pair exclusion bitmap (pairmask.hip) on top of
+// `eligible`; a set bit makes its element -inf like an ineligible one, so everything above holds for what remains.  The words of a
+// tile reach LDS by one or two more LDS-DMAs in the tile's group (pairmask.h); the MASKED = false kernels are what they were.
+#include "pairmask.h"
 
 namespace {
 
@@ -42,6 +46,15 @@ struct TopkArgs {
   int k;
   int eligible;         // mdg_topk_eligible
 };
+
+// The kernel argument: TopkArgs itself, plus the exclusion mask in the MASKED instantiations (mdg_bilinear_topk_masked).
+template <bool MASKED> struct TopkKArgs : TopkArgs {};
+template <> struct TopkKArgs<true> : TopkArgs { PairMask mask; };
+
+// LDS of a MASKED sweep behind the three stage buffers: per stage buffer and wave, NMW slots of 256 bytes -- the mask words of the
+// wave's row block(s) for the 64 columns of that buffer's tile (pairmask.h).
+template <int NMW> constexpr int topk_mask_stage = 8 * NMW * PAIRMASK_SLOT;
+template <bool MASKED, int NMW> constexpr int topk_lds_bytes = 3 * STAGE_BYTES + (MASKED ? 3 * topk_mask_stage<NMW> : 0);
 
 // Sorted insert of the candidates (cand, x, col) of one row into its list.  Must be called in wave-uniform control flow.
 // G lanes share the row; lv / li: this lane's slots of the list (entry s * G + (lane % G)), thr: the row's k-th value.
@@ -106,8 +119,12 @@ __device__ __forceinline__ int topk_tiles(const TopkArgs& p, int64_t row0, int B
 }
 
 // ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the list epilogue ---------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkArgs p) {
+// MASKED: an element is eligible when the mode allows it AND its bit of the exclusion mask is clear.  The 64 words
+// [row block of the wave][columns of the tile] ride with the tile: one more LDS-DMA per wave and tile group, into a slot of the
+// wave's own behind the stage buffers, so the group is NDMA + 1 = 5 instructions and the wait below keeps 5 in flight.  Lane
+// (r, h) then reads words r and 32 + r of the slot (its columns for t = 0, 1); its rows are bits acc_row(v, h) of them.
+template <int MODE, bool MASKED>
+__global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkKArgs<MASKED> p) {
   static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "32x32 sweep of the fp32-grade modes");
   constexpr int NW = 8, BM = 32 * NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -167,19 +184,32 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkArgs p)
   for (int v = 0; v < 16; ++v) { lv[v][0] = -INFINITY; li[v][0] = -1; thr[v] = -INFINITY; }
   constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
   static_assert(NDMA == 4, "vmcnt immediate below");
+  // MASKED: the wave's mask slot of stage buffer b is mslot + b * topk_mask_stage<1>; every group of DMAs below (tile + words)
+  // is issued together, so "the last group in flight" is 5 instructions instead of 4 and nothing else about the chain changes.
+  constexpr int MSTAGE = topk_mask_stage<1>;
+  const char* const mslot = smem + 3 * STAGE_BYTES + wave * PAIRMASK_SLOT;
+  const unsigned* mplane = nullptr;
+  if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
   stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  if constexpr (MASKED) pairmask_dma(p.mask, mplane, wrow0 >> 5, 0, lane, lds_addr(mslot));
   stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  if constexpr (MASKED) pairmask_dma(p.mask, mplane, wrow0 >> 5, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, lane, lds_addr(mslot + MSTAGE));
   int cur = 0;
   for (int s = 0; s < nst; ++s) {
     const int64_t tcol0 = static_cast<int64_t>(s) * BN;
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = NDMA: tile s landed, tile s+1 stays in flight
+    if constexpr (MASKED) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");       // = NDMA + 1 mask DMA: group s landed, group s+1 stays in flight
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = NDMA: tile s landed, tile s+1 stays in flight
     __builtin_amdgcn_s_barrier();      // tile s landed for every wave; every wave finished reading tile s-1
     const int nxt2 = cur == 0 ? 2 : cur - 1;                           // (cur + 2) % 3 = buffer of tile s-1
     const int s2 = s + 2 < nst ? s + 2 : nst - 1;                      // past the end: a copy nobody consumes
     stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    if constexpr (MASKED) pairmask_dma(p.mask, mplane, wrow0 >> 5, static_cast<int64_t>(s2) * BN, lane, lds_addr(mslot + nxt2 * MSTAGE));
     const char* lds = smem + cur * STAGE_BYTES;
+    const char* const mcur = mslot + cur * MSTAGE;                     // this wave's words of tile s (its own DMA: landed with the wait above)
     cur = cur == 2 ? 0 : cur + 1;
     if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 31) continue;       // wave-uniform: no column of this tile is below any of my rows
+    unsigned w0 = 0u, w1 = 0u;                                          // MASKED: read ahead of the MFMAs, whose issue hides the LDS latency
+    if constexpr (MASKED) { w0 = pairmask_word(mcur, r); w1 = pairmask_word(mcur, 32 + r); }
     f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -195,6 +225,15 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkArgs p)
 #pragma unroll
         for (int v = 0; v < 16; ++v)
           acc[t][v] = topk_eligible(mode, wrow0 + acc_row(v, h), tcol0 + 32 * t + r, p.n_tail) ? acc[t][v] : -INFINITY;
+    }
+    if constexpr (MASKED) {
+      if (__ballot((w0 | w1) != 0u) != 0) {                            // wave-uniform: a tile without a known pair costs two reads and this ballot
+        const unsigned mw[2] = {w0 >> (4 * h), w1 >> (4 * h)};         // bit acc_row(v, 0) of mw[t] <-> row acc_row(v, h)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[t][v] = (mw[t] >> acc_row(v, 0)) & 1u ? -INFINITY : acc[t][v];
+      }
     }
     bool any = false;
 #pragma unroll
@@ -232,8 +271,11 @@ __device__ __forceinline__ f32x4v topk_mma16x16(const bf16x8& a, const bf16x8& b
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkArgs p) {
+// MASKED: as above; the wave's 64 rows are two row blocks of the mask, so two mask DMAs per tile group (2 + 2 = 4 in flight) and
+// two slots: lane (c16, g4) reads word 16 ct + c16 of each for sub-tile ct; row 16 rt + 4 g4 + i is bit 16 (rt & 1) + 4 g4 + i
+// of the word of row block rt >> 1.
+template <int MODE, bool MASKED>
+__global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkKArgs<MASKED> p) {
   static_assert(kSingle16<MODE>, "one rounded 16-bit product per k step");
   constexpr int NW = 8, BM = 512;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -298,21 +340,42 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkArgs 
   int li[16][2];
 #pragma unroll
   for (int q = 0; q < 16; ++q) { lv[q][0] = lv[q][1] = -INFINITY; li[q][0] = li[q][1] = -1; thr[q] = -INFINITY; }
+  constexpr int MSTAGE = topk_mask_stage<2>;
+  const char* const mslot = smem + 3 * STAGE_BYTES + wave * 2 * PAIRMASK_SLOT;
+  const unsigned* mplane = nullptr;
+  if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
+  auto mask_dma = [&](int64_t col0, const char* slot) {               // the group's two mask DMAs: row blocks wrow0 / 32 and + 1
+    if constexpr (MASKED) {
+      pairmask_dma(p.mask, mplane, wrow0 >> 5, col0, lane, lds_addr(slot));
+      pairmask_dma(p.mask, mplane, (wrow0 >> 5) + 1, col0, lane, lds_addr(slot + PAIRMASK_SLOT));
+    }
+  };
   stage_dma<MODE>(p.zt, 0, smem, wave, lane, NW);
+  if constexpr (MASKED) mask_dma(0, mslot);
   stage_dma<MODE>(p.zt, static_cast<int64_t>(1 < nst ? 1 : 0) * BN, smem + STAGE_BYTES, wave, lane, NW);
+  if constexpr (MASKED) mask_dma(static_cast<int64_t>(1 < nst ? 1 : 0) * BN, mslot + MSTAGE);
   int cur = 0;
   for (int s = 0; s < nst; ++s) {
     const int64_t tcol0 = static_cast<int64_t>(s) * BN;
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // = LDS-DMA instructions per wave and tile: tile s landed, tile s+1 stays in flight
+    if constexpr (MASKED) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // = 2 tile + 2 mask DMAs per group: group s landed, group s+1 stays in flight
+    else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");           // = LDS-DMA instructions per wave and tile: tile s landed, tile s+1 stays in flight
     __builtin_amdgcn_s_barrier();
     const int nxt2 = cur == 0 ? 2 : cur - 1;
     const int s2 = s + 2 < nst ? s + 2 : nst - 1;
     stage_dma<MODE>(p.zt, static_cast<int64_t>(s2) * BN, smem + nxt2 * STAGE_BYTES, wave, lane, NW);
+    if constexpr (MASKED) mask_dma(static_cast<int64_t>(s2) * BN, mslot + nxt2 * MSTAGE);
     const char* lds = smem + cur * STAGE_BYTES;
+    const char* const mcur = mslot + cur * MSTAGE;                     // this wave's words of tile s (its own DMAs: landed with the wait above)
     cur = cur == 2 ? 0 : cur + 1;
     if (mode == MDG_TOPK_LOWER && tcol0 >= wrow0 + 63) continue;       // wave-uniform: nothing below the diagonal for my rows
     const bool plain = tcol0 + BN <= p.n_tail &&
                        (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 63));
+    unsigned mwd[4][2];                                                // MASKED: the tile's eight words, read ahead of the MFMAs that hide the LDS latency
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      mwd[ct][0] = mwd[ct][1] = 0u;
+      if constexpr (MASKED) { mwd[ct][0] = pairmask_word(mcur, 16 * ct + c16); mwd[ct][1] = pairmask_word(mcur + PAIRMASK_SLOT, 16 * ct + c16); }
+    }
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
       f32x4v acc[4];
@@ -331,6 +394,15 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkArgs 
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             acc[rt][i] = topk_eligible(mode, wrow0 + 16 * rt + 4 * g4 + i, col, p.n_tail) ? acc[rt][i] : -INFINITY;
+      }
+      if constexpr (MASKED) {
+        if (__ballot((mwd[ct][0] | mwd[ct][1]) != 0u) != 0) {           // wave-uniform, per 16-column sub-tile
+          const unsigned mw[2] = {mwd[ct][0] >> (4 * g4), mwd[ct][1] >> (4 * g4)};
+#pragma unroll
+          for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[rt][i] = (mw[rt >> 1] >> (16 * (rt & 1) + i)) & 1u ? -INFINITY : acc[rt][i];
+        }
       }
       bool any = false;
 #pragma unroll
@@ -395,8 +467,8 @@ __global__ void topk_images_kernel(const float* __restrict__ x, __bf16* __restri
 
 inline size_t topk_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
-template <int MODE>
-int launch_topk(TopkArgs& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st) {
+template <int MODE, bool MASKED>
+int launch_topk(TopkKArgs<MASKED>& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st) {
   if constexpr (MODE == MDG_PREC_F32) {
     a.zt.f32 = z_tail;
     a.w.f32 = w_sym;
@@ -414,12 +486,22 @@ int launch_topk(TopkArgs& a, const float* z_tail, const float* w_sym, int64_t n_
     a.zt.hi = zhi; a.zt.lo = zlo;
     a.w.hi = whi; a.w.lo = wlo;
   }
+  if constexpr (MASKED) {                         // more dynamic LDS than the unmasked sweeps use: raise the kernel's limit once
+    static bool attr_done = false;
+    if (!attr_done) {
+      if constexpr (kSingle16<MODE>)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_topk16_kernel<MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, topk_lds_bytes<true, 2>);
+      else
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_topk_kernel<MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, topk_lds_bytes<true, 1>);
+      attr_done = true;
+    }
+  }
   if constexpr (kSingle16<MODE>) {
     const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL(bilinear_topk16_kernel<MODE>, grid, dim3(512), 3 * STAGE_BYTES, st, a);
+    hipLaunchKernelGGL((bilinear_topk16_kernel<MODE, MASKED>), grid, dim3(512), (topk_lds_bytes<MASKED, 2>), st, a);
   } else {
     const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL(bilinear_topk_kernel<MODE>, grid, dim3(512), 3 * STAGE_BYTES, st, a);
+    hipLaunchKernelGGL((bilinear_topk_kernel<MODE, MASKED>), grid, dim3(512), (topk_lds_bytes<MASKED, 1>), st, a);
   }
   MDG_CHECK_LAUNCH("mdg_bilinear_topk");
   return MDG_OK;
@@ -436,9 +518,13 @@ extern "C" size_t mdg_bilinear_topk_workspace_bytes(int64_t n_head, int64_t n_ta
   return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
 }
 
-extern "C" int mdg_bilinear_topk(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx, int64_t n_head,
-                                 int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int k, int eligible, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+namespace {
+
+// Both entry points; MASKED: `mask` is not null.
+template <bool MASKED>
+int topk_run(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx, int64_t n_head, int64_t n_tail,
+             int64_t n_labels, int64_t D_, int precision, int k, int eligible, void* workspace, size_t workspace_bytes, void* stream,
+             const uint32_t* mask, int64_t plane_stride) {
   MDG_CHECK_ARG(D_ == D, "mdg_bilinear_topk: D must be %d (got %lld)", D, (long long)D_);
   MDG_CHECK_ARG(k >= 1 && k <= TOPK_MAX_K, "mdg_bilinear_topk: k must be in 1..%d (got %d)", TOPK_MAX_K, k);
   MDG_CHECK_ARG(n_head >= 0 && n_tail >= 0 && n_labels >= 0, "mdg_bilinear_topk: negative size");
@@ -455,13 +541,19 @@ extern "C" int mdg_bilinear_topk(const float* z_head, const float* z_tail, const
   MDG_CHECK_ARG(z_head && z_tail && w_sym && vals && idx, "mdg_bilinear_topk: null pointer");
   MDG_CHECK_ARG(mdg_aligned16(z_head) && mdg_aligned16(z_tail) && mdg_aligned16(w_sym),
                 "mdg_bilinear_topk: z_head, z_tail and w_sym must be 16-byte aligned");
+  if constexpr (MASKED) {
+    MDG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, "mdg_bilinear_topk_masked: mask must be 4-byte aligned");
+    MDG_CHECK_ARG(plane_stride == 0 || plane_stride >= mdg_pair_mask_plane_words(n_head, n_tail),
+                  "mdg_bilinear_topk_masked: plane_stride %lld is neither 0 (shared plane) nor >= the %lld words of a plane", (long long)plane_stride,
+                  (long long)mdg_pair_mask_plane_words(n_head, n_tail));
+  }
   const size_t need = mdg_bilinear_topk_workspace_bytes(n_head, n_tail, n_labels, D_, precision, k);
   if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
     mdg_set_error("mdg_bilinear_topk: workspace of %zu bytes (16-byte aligned) required, got %zu", need, workspace_bytes);
     return MDG_EWORKSPACE;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  TopkArgs a{};
+  TopkKArgs<MASKED> a{};
   a.z_head = z_head;
   a.vals = vals;
   a.idx = idx;
@@ -470,11 +562,36 @@ extern "C" int mdg_bilinear_topk(const float* z_head, const float* z_tail, const
   a.eligible = eligible;
   a.zt.nrows = n_tail;
   a.w.nrows = D;
+  if constexpr (MASKED) {
+    a.mask.words = mask;
+    a.mask.plane_stride = plane_stride;
+    a.mask.ld = mdg_pair_mask_ld(n_tail);
+    a.mask.nrb = mdg_cdiv(n_head, 32);
+  }
   char* ws = static_cast<char*>(workspace);
   switch (precision) {
-    case MDG_PREC_F32: return launch_topk<MDG_PREC_F32>(a, z_tail, w_sym, n_labels, ws, st);
-    case MDG_PREC_BF16X3: return launch_topk<MDG_PREC_BF16X3>(a, z_tail, w_sym, n_labels, ws, st);
-    case MDG_PREC_BF16: return launch_topk<MDG_PREC_BF16>(a, z_tail, w_sym, n_labels, ws, st);
-    default: return launch_topk<MDG_PREC_F16>(a, z_tail, w_sym, n_labels, ws, st);
+    case MDG_PREC_F32: return launch_topk<MDG_PREC_F32, MASKED>(a, z_tail, w_sym, n_labels, ws, st);
+    case MDG_PREC_BF16X3: return launch_topk<MDG_PREC_BF16X3, MASKED>(a, z_tail, w_sym, n_labels, ws, st);
+    case MDG_PREC_BF16: return launch_topk<MDG_PREC_BF16, MASKED>(a, z_tail, w_sym, n_labels, ws, st);
+    default: return launch_topk<MDG_PREC_F16, MASKED>(a, z_tail, w_sym, n_labels, ws, st);
   }
+}
+
+}  // namespace
+
+extern "C" int mdg_bilinear_topk(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx, int64_t n_head,
+                                 int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int k, int eligible, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return topk_run<false>(z_head, z_tail, w_sym, vals, idx, n_head, n_tail, n_labels, D_, precision, k, eligible, workspace, workspace_bytes,
+                         stream, nullptr, 0);
+}
+
+extern "C" int mdg_bilinear_topk_masked(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx,
+                                        int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int k, int eligible,
+                                        void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride) {
+  if (!mask)
+    return topk_run<false>(z_head, z_tail, w_sym, vals, idx, n_head, n_tail, n_labels, D_, precision, k, eligible, workspace, workspace_bytes,
+                           stream, nullptr, 0);
+  return topk_run<true>(z_head, z_tail, w_sym, vals, idx, n_head, n_tail, n_labels, D_, precision, k, eligible, workspace, workspace_bytes, stream,
+                        mask, plane_stride);
 }

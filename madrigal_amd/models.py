@@ -1674,17 +1674,26 @@ class BilinearDDIScorer(nn.Bilinear):
         ops.forward_only(input1, input2)
         return ops.bilinear_allpairs(input1, input2, weight, precision=_state["precision"], epilogue=epilogue, out=out)
 
-    def topk(self, input1, input2, k: int, label_range: tuple = None, eligible: str = "all"):
+    def _exclude_planes(self, exclude, label_range):
+        """An exclusion mask with one plane per outcome of the head, sliced like the weight (a shared plane serves every range)."""
+        if label_range is None or not isinstance(exclude, torch.Tensor) or exclude.dim() != 3 or exclude.shape[0] == 1 \
+                or exclude.shape[0] != self.symmetric_weight().shape[0]:
+            return exclude
+        return exclude[label_range[0]:label_range[1]]
+
+    def topk(self, input1, input2, k: int, label_range: tuple = None, eligible: str = "all", exclude=None):
         """Extension (screening): ``(vals, idx)`` [L', n1, k] -- for every outcome and row of ``input1`` the ``k`` highest scores of
         ``forward(input1, input2, label_range)`` over the eligible columns (``"all"``, ``"not_self"``: j != i, ``"lower"``: j < i) and
         those columns, ordered by (score descending, column ascending), in the precision ``forward`` uses; nothing of
-        [L', n1, n2] is materialised (``ops.bilinear_topk``).  Inference only."""
+        [L', n1, n2] is materialised (``ops.bilinear_topk``).  ``exclude``: an ``ops.pair_mask`` of pairs to leave out -- one plane,
+        or one per outcome of the WHOLE head (sliced by ``label_range`` like the weight).  Inference only."""
         ops.forward_only(input1, input2)
         w = self.symmetric_weight()
         if label_range is not None:
             assert len(label_range) == 2
             w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_topk(input1, input2, w, k, eligible=eligible, precision=_state["precision"])
+        return ops.bilinear_topk(input1, input2, w, k, eligible=eligible, precision=_state["precision"],
+                                 exclude=self._exclude_planes(exclude, label_range))
 
     def bincount(self, input1, input2, edges, label_range: tuple = None, eligible: str = "all"):
         """Extension (screening): int64 [L', B+1] -- per outcome the number of eligible scores of ``forward(input1, input2,
@@ -1697,28 +1706,30 @@ class BilinearDDIScorer(nn.Bilinear):
             w = w[label_range[0]:label_range[1]]
         return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"])
 
-    def select_count(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all"):
+    def select_count(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", exclude=None):
         """Extension (screening): int32 [L', n1] -- per outcome and row of ``input1`` the number of eligible scores of
         ``forward(input1, input2, label_range)`` at or above ``thresholds`` [L'], in the precision ``forward`` uses; nothing of
-        [L', n1, n2] is materialised (``ops.bilinear_select_count``).  Inference only."""
+        [L', n1, n2] is materialised (``ops.bilinear_select_count``).  ``exclude``: as in ``topk``.  Inference only."""
         ops.forward_only(input1, input2)
         w = self.symmetric_weight()
         if label_range is not None:
             assert len(label_range) == 2
             w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_select_count(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"])
+        return ops.bilinear_select_count(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"],
+                                         exclude=self._exclude_planes(exclude, label_range))
 
-    def select(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", max_bytes: int = 1 << 30):
+    def select(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", max_bytes: int = 1 << 30, exclude=None):
         """Extension (screening): ``(row_ptr int64 [L' * n1 + 1], cols int32 [T], vals fp32 [T])`` -- every eligible entry of
         ``forward(input1, input2, label_range)`` at or above ``thresholds`` [L'] as CSR over the rows (outcome, row of ``input1``),
         columns ascending: ``torch.nonzero`` of the dense mask, in the precision ``forward`` uses; nothing of [L', n1, n2] is
-        materialised (``ops.bilinear_select``).  Inference only."""
+        materialised (``ops.bilinear_select``).  ``exclude``: as in ``topk``.  Inference only."""
         ops.forward_only(input1, input2)
         w = self.symmetric_weight()
         if label_range is not None:
             assert len(label_range) == 2
             w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_select(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"], max_bytes=max_bytes)
+        return ops.bilinear_select(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"], max_bytes=max_bytes,
+                                   exclude=self._exclude_planes(exclude, label_range))
 
     def score_triples(self, input1, input2, plan: dict) -> torch.Tensor:
         """Extension (finetune step): scores of the plan's (label, head, tail) triples only, in the plan's

@@ -139,13 +139,118 @@ def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
 TOPK_ELIGIBLE = {"all": 0, "not_self": 1, "lower": 2}
 
 
+# ---- known-pair exclusion masks of the in-sweep products (include/madrigal_hip.h, "Known-pair exclusion masks") ----
+def _pair_list(x, name: str, n: int, what: str) -> torch.Tensor:
+    """int64 CPU/GPU vector from an index list, every entry in [0, n)."""
+    import numpy as np
+    if not isinstance(x, torch.Tensor):
+        arr = np.asarray(x)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise ValueError(f"{name}: expected integer indices, got {arr.dtype}")
+        x = torch.as_tensor(arr.astype(np.int64))
+    t = x
+    if t.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+        raise ValueError(f"{name}: expected integer indices, got {t.dtype}")
+    t = t.long().reshape(-1)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+        raise ValueError(f"{name}: {what} must lie in [0, {n}), got [{int(t.min())}, {int(t.max())}]")
+    return t
+
+
+def pair_mask(heads, tails, n_head: int, n_tail: Optional[int] = None, *, labels=None, n_labels: Optional[int] = None,
+              symmetric: bool = False, device=None) -> torch.Tensor:
+    """Exclusion mask of the listed pairs for ``bilinear_topk`` / ``bilinear_select_count`` / ``bilinear_select`` (``exclude=``)
+    -> int32 GPU tensor ``[P, ceil(n_head / 32), ld]``, ``ld`` = ``n_tail`` rounded up to 64: bit ``i & 31`` of word
+    ``[p, i >> 5, j]`` is set when (head row i, tail column j) is listed, and a set bit takes the pair out of the sweep's results.
+
+    ``heads`` / ``tails``: index lists of one length (any order, duplicates allowed; every index is checked here).  ``n_tail``
+    defaults to ``n_head`` (one drug set).  ``labels`` (with ``n_labels``): the outcome of every pair -> one plane per outcome,
+    ``P = n_labels``; without it ``P = 1``, one plane for all outcomes.  ``symmetric``: (t, h) is excluded with (h, t); needs
+    ``n_head == n_tail``.  The bits are set on the device with integer ORs: the result does not depend on the order of the list.
+    ``device``: where to build it (default: the lists' device if they are GPU tensors, else the current GPU)."""
+    n_tail = n_head if n_tail is None else n_tail
+    for v, name in ((n_head, "n_head"), (n_tail, "n_tail")):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name}: expected a non-negative int, got {v!r}")
+    if symmetric and n_head != n_tail:
+        raise ValueError(f"symmetric=True needs one drug set against itself (n_head {n_head} != n_tail {n_tail})")
+    if (labels is None) != (n_labels is None):
+        raise ValueError("labels and n_labels go together (one plane per outcome) or are both omitted (one shared plane)")
+    P = 1
+    if n_labels is not None:
+        if isinstance(n_labels, bool) or not isinstance(n_labels, int) or n_labels < 1:
+            raise ValueError(f"n_labels: expected a positive int, got {n_labels!r}")
+        P = n_labels
+    h = _pair_list(heads, "heads", n_head, "head rows")
+    t = _pair_list(tails, "tails", n_tail, "tail columns")
+    pl = None if labels is None else _pair_list(labels, "labels", P, "outcomes")
+    if h.numel() != t.numel() or (pl is not None and pl.numel() != h.numel()):
+        raise ValueError("heads, tails (and labels): index lists of one length")
+    if device is None:
+        device = next((x.device for x in (heads, tails, labels) if isinstance(x, torch.Tensor) and x.is_cuda), torch.device("cuda"))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"device: the mask is built on the GPU, got {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    L = lib()
+    ld, nrb = L.mdg_pair_mask_ld(n_tail), (n_head + 31) // 32
+    mask = torch.zeros((P, nrb, ld), dtype=torch.int32, device=device)
+    if h.numel() and mask.numel():
+        h, t = h.to(device).contiguous(), t.to(device).contiguous()
+        pl = None if pl is None else pl.to(device).contiguous()
+        with torch.cuda.device(device):
+            call("mdg_pair_mask_set", _ptr(mask), P, n_head, n_tail, _ptr(h), _ptr(t), _ptr(pl), h.numel(), int(bool(symmetric)), _stream(mask))
+    return mask
+
+
+def _mask_planes(mask: torch.Tensor, n_head: int, n_tail: int) -> int:
+    """Shape and dtype check of a packed mask against (n_head, n_tail) -> its number of planes.  A pure check (CPU or GPU tensors)."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32:
+        raise ValueError(f"exclude: expected an int32 mask from ops.pair_mask, got "
+                         f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+    want = ((n_head + 31) // 32, (n_tail + 63) // 64 * 64 if n_tail > 0 else 0)
+    if mask.dim() != 3 or tuple(mask.shape[1:]) != want:
+        raise ValueError(f"exclude: expected [P, {want[0]}, {want[1]}] for {n_head} head rows and {n_tail} tail columns, got {tuple(mask.shape)}")
+    return mask.shape[0]
+
+
+def pair_mask_dense(mask: torch.Tensor, n_head: int, n_tail: int) -> torch.Tensor:
+    """A packed exclusion mask unpacked -> bool ``[P, n_head, n_tail]``, True where the pair is excluded (for re-scoring dense
+    rows and for tests).  A pure tensor function (CPU or GPU)."""
+    P = _mask_planes(mask, n_head, n_tail)
+    shifts = torch.arange(32, dtype=torch.int32, device=mask.device)
+    bits = (mask[:, :, None, :] >> shifts[None, None, :, None]) & 1                 # [P, row blocks, 32, ld]
+    return bits.reshape(P, -1, mask.shape[2])[:, :n_head, :n_tail].bool()
+
+
+def pair_mask_rows(mask: torch.Tensor, plane: int, rows: torch.Tensor, n_tail: int) -> torch.Tensor:
+    """Rows ``rows`` (int64 indices) of plane ``plane`` of a packed mask -> bool ``[len(rows), n_tail]``: the rows
+    ``pair_mask_dense(mask, ...)[plane, rows]`` holds, without unpacking the plane.  A pure tensor function (CPU or GPU)."""
+    words = mask[plane].index_select(0, rows >> 5)[:, :n_tail]
+    return ((words >> (rows & 31).to(torch.int32)[:, None]) & 1).bool()
+
+
+def _exclude_args(exclude, zh: torch.Tensor, Nh: int, Nt: int, L: int):
+    """``exclude=`` of the in-sweep products -> (contiguous mask | None, plane stride in words)."""
+    if exclude is None:
+        return None, 0
+    P = _mask_planes(exclude, Nh, Nt)
+    if not exclude.is_cuda or exclude.device != zh.device:
+        raise ValueError(f"exclude: must live on the device of the embeddings ({zh.device}), got {exclude.device}")
+    if P != 1 and P != L:
+        raise ValueError(f"exclude: {P} planes; expected 1 (shared by all outcomes) or one per outcome ({L})")
+    m = exclude if exclude.is_contiguous() else exclude.contiguous()
+    return m, (0 if P == 1 else m.shape[1] * m.shape[2])
+
+
 def bilinear_topk_max_k() -> int:
     """Largest ``k`` of ``bilinear_topk`` (at least 32)."""
     return lib().mdg_bilinear_topk_max_k()
 
 
 def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, k: int, *, eligible: str = "all",
-                  precision="bf16x3", out=None):
+                  precision="bf16x3", out=None, exclude: Optional[torch.Tensor] = None):
     """Per-row top-k of the all-pairs sweep: ``(vals [L,Nh,k] fp32, idx [L,Nh,k] int32)``, for every outcome and head row the
     ``k`` largest scores ``z_head[i]^T W_sym[l] z_tail[j]`` over the eligible tail columns and those columns, ordered by
     (score descending, column ascending); rows with fewer than ``k`` eligible columns are padded with ``-inf`` / ``-1``.
@@ -154,7 +259,11 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     ``eligible``: ``"all"`` (two drug sets), ``"not_self"`` (``j != i``), ``"lower"`` (``j < i``, the strict lower triangle the
     rank normalisation reads; tiles on or above the diagonal are not computed); the last two need ``Nh == Nt``.  The scores
     are those of ``bilinear_allpairs``'s general sweep in the same ``precision`` ("f32" / "bf16x3": bit for bit; "bf16" / "f16":
-    the row-statistics sweep, fp32 sums grouped differently, <= 2e-6 of the scale).  ``out``: optional ``(vals, idx)`` pair."""
+    the row-statistics sweep, fp32 sums grouped differently, <= 2e-6 of the scale).  ``out``: optional ``(vals, idx)`` pair.
+
+    ``exclude``: a mask from ``pair_mask`` (``[1, ...]`` shared by all outcomes or ``[L, ...]``, one plane per outcome): a pair
+    whose bit is set is not eligible, on top of ``eligible`` -- the known interactions of a screening run.  The scores that remain
+    and their order are those of the call without it."""
     zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
     D = zh.shape[1]
     if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
@@ -172,6 +281,7 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
     if eligible != "all" and Nh != Nt:
         raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    mask, mstride = _exclude_args(exclude, zh, Nh, Nt, L)
     shape = (L, Nh, k)
     if out is None:
         vals = torch.empty(shape, dtype=torch.float32, device=zh.device)
@@ -191,8 +301,12 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     for lo in range(0, L, 65535):
         hi = min(L, lo + 65535)
         ws, nbytes = _scratch("mdg_bilinear_topk_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec, int(k))
-        call("mdg_bilinear_topk", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, vals.data_ptr() + lo * Nh * k * 4,
-             idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, hi - lo, D, prec, int(k), TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+        args = (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt,
+                hi - lo, D, prec, int(k), TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+        if mask is None:
+            call("mdg_bilinear_topk", *args)
+        else:
+            call("mdg_bilinear_topk_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
     return vals, idx
 
 
@@ -288,7 +402,7 @@ def _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_che
     return zh, zt, w, thr, prec
 
 
-def _select_count(zh, zt, w, thr, prec, eligible) -> torch.Tensor:
+def _select_count(zh, zt, w, thr, prec, eligible, mask=None, mstride=0) -> torch.Tensor:
     L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
     counts = torch.empty((L, Nh), dtype=torch.int32, device=zh.device)
     if counts.numel() == 0:
@@ -299,24 +413,30 @@ def _select_count(zh, zt, w, thr, prec, eligible) -> torch.Tensor:
     for lo in range(0, L, 65535):
         hi = min(L, lo + 65535)
         ws, nbytes = _scratch("mdg_bilinear_select_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
-        call("mdg_bilinear_select_count", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4,
-             counts.data_ptr() + lo * Nh * 4, Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+        args = (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4, counts.data_ptr() + lo * Nh * 4, Nh, Nt, hi - lo, D,
+                prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+        if mask is None:
+            call("mdg_bilinear_select_count", *args)
+        else:
+            call("mdg_bilinear_select_count_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
     return counts
 
 
 def bilinear_select_count(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, thresholds: torch.Tensor, *,
-                          eligible: str = "all", precision="bf16x3") -> torch.Tensor:
+                          eligible: str = "all", precision="bf16x3", exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-row sizes of ``bilinear_select`` -> int32 [L, Nh]: ``counts[l, i]`` is the number of eligible tail columns j with
     ``S[l,i,j] >= thresholds[l]``, counted inside the all-pairs sweep (nothing of [L,Nh,Nt] is materialised).  With one drug set and
     ``eligible="not_self"`` this is the degree of drug i in the outcome's predicted network.  ``thresholds``: fp32 [L], no NaN;
     ``-inf`` counts every eligible column, ``+inf`` none.  ``eligible`` and the score arithmetic are those of ``bilinear_topk``.
+    ``exclude``: a mask from ``pair_mask`` (one plane or one per outcome); a pair whose bit is set is not counted.
     Deterministic: no atomics."""
     zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision)
-    return _select_count(zh, zt, w, thr, prec, eligible)
+    mask, mstride = _exclude_args(exclude, zh, zh.shape[0], zt.shape[0], w.shape[0])
+    return _select_count(zh, zt, w, thr, prec, eligible, mask, mstride)
 
 
 def bilinear_select(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, thresholds: torch.Tensor, *, eligible: str = "all",
-                    precision="bf16x3", max_bytes: int = 1 << 30):
+                    precision="bf16x3", max_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
     """Every eligible pair at or above a per-outcome cut, as CSR -> ``(row_ptr int64 [L*Nh + 1], cols int32 [T], vals fp32 [T])``:
     row ``l * Nh + i`` holds, at ``[row_ptr[r], row_ptr[r + 1])``, the tail columns j with ``S[l,i,j] >= thresholds[l]`` in ascending
     order and those scores.  This is ``torch.nonzero((S >= thresholds[:, None, None]) & eligible_mask)`` of the dense scores, in that
@@ -327,10 +447,14 @@ def bilinear_select(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Ten
     best value (``top_pairs``) includes that value, and an edge of ``score_histogram`` selects the bins at and above it.
     ``eligible`` and the score arithmetic are those of ``bilinear_topk`` ("f32" / "bf16x3": the general sweep's scores bit for bit;
     "bf16" / "f16": the row-statistics sweep, <= 2e-6 of the scale).  ``max_bytes``: if the result's 8 T bytes exceed it a ValueError
-    naming ``T`` is raised before anything is allocated or filled.  Deterministic: no atomics; bit-identical from call to call."""
+    naming ``T`` is raised before anything is allocated or filled.  Deterministic: no atomics; bit-identical from call to call.
+
+    ``exclude``: a mask from ``pair_mask`` (one plane or one per outcome); a pair whose bit is set is not eligible, so the known
+    network is neither counted nor stored.  What remains is what the call without it returns, minus those pairs."""
     zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False)
     L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
-    counts = _select_count(zh, zt, w, thr, prec, eligible)          # (a NaN cut selects nothing: harmless until it is refused below)
+    mask, mstride = _exclude_args(exclude, zh, Nh, Nt, L)
+    counts = _select_count(zh, zt, w, thr, prec, eligible, mask, mstride)          # (a NaN cut selects nothing: harmless until it is refused below)
     row_ptr = torch.zeros(L * Nh + 1, dtype=torch.int64, device=zh.device)
     T = 0
     if L:
@@ -348,9 +472,12 @@ def bilinear_select(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Ten
     for lo in range(0, L, 65535):
         hi = min(L, lo + 65535)
         ws, nbytes = _scratch("mdg_bilinear_select_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
-        call("mdg_bilinear_select_fill", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4,
-             row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols), _ptr(vals), Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes,
-             _stream(zh))
+        args = (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4, row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols),
+                _ptr(vals), Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+        if mask is None:
+            call("mdg_bilinear_select_fill", *args)
+        else:
+            call("mdg_bilinear_select_fill_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
     return row_ptr, cols, vals
 
 

@@ -181,9 +181,38 @@ def _outcomes(model, label_range) -> Tuple[int, int]:
     return lo, hi
 
 
+def known_pairs_mask(N: int, heads, tails, labels=None, n_labels: Optional[int] = None, device=None) -> torch.Tensor:
+    """Exclusion mask of the KNOWN interactions of one drug set, for the ``exclude=`` of the screening products below: the pairs
+    {heads[q], tails[q]} (indices into z; any order, duplicates allowed) are taken out from both sides -- (h, t) and (t, h) --
+    -> int32 ``[P, ceil(N / 32), N rounded up to 64]`` on the GPU (``ops.pair_mask``, symmetric).  Without ``labels`` the pairs are
+    excluded under every outcome (P = 1: "any known interaction"); with ``labels`` (the outcome of every pair, indices into ALL
+    ``n_labels`` outcomes of the head) each outcome has its own plane, which the products slice by their ``label_range``.
+    One plane of 100 352 drugs is 1.26 GB (N^2 / 8 bytes), so at that scale the shared plane is the practical form."""
+    if isinstance(N, bool) or not isinstance(N, int) or N < 0:
+        raise ValueError(f"N: expected the number of drugs, got {N!r}")
+    return ops.pair_mask(heads, tails, N, N, labels=labels, n_labels=n_labels, symmetric=True, device=device)
+
+
+def _exclusion(exclude, model) -> Optional[torch.Tensor]:
+    """``exclude`` of the screening products, checked against the head: one shared plane, or one plane per outcome of the WHOLE head
+    (the decoder slices those by the ``label_range`` of each call, like the weight)."""
+    if exclude is None:
+        return None
+    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 3:
+        raise ValueError("exclude: expected a mask from known_pairs_mask / ops.pair_mask")
+    if exclude.shape[0] not in (1, _n_outcomes(model)):
+        raise ValueError(f"exclude: {exclude.shape[0]} planes; expected 1 or one per outcome of the head ({_n_outcomes(model)})")
+    return exclude
+
+
+def _n_outcomes(model) -> int:
+    dec = model.decoder
+    return dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
+
+
 @torch.no_grad()
 def top_partners(model, z: torch.Tensor, k: int, label_range: Optional[Tuple[int, int]] = None, drug_rows=None,
-                 max_temp_bytes: int = 1 << 30):
+                 max_temp_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
     """The ``k`` highest-scoring partners of every drug per outcome -> ``(vals, idx)`` [L', n, k] (fp32, int32): row i of
     outcome l holds the k largest S[l, i, j] over j != i and those j, ordered by (score descending, j ascending); padded with
     -inf / -1 when k > N - 1.  What the reference looks up in its stored [L,N,N] tensor (notebooks/quick_predictions.ipynb cell 8),
@@ -193,19 +222,23 @@ def top_partners(model, z: torch.Tensor, k: int, label_range: Optional[Tuple[int
     ``drug_rows`` are picked from outcome chunks whose temporaries ([c, N, k] values and indices) stay under ``max_temp_bytes``.
     Without ``drug_rows`` the kernel writes straight into the result and there is no temporary.  The result itself is the
     caller's: L' * n * k * 8 bytes (1 024 outcomes x 100 352 drugs x k = 8: 6.6 GB).
+    ``exclude``: a ``known_pairs_mask``; its pairs are skipped INSIDE the sweep, so the k partners are the k best NOVEL ones --
+    for a drug with hundreds of known partners the lists would otherwise hold nothing else, and no post-filter can bring back
+    what the sweep dropped.  A row with fewer than k partners left is padded.
     Multi-GPU: pass the outcome shard the rank owns as ``label_range``; no collective is involved."""
     lo, hi = _outcomes(model, label_range)
     N = z.shape[0]
     rows = _index(drug_rows, N, "drug_rows", z.device)
+    excl = _exclusion(exclude, model)
     if rows is None:
-        return model.decoder.topk(z, z, k, (lo, hi), eligible="not_self")
+        return model.decoder.topk(z, z, k, (lo, hi), eligible="not_self", exclude=excl)
     n = int(rows.numel())
     vals = torch.empty((hi - lo, n, k), dtype=torch.float32, device=z.device)
     idx = torch.empty((hi - lo, n, k), dtype=torch.int32, device=z.device)
     chunk = max(1, int(max_temp_bytes) // max(N * k * 8, 1))
     for s in range(lo, hi, chunk):
         e = min(hi, s + chunk)
-        v, i = model.decoder.topk(z, z, k, (s, e), eligible="not_self")
+        v, i = model.decoder.topk(z, z, k, (s, e), eligible="not_self", exclude=excl)
         vals[s - lo:e - lo] = v[:, rows]
         idx[s - lo:e - lo] = i[:, rows]
     return vals, idx
@@ -275,7 +308,7 @@ def merge_row_candidates(vals: torch.Tensor, idx: torch.Tensor, K: int, rescore,
 
 @torch.no_grad()
 def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, int]] = None, k_row: Optional[int] = None,
-              max_temp_bytes: int = 1 << 30, info: Optional[dict] = None):
+              max_temp_bytes: int = 1 << 30, info: Optional[dict] = None, exclude: Optional[torch.Tensor] = None):
     """The ``K`` highest-scoring unordered drug pairs of every outcome -> ``(vals [L', K] fp32, head [L', K], tail [L', K]
     int64)``: the pair {i, j} is scored as S[l, i, j] with i > j (the strict lower triangle the rank normalisation reads,
     notebooks/normalize_scores.py:39-46; the value is the general sweep's (z_i W) z_j), ordered by (score descending, i ascending,
@@ -290,7 +323,10 @@ def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, i
     values, so pairs closer than that may swap places against a brute-force ranking of either sweep.
     Temporaries: outcome chunks sized so that the candidate lists and their sort stay under ``max_temp_bytes`` (48 bytes per
     candidate), plus, per open outcome, the dense rows ([<= K / k_row, N] fp32).  Multi-GPU: pass the rank's outcome shard as
-    ``label_range``.  ``info["open_rows"]``: open rows per outcome."""
+    ``label_range``.  ``info["open_rows"]``: open rows per outcome.
+    ``exclude``: a ``known_pairs_mask``; the K best pairs NOT in it.  The row lists skip its pairs inside the sweep and the re-scored
+    rows get -inf at their excluded columns (``ops.pair_mask_rows``), so the result is exact as before: a row is open under the
+    same condition (removing columns only shortens what lies behind a row's last entry)."""
     lo, hi = _outcomes(model, label_range)
     N = z.shape[0]
     max_k = ops.bilinear_topk_max_k()
@@ -300,6 +336,7 @@ def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, i
     if isinstance(k_row, bool) or not isinstance(k_row, int) or not 1 <= k_row <= max_k:
         raise ValueError(f"k_row: expected an int in 1..{max_k}, got {k_row!r}")
     dec = model.decoder
+    excl = _exclusion(exclude, model)
     out_v = torch.empty((hi - lo, K), dtype=torch.float32, device=z.device)
     out_h = torch.empty((hi - lo, K), dtype=torch.int64, device=z.device)
     out_t = torch.empty((hi - lo, K), dtype=torch.int64, device=z.device)
@@ -307,9 +344,16 @@ def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, i
     chunk = max(1, int(max_temp_bytes) // max(N * k_row * 48, 1))
     for s in range(lo, hi, chunk):
         e = min(hi, s + chunk)
-        vals, idx = dec.topk(z, z, k_row, (s, e), eligible="lower")
+        vals, idx = dec.topk(z, z, k_row, (s, e), eligible="lower", exclude=excl)
         part = {}
-        v, h, t = merge_row_candidates(vals, idx, K, lambda l, rows: dec(z[rows].contiguous(), z, (s + l, s + l + 1))[0], part)
+
+        def rescore(l, rows, s=s):
+            dense = dec(z[rows].contiguous(), z, (s + l, s + l + 1))[0]
+            if excl is not None:
+                dense.masked_fill_(ops.pair_mask_rows(excl, 0 if excl.shape[0] == 1 else s + l, rows, N), float("-inf"))
+            return dense
+
+        v, h, t = merge_row_candidates(vals, idx, K, rescore, part)
         out_v[s - lo:e - lo], out_h[s - lo:e - lo], out_t[s - lo:e - lo] = v, h, t
         opened += part["open_rows"]
         del vals, idx, v, h, t
@@ -364,29 +408,36 @@ def csr_rows(row_ptr: torch.Tensor, n_head: int, total: Optional[int] = None):
 
 
 @torch.no_grad()
-def partner_counts(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+def partner_counts(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None,
+                   exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
     """How many partners j != i of every drug score at or above the outcome's cut -> int32 [L', N]: ``counts[l, i]`` =
     #{j != i : S[l, i, j] >= thresholds[l]}, the degree of drug i in outcome l's predicted interaction network, counted inside the
     sweep (``decoder.select_count``, ``not_self`` mode) -- no [L', N, N] tensor at any N.  ``thresholds``: a number or [L'], no NaN.
+    ``exclude``: a ``known_pairs_mask``; its pairs are not counted (the degree in the NOVEL predicted network).
     Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
     lo, hi = _outcomes(model, label_range)
-    return model.decoder.select_count(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self")
+    return model.decoder.select_count(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self",
+                                      exclude=_exclusion(exclude, model))
 
 
 @torch.no_grad()
-def partners_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30):
+def partners_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30,
+                   exclude: Optional[torch.Tensor] = None):
     """ALL partners of every drug at or above the outcome's cut, as CSR -> ``(row_ptr int64 [L' * N + 1], cols int32 [T], vals fp32
     [T])``: row ``l * N + i`` lists the j != i with S[l, i, j] >= thresholds[l] in ascending order and those scores (``decoder.select``,
     ``not_self`` mode; ``csr_rows(row_ptr, N)`` gives every entry's outcome and drug).  Where ``top_partners`` returns the k best of a
     drug, this returns its whole neighbourhood in the predicted network; every unordered pair appears from both sides, with
     S[l, i, j] and S[l, j, i] (equal up to the last bits).  The result's size is known only after the counting sweep: more than
-    ``max_bytes`` (8 bytes per entry) raises a ValueError naming the size.  ``thresholds``: a number or [L'], no NaN."""
+    ``max_bytes`` (8 bytes per entry) raises a ValueError naming the size.  ``thresholds``: a number or [L'], no NaN.
+    ``exclude``: a ``known_pairs_mask``; its pairs are neither counted nor stored."""
     lo, hi = _outcomes(model, label_range)
-    return model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self", max_bytes=max_bytes)
+    return model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self", max_bytes=max_bytes,
+                                exclude=_exclusion(exclude, model))
 
 
 @torch.no_grad()
-def pairs_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30):
+def pairs_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30,
+                exclude: Optional[torch.Tensor] = None):
     """ALL unordered drug pairs of every outcome that score at or above its cut -- the outcome's predicted interaction network --
     -> ``(offsets int64 [L' + 1], head int64 [T], tail int64 [T], vals fp32 [T])``: outcome l owns the entries
     ``offsets[l]:offsets[l + 1]``.  The pair {i, j} is scored as S[l, i, j] with i > j, the strict-lower-triangle entry ``top_pairs``,
@@ -401,9 +452,12 @@ def pairs_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[
       * an edge of ``score_histogram``: the pairs of the bins at and above it, whose number the histogram already told.
     ``normalized_ranks_of(model, z, vals)`` -- per outcome, e.g. on ``vals[offsets[l]:offsets[l + 1]][None, :]`` with
     ``label_range=(l, l + 1)`` -- gives the normalised ranks of what was selected.
+    ``exclude``: a ``known_pairs_mask``; the known network is neither counted nor stored, so a cut low enough to be interesting
+    returns (and sizes ``max_bytes`` by) the novel pairs alone.  Ranks stay those over ALL pairs (``normalized_ranks_of``).
     Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
     lo, hi = _outcomes(model, label_range)
-    row_ptr, cols, vals = model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="lower", max_bytes=max_bytes)
+    row_ptr, cols, vals = model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="lower", max_bytes=max_bytes,
+                                               exclude=_exclusion(exclude, model))
     _, head, offsets = csr_rows(row_ptr, z.shape[0], total=int(cols.numel()))
     if z.shape[0] == 0:
         offsets = torch.zeros(hi - lo + 1, dtype=torch.int64, device=z.device)
