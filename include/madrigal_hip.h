@@ -33,6 +33,7 @@ extern "C" {
 #define MDG_EWORKSPACE (-2) /* workspace too small / missing */
 #define MDG_ELAUNCH (-3)  /* HIP launch failed */
 #define MDG_EUNSUPPORTED (-4)
+#define MDG_GATHER_MAX_SOURCES 19 /* source matrices of one mdg_gather_rows_multi call */
 
 /* Arithmetic of the matrix products.  Inputs and outputs stay fp32. */
 enum mdg_precision {
@@ -253,6 +254,19 @@ int mdg_pack_operand(const float* src, int64_t ld, int64_t rows, int64_t K, int 
  * the weight image of the backward product dx = g W (a dense block with weight W^T) without materialising W^T. */
 int mdg_pack_operand_transposed(const float* src, int64_t ld, int64_t rows, int64_t cols, int precision, void* dst, size_t dst_bytes,
                                 void* stream);
+/* Rows gathered across up to MDG_GATHER_MAX_SOURCES fp32 matrices of one width, standing for
+ * torch.cat(sources).index_select(0, idx) without the concatenated copy (the reference stacks the 16 per-cell-line signature
+ * matrices, madrigal/models/models.py:753-769, and the [str | kg | cv | tx] embeddings, :781-790, before it indexes them):
+ *   out[i, :] = sources[idx[i] / rows_per_source][idx[i] % rows_per_source, :]          i in [0, n)
+ * sources_host / source_rows_host / source_ld_host are HOST arrays of n_sources entries (device pointer, row count <=
+ * rows_per_source, row stride in floats >= width); idx is a DEVICE array.  An index that is negative or names a row its source
+ * does not have gathers a zero row (nothing outside the sources is ever read).  out (nullable) [n, ldo] receives the rows with
+ * the columns from width up to width rounded up to 4 zeroed (ldo % 4 == 0); image (nullable; 16-bit modes) receives the same rows as
+ * the operand image of mdg_linear_packed_x: the bytes mdg_pack_operand writes for out, mdg_pack_operand_bytes(n, width rounded
+ * up to 4, precision) of them.  Sources need 4-byte alignment only; wider loads are used where every row allows them. */
+int mdg_gather_rows_multi(const float* const* sources_host, const int64_t* source_rows_host, const int64_t* source_ld_host,
+                          int n_sources, int64_t rows_per_source, int64_t width, const int64_t* idx, int64_t n, float* out,
+                          int64_t ldo, void* image, size_t image_bytes, int precision, void* stream);
 size_t mdg_linear_workspace_bytes(int64_t M, int64_t N, int64_t K, int precision, int w_is_packed);
 int mdg_linear(const float* x, int64_t ldx, const float* w, int64_t ldw, const void* w_packed, float* y, int64_t ldy, int64_t M,
                int64_t N, int64_t K, const float* bias, const float* scale, const float* shift, int activation,

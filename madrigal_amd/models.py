@@ -1853,6 +1853,12 @@ class NovelDDIEncoder(nn.Module):
         self.live_tokens_only = True
         # run the KG encoder on a second HIP stream beside the structure / cv / tx encoders
         self.overlap_kg = True
+        # inference: rows that live in several matrices are read by one gather kernel (ops.gather_rows_multi) instead of being
+        # stacked first -- the present signatures of the 16 cell lines, the single modality of the uni-modal drugs, the KG rows
+        # of the batch (filler rows for drugs outside the KG).  Bytes only: the results are bit-identical either way.
+        self.gather_tx_rows = True
+        self.gather_uni_rows = True
+        self.gather_kg_rows = True
         self._plan_cache = None
         self._kg_stream = None
 
@@ -1966,7 +1972,12 @@ class NovelDDIEncoder(nn.Module):
         read them)."""
         if self.tx_encoder_dict is not None:
             return torch.cat([self.tx_encoder_dict[c](batch_tx_dict[c]['sigs']) for c in CELL_LINES], dim=0)
-        sigs = torch.cat([batch_tx_dict[c]['sigs'] for c in CELL_LINES], dim=0)
+        per_line = [batch_tx_dict[c]['sigs'] for c in CELL_LINES]
+        # inference over the present rows only: they are read straight from the 16 matrices (no 16 n-row stack, of which about
+        # a tenth is selected), already zero-padded to the multiple of 4 columns the dense block takes
+        direct = (present_rows is not None and self.gather_tx_rows and not ag.needs_grad(*per_line)
+                  and all(s.is_cuda and s.dtype == torch.float32 and s.dim() == 2 and s.shape == per_line[0].shape for s in per_line))
+        sigs = None if direct else torch.cat(per_line, dim=0)
         # covariate (cell line) index per row of the stack; host work + H2D copy only when the name arrays change
         names = [np.asarray(batch_tx_dict[c]['cell_lines']) for c in CELL_LINES]
         ckey = (str(device),) + tuple((a.size, str(a[0]) if a.size else "", bool(a.size and np.all(a == a[0]))) for a in names)
@@ -1982,9 +1993,13 @@ class NovelDDIEncoder(nn.Module):
             self.__dict__["_cov_cache"] = hit
         cov = hit[1]
         sel = present_rows
-        if sel is not None:
-            sigs, cov = sigs.index_select(0, sel), cov.index_select(0, sel)
-        zeros = torch.zeros(sigs.shape[0], dtype=torch.int64, device=device)
+        if direct:
+            sigs, cov = ops.gather_rows_multi(per_line, sel, pad4=True), cov.index_select(0, sel)
+            zeros = cov                                     # drugs_idx / dosages: required, never read (use_drugs=False)
+        else:
+            if sel is not None:
+                sigs, cov = sigs.index_select(0, sel), cov.index_select(0, sel)
+            zeros = torch.zeros(sigs.shape[0], dtype=torch.int64, device=device)
         if sigs.shape[0] == 0:
             lat = torch.zeros(0, self.embed_dim, device=device)
         else:
@@ -2058,7 +2073,25 @@ class NovelDDIEncoder(nn.Module):
                         cache.pop(next(iter(cache)))
                     hit = cache[gkey] = (gkey, pos[batch_drugs].contiguous(), kg_map, batch_drugs)
                 return ag.gather_rows_or(kg_valid, hit[1], filler.to(dev)[batch_drugs])
-            table = filler.to(dev).clone()
+            fill = filler.to(dev)
+            if (self.gather_kg_rows and kg_valid.is_cuda and kg_valid.dtype == fill.dtype == torch.float32 and batch_drugs.dim() == 1
+                    and kg_valid.shape[0] == kg_map.numel() and not ag.needs_grad(kg_valid, fill)):
+                # one gather instead of clone + indexed store + indexed read: drug d's row of the KG encoder's output, or of the
+                # filler table for a drug outside the KG, through an index kept per (map, batch) as the training path keeps its own
+                gkey = (kg_map.data_ptr(), kg_map._version, kg_map.numel(), batch_drugs.data_ptr(), batch_drugs._version, tuple(batch_drugs.shape),
+                        batch_drugs.stride(), int(fill.shape[0]))
+                cache = self.__dict__.setdefault("_kg_gather_rows", {})
+                hit = cache.get(gkey)
+                rps = max(int(kg_map.numel()), int(fill.shape[0]), 1)          # the two tables as sources of one stacked row space
+                if hit is None or hit[2] is not kg_map or hit[3] is not batch_drugs:
+                    pos = torch.full((int(fill.shape[0]),), -1, dtype=torch.int64, device=dev)
+                    pos[kg_map] = torch.arange(kg_map.numel(), device=dev)
+                    at = pos[batch_drugs]
+                    while len(cache) >= 4:
+                        cache.pop(next(iter(cache)))
+                    hit = cache[gkey] = (gkey, torch.where(at >= 0, at, batch_drugs + rps).contiguous(), kg_map, batch_drugs)
+                return ops.gather_rows_multi([kg_valid, fill], hit[1], rows_per_source=rps)
+            table = fill.clone()
             table[kg_map] = kg_valid
             return table[batch_drugs]
         main = torch.cuda.current_stream(dev)
@@ -2182,8 +2215,14 @@ class NovelDDIEncoder(nn.Module):
         z = torch.empty((n, Dm), dtype=torch.float32, device=dev)
         z[rows] = z_f
         if mp["n_uni"] > 0:
-            all_embeds = torch.stack([str_out, kg_out, cv_out] + list(tx_out.split(n)), dim=1)
-            uni = all_embeds[uni_rows, mp["uni_col"]]
+            outs = [str_out, kg_out, cv_out, tx_out]
+            if (self.gather_uni_rows and all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == Dm for t in outs)
+                    and all(t.shape[0] == n for t in outs[:3]) and tx_out.shape[0] == len(CELL_LINES) * n and not ag.needs_grad(*outs)):
+                # the single modality of each uni-modal drug, read from the 19 [n, D] blocks where they are (no [n, 19, D] stack)
+                uni = ops.gather_rows_multi(outs[:3] + list(tx_out.split(n)), mp["uni_flat"], rows_per_source=n)
+            else:
+                all_embeds = torch.stack([str_out, kg_out, cv_out] + list(tx_out.split(n)), dim=1)
+                uni = all_embeds[uni_rows, mp["uni_col"]]
             if self.normalize:
                 uni = norm(uni)
             z[uni_rows] = self.uni_fuser(uni)

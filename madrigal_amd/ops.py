@@ -616,6 +616,58 @@ def pack_operand(x: torch.Tensor, precision="bf16x3") -> Optional[torch.Tensor]:
     return img
 
 
+GATHER_MAX_SOURCES = 19
+
+
+def gather_rows_multi(sources, idx: torch.Tensor, rows_per_source: Optional[int] = None, *, pad4: bool = False, image=None,
+                      want_fp32: bool = True):
+    """``torch.cat(sources).index_select(0, idx)`` for 1..19 fp32 matrices of one width without the concatenated copy
+    (mdg_gather_rows_multi): row ``idx[i] % rows_per_source`` of source ``idx[i] // rows_per_source``.  ``rows_per_source``
+    defaults to the sources' common row count (then the result equals the cat + index_select bit for bit); with a larger value
+    the sources may be shorter, and an index that is negative or outside its source gathers a zero row.
+
+    ``pad4``: the result is [n, width rounded up to 4] with zero columns behind ``width`` (what ``linear`` pads a 978-wide
+    input to), else [n, width].  ``image`` (a precision): also return the rows as the packed operand of ``linear_packed``, the
+    bytes of ``pack_operand`` on them; None where the mode takes none.  -> rows, or (rows | None, image | None) with ``image``."""
+    srcs = list(sources)
+    if not 1 <= len(srcs) <= GATHER_MAX_SOURCES:
+        raise ValueError(f"gather_rows_multi: 1 to {GATHER_MAX_SOURCES} sources, got {len(srcs)}")
+    dev, W = srcs[0].device, srcs[0].shape[-1]
+    for j, t in enumerate(srcs):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == W and t.device == dev):
+            raise ValueError(f"gather_rows_multi: sources[{j}] must be an fp32 cuda matrix of width {W} on {dev}")
+        if t.shape[0] and t.stride(1) != 1:
+            srcs[j] = t.contiguous()
+    forward_only(*srcs)
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1 and idx.device == dev):
+        raise ValueError("gather_rows_multi: idx must be a 1-D int64 cuda tensor on the sources' device")
+    idx = idx if idx.is_contiguous() else idx.contiguous()
+    rps = max(t.shape[0] for t in srcs) if rows_per_source is None else int(rows_per_source)
+    if rows_per_source is None and any(t.shape[0] != rps for t in srcs):
+        raise ValueError("gather_rows_multi: sources of different row counts need an explicit rows_per_source")
+    if rps < max(t.shape[0] for t in srcs):
+        raise ValueError("gather_rows_multi: rows_per_source smaller than a source")
+    n, Wo = idx.numel(), _ceil4(W)
+    prec = None if image is None else _prec(image)
+    nbytes = 0 if prec is None or prec == PREC_F32 else lib().mdg_pack_operand_bytes(n, Wo, prec)
+    img = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    out = None
+    if want_fp32 or img is None:
+        out = torch.empty((n, Wo if pad4 or W % 4 else W), dtype=torch.float32, device=dev)
+    if n and W and rps:
+        K = len(srcs)
+        a_p = (ctypes.c_void_p * K)(*[t.data_ptr() for t in srcs])
+        a_r = (ctypes.c_int64 * K)(*[t.shape[0] for t in srcs])
+        a_l = (ctypes.c_int64 * K)(*[t.stride(0) if t.shape[0] > 1 else W for t in srcs])
+        call("mdg_gather_rows_multi", a_p, a_r, a_l, K, rps, W, _ptr(idx), n, _ptr(out), 0 if out is None else out.stride(0), _ptr(img), nbytes,
+             0 if prec is None else prec, _stream(idx))
+    elif out is not None:
+        out.zero_()
+    if out is not None and out.shape[1] != W and not pad4:
+        out = out[:, :W]
+    return out if image is None else (out, img)
+
+
 def _rows2d(x: torch.Tensor, name: str):
     """[..., K] fp32 cuda tensor -> (2-D view/copy with unit inner stride and ld % 4 == 0, leading shape)."""
     x = _f32_cuda(x, name)
