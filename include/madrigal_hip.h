@@ -268,6 +268,10 @@ int mdg_gather_rows_multi(const float* const* sources_host, const int64_t* sourc
                           int n_sources, int64_t rows_per_source, int64_t width, const int64_t* idx, int64_t n, float* out,
                           int64_t ldo, void* image, size_t image_bytes, int precision, void* stream);
 size_t mdg_linear_workspace_bytes(int64_t M, int64_t N, int64_t K, int precision, int w_is_packed);
+/* (ABI 18) Edge of the output tile mdg_linear (and its _dropout / _packed_x forms) runs an [M, N] product on: 256 or 128.  The launch path's
+ * own decision (shape, precision, MDG_LINEAR_TILE; re-read after mdg_tuning_reload()); launches nothing, needs no device.
+ * mdg_linear_rowscaled takes the 128-tile kernel unless MDG_LINEAR_TILE says otherwise. */
+int mdg_linear_tile(int64_t M, int64_t N, int precision);
 int mdg_linear(const float* x, int64_t ldx, const float* w, int64_t ldw, const void* w_packed, float* y, int64_t ldy, int64_t M,
                int64_t N, int64_t K, const float* bias, const float* scale, const float* shift, int activation,
                const float* residual, int64_t ldr, float alpha, float beta, int precision, void* workspace,

@@ -1469,6 +1469,9 @@ static bool choose_big(int precision, int64_t M, int64_t N, bool prefer_small = 
   return big;
 }
 
+// the tile shape a dense block of this output shape runs on (no launch, no device): what launch_linear_core decides
+extern "C" int mdg_linear_tile(int64_t M, int64_t N, int precision) { return choose_big(precision, M, N) ? 256 : 128; }
+
 // 128-tile kernel, 16-bit modes: x is rounded / split while it is staged, no pre-pass over it (MDG_LINEAR_RAWX=0: pre-pass)
 static bool raw_x_ok(int precision, bool big) {
   static MdgEnvInt raw_sw{"MDG_LINEAR_RAWX", 1};

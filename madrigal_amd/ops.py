@@ -685,6 +685,12 @@ class PackedWeight:
         self.shape, self.image, self.device = tuple(int(v) for v in shape), image, image.device
 
 
+def linear_tile(M: int, N: int, precision="bf16x3") -> int:
+    """Edge of the output tile the dense block runs an [M, N] product on, 256 or 128 (mdg_linear_tile: the launch path's own
+    decision by shape, mode and MDG_LINEAR_TILE; no launch, no device)."""
+    return int(lib().mdg_linear_tile(int(M), int(N), _prec(precision)))
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, scale=None, shift=None,
            act=None, residual: Optional[torch.Tensor] = None, alpha: float = 1.0, beta: float = 1.0,
            precision="bf16x3", out: Optional[torch.Tensor] = None, cache_weight: bool = True,

@@ -26,6 +26,32 @@ def test_workspace_queries_need_no_gpu():
     assert b3 == 2 * b1 and b1 >= 4096 * 128 * 2 + 896 * 128 * 128 * 2
 
 
+def test_dense_block_tile_query_needs_no_gpu(monkeypatch):
+    """mdg_linear_tile / ops.linear_tile: the launch path's own choice between the 256- and the 128-tile kernel -- 16-bit mode,
+    M >= 1024, N >= 256 and at least 192 tiles of 256 x 256 -- and the MDG_LINEAR_TILE switch, re-read after a reload."""
+    from helpers import set_switch
+    from madrigal_amd import _lib, ops
+    monkeypatch.delenv("MDG_LINEAR_TILE", raising=False)
+    _lib.lib().mdg_tuning_reload()
+    for M, N in ((1023, 49152), (4097, 2048), (1024, 12288), (3100, 3800), (1, 1), (22016, 6144)):
+        assert ops.linear_tile(M, N, "f32") == 128, (M, N)
+    for prec in ("bf16", "bf16x3"):
+        assert ops.linear_tile(1023, 49152, prec) == 128                  # 4 x 192 tiles, but M < 1024
+        assert ops.linear_tile(4097, 2048, prec) == 128                   # 17 x 8 = 136 tiles
+        assert ops.linear_tile(1024, 12288, prec) == 256                  # 4 x 48 = 192 tiles
+        assert ops.linear_tile(3100, 3800, prec) == 256                   # 13 x 15 = 195 tiles
+        assert ops.linear_tile(22016, 6144, prec) == 256
+    assert _lib.lib().mdg_linear_tile(3100, 3800, ops.PREC_BF16) == 256
+    set_switch(monkeypatch, "MDG_LINEAR_TILE", "256")
+    assert ops.linear_tile(1, 1, "bf16") == 256 and ops.linear_tile(1, 1, "bf16x3") == 256 and ops.linear_tile(1, 1, "f32") == 128
+    set_switch(monkeypatch, "MDG_LINEAR_TILE", "128")
+    for prec in ("f32", "bf16", "bf16x3"):
+        assert ops.linear_tile(22016, 6144, prec) == 128
+    monkeypatch.delenv("MDG_LINEAR_TILE")
+    _lib.lib().mdg_tuning_reload()
+    assert ops.linear_tile(22016, 6144, "bf16") == 256 and ops.linear_tile(1, 1, "bf16") == 128
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from madrigal_amd import ops

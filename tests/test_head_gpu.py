@@ -182,7 +182,12 @@ def test_asymmetric_operands_catch_transposes(ops):
     ref = _oracle(zh, zt, w)
     got = ops.bilinear_allpairs(zh.cuda(), zt.cuda(), ops.symmetrize(w.cuda()), precision="f32").cpu()
     assert rel_err(got, ref) < 1e-6
-    assert rel_err(got, ref.transpose(1, 2)[:, :n, :50] if False else ref) < 1e-6
+    # The operand roles swapped: the oracle then holds S^T, [L, 50, n].  W is symmetric here (the head's premise), so transposing that
+    # back gives S again and cannot tell the roles apart; left as it is, on the common n x n block, it is what a head that
+    # confused z_head with z_tail (or wrote S[j, i] where S[i, j] belongs) would store -- entries of the score's own size away.
+    swapped = _oracle(zt, zh, w)
+    assert swapped.shape == (L, 50, n) and rel_err(swapped.transpose(1, 2), ref) < 1e-5
+    assert rel_err(got[:, :n, :n], swapped[:, :n, :n]) > 0.1
 
 
 def test_sigmoid_epilogue(ops):
