@@ -235,6 +235,33 @@ int mdg_bilinear_select_fill_masked(const float* z_head, const float* z_tail, co
                                     int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream,
                                     const uint32_t* mask, int64_t plane_stride);
 
+/* Per-pair outcome profiles of the all-pairs sweep (ABI 19): the reduction of the sweep over the OUTCOMES instead of over the pairs.
+ * With S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j], per-outcome cuts thr[l] and scales scale[l] (finite, > 0; NULL = all ones), three
+ * [n_head, ldo] matrices (row pitch ldo >= n_tail elements) -- for every eligible pair (i,j), over the n_labels outcomes of the call:
+ *   count[i,j]  int32 = #{l : S[l,i,j] >= thr[l]}              (the compare is on S itself: the test of mdg_bilinear_select_*)
+ *   margin[i,j] fp32  = max_l u_l,  u_l = (S[l,i,j] - thr[l]) * scale[l]   (a subtract, then a multiply, each rounded to fp32)
+ *   best[i,j]   int32 = the smallest l attaining that maximum
+ * The running state starts at margin = -inf, best = -1 and moves only on u > margin, so a pair whose every u is -inf (thr = +inf)
+ * or NaN keeps best = -1; a NaN score is never counted and never best.  Ineligible pairs (enum mdg_topk_eligible: the diagonal in
+ * NOT_SELF, j >= i in LOWER) get count 0, best -1, margin -inf.  EVERY entry [i,j] with i < n_head, j < n_tail is written (callers
+ * need no zeroing); nothing at columns [n_tail, ldo) is touched.  "How many outcomes is this pair flagged for, and which is its
+ * strongest": the reference has no function of this kind; it reads such summaries off its stored score tensor.
+ *   Scores: in ALL FOUR precisions bit for bit those of mdg_bilinear_allpairs' general sweep (MDG_EPI_STORE); the 16-bit modes run
+ *   the same 32x32x16 products here, not the regrouped sums of the row-statistics sweeps.
+ *   D == 128; n_labels <= 65535 per call (count and best share a register; merge chunks on the caller's side: counts add, the
+ *   larger margin wins, equal margins keep the lower outcome); n_tail < 2^31 - 64; n_head <= 65535 * 256; NOT_SELF / LOWER need
+ *   n_head == n_tail.  thr may be +-inf; a NaN in thr, or a scale that is not finite and > 0, is refused with MDG_EINVAL: the call
+ *   reads thr and scale back and synchronises `stream` once before it launches (so it cannot be captured into a graph).  A refused
+ *   call launches nothing.  n_labels == 0 writes the ineligible values everywhere.
+ * Deterministic: a workgroup owns a tile of pairs, walks the outcomes in ascending order and keeps the state in registers; no
+ * atomics; bit-identical from launch to launch.  LOWER does no product work for tiles wholly on or above the diagonal.
+ * Workspace: the operand images of mdg_bilinear_allpairs (0 for F32). */
+size_t mdg_bilinear_profile_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision);
+int mdg_bilinear_profile(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const float* scale,
+                         int32_t* count, int32_t* best, float* margin, int64_t ldo, int64_t n_head, int64_t n_tail,
+                         int64_t n_labels, int64_t D, int precision, int eligible, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ------------------------------------------------------------------------ dense blocks ---- */
 
 /* Y = alpha * act( (X W^T + bias) * scale + shift ) + beta * R      X [M,K] ldx, W [N,K] ldw (nn.Linear

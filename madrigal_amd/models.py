@@ -1731,6 +1731,18 @@ class BilinearDDIScorer(nn.Bilinear):
         return ops.bilinear_select(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"], max_bytes=max_bytes,
                                    exclude=self._exclude_planes(exclude, label_range))
 
+    def profile(self, input1, input2, thresholds, scale=None, label_range: tuple = None, eligible: str = "all", out=None):
+        """Extension (screening): ``(count int32, best int32, margin fp32)`` [n1, n2] -- per pair, over the outcomes of
+        ``forward(input1, input2, label_range)``: how many score at or above ``thresholds`` [L'], the largest
+        ``(score - threshold) * scale`` and the lowest outcome (an index into the range) attaining it, in the precision ``forward``
+        uses; nothing of [L', n1, n2] is materialised (``ops.bilinear_profile``; L' <= 65535).  Inference only."""
+        ops.forward_only(input1, input2)
+        w = self.symmetric_weight()
+        if label_range is not None:
+            assert len(label_range) == 2
+            w = w[label_range[0]:label_range[1]]
+        return ops.bilinear_profile(input1, input2, w, thresholds, scale=scale, eligible=eligible, precision=_state["precision"], out=out)
+
     def score_triples(self, input1, input2, plan: dict) -> torch.Tensor:
         """Extension (finetune step): scores of the plan's (label, head, tail) triples only, in the plan's
         label-sorted order, differentiable w.r.t. both embeddings and the weight (train_ddi_batch.py:285-286

@@ -481,6 +481,67 @@ def bilinear_select(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Ten
     return row_ptr, cols, vals
 
 
+def _profile_out(out, Nh: int, Nt: int, device):
+    """The (count, best, margin) triple of ``bilinear_profile``: fresh row-pitched tensors, or the caller's, checked."""
+    dtypes = (torch.int32, torch.int32, torch.float32)
+    if out is None:
+        pitch = (Nt + 31) // 32 * 32                  # rows on 128-byte lines, as empty_scores (a multiple of 4 elements)
+        return tuple(torch.empty((Nh, pitch), dtype=dt, device=device)[:, :Nt] for dt in dtypes)
+    if not (isinstance(out, (tuple, list)) and len(out) == 3):
+        raise ValueError("out: expected a (count, best, margin) triple")
+    for t, dt, name in zip(out, dtypes, ("count", "best", "margin")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dt and tuple(t.shape) == (Nh, Nt)):
+            raise ValueError(f"out: {name} must be a {dt} GPU tensor of shape {(Nh, Nt)} on {device}")
+        if t.numel() and (t.stride(1) != 1 or t.stride(0) < Nt or t.stride(0) != out[0].stride(0)):
+            raise ValueError(f"out: {name} must be contiguous or row-pitched, with one pitch for all three (strides {tuple(t.stride())})")
+    return tuple(out)
+
+
+def bilinear_profile(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, thresholds: torch.Tensor, *,
+                     scale: Optional[torch.Tensor] = None, eligible: str = "all", precision="bf16x3", out=None):
+    """Per-pair outcome profile of the all-pairs head -> ``(count int32, best int32, margin fp32)``, each [Nh, Nt]: over the L
+    outcomes of ``w_sym``, ``count[i, j]`` = #{l : S[l,i,j] >= thresholds[l]}, ``margin[i, j]`` = max_l (S[l,i,j] - thresholds[l]) *
+    scale[l] (a subtract, then a multiply, in fp32) and ``best[i, j]`` the lowest l attaining it -- the sweep reduced over the
+    OUTCOMES, with nothing of [L,Nh,Nt] materialised (``mdg_bilinear_profile``: a workgroup holds a tile of pairs and walks l).
+    ``scale``: fp32 [L], finite and > 0 (None: ones).  ``thresholds``: fp32 [L], no NaN; with ``-inf`` every eligible pair counts
+    and its margin is +inf, with ``+inf`` none does; a pair no outcome moves off ``-inf`` keeps ``best = -1``.  Ineligible pairs
+    (``eligible`` as in ``bilinear_topk``) get 0 / -1 / -inf; every entry is written.  The scores are the general sweep's
+    (``bilinear_allpairs``) bit for bit in all four precisions.  L <= 65535 per call: merge chunks with ``profile_merge``.
+    ``out``: an optional (count, best, margin) triple to reuse, contiguous or with one common row pitch.  The values of
+    ``thresholds`` and ``scale`` are checked by the library, which synchronises the stream once.  Deterministic: no atomics."""
+    if scale is not None and isinstance(w_sym, torch.Tensor) and w_sym.dim() == 3:           # shapes first, then the device
+        if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or tuple(scale.shape) != (w_sym.shape[0],):
+            raise ValueError(f"scale: expected a float32 tensor [{w_sym.shape[0]}] (one per outcome)")
+    zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False)
+    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
+    if L > 65535:
+        raise ValueError(f"w_sym: {L} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
+    sc = None
+    if scale is not None:
+        sc = _f32_cuda(scale, "scale", 1)
+        if sc.device != zh.device:
+            raise ValueError("scale must be on the device of z_head")
+    res = _profile_out(out, Nh, Nt, zh.device)
+    if Nh == 0 or Nt == 0:
+        return res
+    ws, nbytes = _scratch("mdg_bilinear_profile_workspace_bytes", zh.device, Nh, Nt, L, D, prec)
+    call("mdg_bilinear_profile", _ptr(zh), _ptr(zt), _ptr(w), _ptr(thr), _ptr(sc), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
+         res[0].stride(0), Nh, Nt, L, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+    return res
+
+
+def profile_merge(a, b, label_offset_b: int):
+    """Merge the ``bilinear_profile`` results of two DISJOINT outcome chunks over the same pairs -> ``(count, best, margin)``:
+    counts add, the larger margin wins, equal margins keep the lower global outcome.  ``a``'s ``best`` already holds global
+    outcome indices; ``b``'s are local to its chunk, whose first outcome is ``label_offset_b``; ``best = -1`` (no outcome moved the
+    pair off -inf) stays -1 and never wins a tie.  Pure torch, any device; the arguments are left unchanged."""
+    ca, ba, ma = a
+    cb, bb, mb = b
+    gb = torch.where(bb >= 0, bb + int(label_offset_b), bb)
+    take_b = (mb > ma) | ((mb == ma) & (gb >= 0) & ((ba < 0) | (gb < ba)))
+    return ca + cb, torch.where(take_b, gb, ba), torch.where(take_b, mb, ma)
+
+
 ENSEMBLE_PRECISIONS ={"f32": PREC_F32, "bf16x3": PREC_BF16X3}
 
 

@@ -499,6 +499,116 @@ def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optio
     return less
 
 
+PROFILE_CHUNK = 65535          # outcomes per call of the profile sweep (count and best share a register there)
+
+
+def _profile_chunks(model, z_head, z_tail, thr, scale, lo, hi, eligible, chunk):
+    """``decoder.profile`` over the outcomes [lo, hi) in chunks, merged -> (count, best, margin), ``best`` relative to ``lo``."""
+    res = None
+    for s in range(lo, max(hi, lo + 1), chunk):
+        e = min(hi, s + chunk)
+        part = model.decoder.profile(z_head, z_tail, thr[s - lo:e - lo], None if scale is None else scale[s - lo:e - lo], (s, e),
+                                     eligible=eligible)
+        res = part if res is None else ops.profile_merge(res, part, s - lo)
+    return res
+
+
+@torch.no_grad()
+def outcome_profile(model, z: torch.Tensor, thresholds, scale=None, label_range: Optional[Tuple[int, int]] = None,
+                    eligible: str = "not_self", head_rows: Optional[Tuple[int, int]] = None, chunk: int = PROFILE_CHUNK):
+    """The screen seen per PAIR instead of per outcome -> ``(count int32, best int64, margin fp32)``, each [N, N] (or [r1 - r0, N]
+    with ``head_rows``): for the pair (i, j), over the outcomes ``label_range`` (default: all), ``count`` is the number of outcomes
+    with S[l, i, j] >= thresholds[l] -- for how many interaction types the pair is flagged --, ``margin`` the largest
+    ``(S[l, i, j] - thresholds[l]) * scale[l]`` and ``best`` the MODEL's index of the lowest outcome attaining it (-1 where no
+    outcome moved the pair off -inf).  Nothing of [L', N, N] is materialised (``decoder.profile``: one sweep per ``chunk`` <= 65535
+    outcomes, merged with ``ops.profile_merge``).  ``thresholds``: a number or [L'], no NaN (cuts come from ``top_pairs``,
+    ``score_histogram`` or ``count_below``); ``scale``: None, a positive number or [L'] (e.g. one over an outcome's score spread, to
+    compare margins across outcomes).  ``eligible``: ``"not_self"`` (default), ``"lower"`` (j < i) or ``"all"``; ineligible entries
+    hold 0 / -1 / -inf.  ``head_rows`` = (r0, r1): only drugs [r0, r1) against all drugs, with the same eligibility in the
+    coordinates of the full matrix; the row blocks concatenate to the full result (row sharding across ranks or over time).
+    Multi-GPU over outcomes: pass the rank's shard as ``label_range`` and merge the shards with ``ops.profile_merge``."""
+    lo, hi = _outcomes(model, label_range)
+    if eligible not in ops.TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(ops.TOPK_ELIGIBLE)}")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= PROFILE_CHUNK:
+        raise ValueError(f"chunk: expected an int in 1..{PROFILE_CHUNK}, got {chunk!r}")
+    thr = _cuts(thresholds, hi - lo, z.device)
+    sc = None if scale is None else _cuts(scale, hi - lo, z.device)
+    N = z.shape[0]
+    if head_rows is None:
+        count, best, margin = _profile_chunks(model, z, z, thr, sc, lo, hi, eligible, chunk)
+    else:
+        r0, r1 = head_rows
+        if not (0 <= r0 <= r1 <= N):
+            raise ValueError(f"head_rows {head_rows} outside [0, {N}]")
+        # a rectangle: the sweep runs in "all" mode and the block's self / upper entries are blanked here
+        count, best, margin = _profile_chunks(model, z[r0:r1], z, thr, sc, lo, hi, "all", chunk)
+        if eligible != "all":
+            i = torch.arange(r0, r1, device=z.device)[:, None]
+            j = torch.arange(N, device=z.device)[None, :]
+            out = (j == i) if eligible == "not_self" else (j >= i)
+            count = count.masked_fill(out, 0)
+            best = best.masked_fill(out, -1)
+            margin = margin.masked_fill(out, float("-inf"))
+    best = best.long()
+    return count, torch.where(best >= 0, best + lo, best), margin
+
+
+def _profile_keys(count: torch.Tensor, margin: torch.Tensor) -> torch.Tensor:
+    """int64 keys whose descending order is (count descending, margin descending); -0.0 and +0.0 compare equal."""
+    b = (margin + 0.0).contiguous().view(torch.int32).long()
+    mkey = torch.where(b < 0, -(b & 0x7FFFFFFF) - 1, b) + (1 << 31)              # ascending with the float, in [0, 2^32)
+    return (count.long() << 32) | mkey
+
+
+@torch.no_grad()
+def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, label_range: Optional[Tuple[int, int]] = None,
+                       max_bytes: int = 1 << 30):
+    """The ``K`` unordered drug pairs flagged for the most outcomes -> ``(count int32 [K], head int64 [K], tail int64 [K], best
+    int64 [K], margin fp32 [K])``: the pair {i, j} is profiled as (i, j) with i > j (the strict lower triangle ``top_pairs`` uses),
+    ordered by (count descending, margin descending, i ascending, j ascending); ``count``, ``best`` and ``margin`` are those of
+    ``outcome_profile``.  Padded with 0 / -1 / -1 / -1 / -inf when K > N (N - 1) / 2.  Streams over row blocks -- rows [r0, r1)
+    against the drugs [0, r1), the rest of the block being the upper triangle -- sized so that a block's profile and its selection
+    temporaries (about 48 bytes per pair) stay under ``max_bytes``, and keeps a running best K: no [N, N] tensor either, so it
+    runs at any N.  Exact: a tie at the K-th place is broken by (i, j) like every other."""
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"K: expected a positive int, got {K!r}")
+    lo, hi = _outcomes(model, label_range)
+    thr = _cuts(thresholds, hi - lo, z.device)
+    sc = None if scale is None else _cuts(scale, hi - lo, z.device)
+    N, dev = z.shape[0], z.device
+    rows = max(1, int(max_bytes) // max(48 * N, 1))
+    if rows >= 256:
+        rows -= rows % 256                      # whole workgroups of the sweep
+    run = None                                  # (key, count, head, tail, best, margin) of the best K so far, in result order
+    for r0 in range(1, N, rows):                # row 0 has no column below it
+        r1 = min(N, r0 + rows)
+        count, best, margin = _profile_chunks(model, z[r0:r1], z[:r1], thr, sc, lo, hi, "all", PROFILE_CHUNK)
+        i = torch.arange(r0, r1, device=dev)[:, None]
+        j = torch.arange(r1, device=dev)[None, :]
+        key = _profile_keys(count, margin).masked_fill_(j >= i, -1).reshape(-1)
+        k = min(K, key.numel())
+        kth = torch.topk(key, k, sorted=True).values[-1].clamp_(min=0)          # (>= 0: ineligible entries never enter)
+        flat = torch.nonzero(key >= kth).reshape(-1)                           # ascending (i, j)
+        ci, cj = flat // r1, flat % r1
+        cand = (key[flat], count[ci, cj], ci + r0, cj, best[ci, cj].long(), margin[ci, cj])
+        if run is not None:
+            cand = tuple(torch.cat([a, b]) for a, b in zip(run, cand))          # earlier rows first
+        order = torch.sort(cand[0], descending=True, stable=True).indices[:K]
+        run = tuple(t[order] for t in cand)
+        del count, best, margin, key, flat
+    out_c = torch.zeros(K, dtype=torch.int32, device=dev)
+    out_h = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    out_t = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    out_b = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    out_m = torch.full((K,), float("-inf"), dtype=torch.float32, device=dev)
+    if run is not None:
+        n = run[0].numel()
+        out_c[:n], out_h[:n], out_t[:n], out_m[:n] = run[1], run[2], run[3], run[5]
+        out_b[:n] = torch.where(run[4] >= 0, run[4] + lo, run[4])
+    return out_c, out_h, out_t, out_b, out_m
+
+
 def ranks_from_counts(less: torch.Tensor, N: int) -> torch.Tensor:
     """Normalised rank of a pair with ``less`` pairs of its outcome scoring below it, among the N (N - 1) / 2 pairs of N drugs
     -> float32: ``(less + 1) / (N (N - 1) / 2)``, divided in float64 and rounded to float32 once -- the arithmetic of
