@@ -218,8 +218,19 @@ int mdg_bilinear_select_fill(const float* z_head, const float* z_tail, const flo
  *   treated exactly like an ineligible one (top-k: never kept, padding -inf / -1 when fewer than k remain; select: never counted
  *   or stored), so order, tie rule, CSR order, bounded writes and determinism are those of the twins, and the scores that remain
  *   are bit for bit the twins'.  mask == NULL forwards to the twin.  The kernels read words [0, ceil(n_head/32)) x [0, ld) of a
- *   plane and nothing else.  Workspace: the twin's query.  mdg_bilinear_bincount takes no mask: a normalised rank is defined over
- *   all N (N - 1) / 2 pairs (notebooks/normalize_scores.py:57). */
+ *   plane and nothing else.  Workspace: the twin's query.
+ *   Counting excludes nothing: a normalised rank is defined over all N (N - 1) / 2 pairs (notebooks/normalize_scores.py:57), so
+ *   mdg_bilinear_bincount takes no mask and its counts stay what they are.  mdg_bilinear_bincount_split (ABI 20) takes the
+ *   arguments of mdg_bilinear_bincount plus `mask` and `plane_stride` (the rules above) and counts the two classes SEPARATELY in
+ *   the same sweep: counts is int64 [2][n_labels][n_edges + 1], zeroed by the call on `stream`; table 0 holds the eligible pairs
+ *   whose bit is CLEAR, table 1 those whose bit is SET; a pair that `eligible` or the bounds rule out is counted in neither,
+ *   whatever its bit (a symmetric mask has bits on the diagonal and above it: under LOWER they change nothing).  The two tables
+ *   sum to the counts of mdg_bilinear_bincount exactly, in all four precisions: it is the same sweep, and the scores are the
+ *   twin's bit for bit.  With the known network as the mask, the cumulative sums of table 1 are the known pairs below every edge:
+ *   exact precision / recall / enrichment at any cut and AUROC bounds over the whole pair universe, per outcome, in one pass.
+ *   mask == NULL: table 0 is the twin's result, table 1 is zero.  Refusals are the twin's plus the mask's alignment and
+ *   plane_stride; a refused call launches nothing and leaves `counts` untouched.  Workspace: mdg_bilinear_bincount_workspace_bytes.
+ *   Deterministic like the twin: integer device-scope adds, bit-identical from launch to launch. */
 int64_t mdg_pair_mask_ld(int64_t n_tail);
 int64_t mdg_pair_mask_plane_words(int64_t n_head, int64_t n_tail);
 int mdg_pair_mask_set(uint32_t* mask, int64_t n_planes, int64_t n_head, int64_t n_tail, const int64_t* heads, const int64_t* tails,
@@ -234,6 +245,9 @@ int mdg_bilinear_select_fill_masked(const float* z_head, const float* z_tail, co
                                     int32_t* cols, float* vals, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D,
                                     int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream,
                                     const uint32_t* mask, int64_t plane_stride);
+int mdg_bilinear_bincount_split(const float* z_head, const float* z_tail, const float* w_sym, const float* edges, int64_t* counts,
+                                int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_edges, int precision, int eligible,
+                                void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
 
 /* Per-pair outcome profiles of the all-pairs sweep (ABI 19): the reduction of the sweep over the OUTCOMES instead of over the pairs.
  * With S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j], per-outcome cuts thr[l] and scales scale[l] (finite, > 0; NULL = all ones), three

@@ -1695,16 +1695,21 @@ class BilinearDDIScorer(nn.Bilinear):
         return ops.bilinear_topk(input1, input2, w, k, eligible=eligible, precision=_state["precision"],
                                  exclude=self._exclude_planes(exclude, label_range))
 
-    def bincount(self, input1, input2, edges, label_range: tuple = None, eligible: str = "all"):
+    def bincount(self, input1, input2, edges, label_range: tuple = None, eligible: str = "all", split=None):
         """Extension (screening): int64 [L', B+1] -- per outcome the number of eligible scores of ``forward(input1, input2,
         label_range)`` between the ascending ``edges`` [L', B] (``torch.bucketize(right=True)`` + bincount), in the precision
-        ``forward`` uses; nothing of [L', n1, n2] is materialised (``ops.bilinear_bincount``).  Inference only."""
+        ``forward`` uses; nothing of [L', n1, n2] is materialised (``ops.bilinear_bincount``).  ``split``: an ``ops.pair_mask`` -- one
+        plane, or one per outcome of the WHOLE head (sliced by ``label_range`` like the weight) -> int64 [2, L', B+1], the pairs whose
+        bit is clear and those whose bit is set counted separately in the same sweep.  Inference only."""
         ops.forward_only(input1, input2)
         w = self.symmetric_weight()
         if label_range is not None:
             assert len(label_range) == 2
             w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"])
+        if split is None:
+            return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"])
+        return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"],
+                                     split=self._exclude_planes(split, label_range))
 
     def select_count(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", exclude=None):
         """Extension (screening): int32 [L', n1] -- per outcome and row of ``input1`` the number of eligible scores of

@@ -316,7 +316,7 @@ def bilinear_bincount_max_edges() -> int:
 
 
 def bilinear_bincount(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, edges: torch.Tensor, *, eligible: str = "all",
-                      precision="bf16x3") -> torch.Tensor:
+                      precision="bf16x3", split: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-outcome counts of the all-pairs sweep's scores between edges -> int64 [L, B+1]: with ``edges`` [L, B] fp32, finite and
     ascending per outcome, ``counts[l, b]`` is the number of eligible pairs (i, j) with ``edges[l, b-1] <= S[l,i,j] < edges[l, b]``
     (``edges[l, -1] = -inf``, ``edges[l, B] = +inf``): ``torch.bucketize(S[l], edges[l], right=True)`` followed by a bincount, with
@@ -324,7 +324,12 @@ def bilinear_bincount(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
 
     ``eligible`` and the score arithmetic are those of ``bilinear_topk`` ("f32" / "bf16x3": the general sweep's scores bit for bit;
     "bf16" / "f16": the row-statistics sweep, <= 2e-6 of the scale).  ``1 <= B <= bilinear_bincount_max_edges()``; Nt < 2^23.
-    Integer sums: bit-identical from launch to launch."""
+    Integer sums: bit-identical from launch to launch.
+
+    ``split``: a mask from ``pair_mask`` (``[1, ...]`` shared by all outcomes or ``[L, ...]``, one plane per outcome) -> int64
+    [2, L, B+1]: the same sweep with the two classes counted separately -- ``[0]`` the eligible pairs whose bit is clear, ``[1]``
+    those whose bit is set (the known pairs); a bit of an ineligible pair changes nothing.  Nothing is excluded: ``result.sum(0)`` is
+    the call without ``split``, exactly, in every precision."""
     # shapes and edge values first (on whatever device the tensors live), then the device: a bad call says what is wrong with it
     for t, name, nd in ((z_head, "z_head", 2), (z_tail, "z_tail", 2), (w_sym, "w_sym", 3), (edges, "edges", 2)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
@@ -356,6 +361,18 @@ def bilinear_bincount(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
     e = _f32_cuda(edges, "edges", 2)
     if zh.device != zt.device or zh.device != w.device or zh.device != e.device:
         raise ValueError("z_head, z_tail, w_sym and edges must be on the same device")
+    if split is not None:
+        mask, mstride = _exclude_args(split, zh, Nh, Nt, L)
+        counts = torch.empty((2, L, B + 1), dtype=torch.int64, device=zh.device)
+        for lo in range(0, L, 65535):
+            hi = min(L, lo + 65535)
+            part = counts if hi - lo == L else torch.empty((2, hi - lo, B + 1), dtype=torch.int64, device=zh.device)   # [2][this call's outcomes]
+            ws, nbytes = _scratch("mdg_bilinear_bincount_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, B, prec)
+            call("mdg_bilinear_bincount_split", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, e.data_ptr() + lo * B * 4, _ptr(part), Nh, Nt,
+                 hi - lo, D, B, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh), mask.data_ptr() + lo * mstride * 4, mstride)
+            if part is not counts:
+                counts[:, lo:hi] = part
+        return counts
     counts = torch.empty((L, B + 1), dtype=torch.int64, device=zh.device)
     # the grid's y extent caps one call at 65535 outcomes; chunk above that
     for lo in range(0, L, 65535):

@@ -364,13 +364,16 @@ def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, i
 
 @torch.no_grad()
 def score_histogram(model, z: torch.Tensor, edges: torch.Tensor, label_range: Optional[Tuple[int, int]] = None,
-                    eligible: str = "lower") -> torch.Tensor:
+                    eligible: str = "lower", known: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-outcome histogram of the all-pairs scores -> int64 [L', B+1]: ``counts[l, b]`` is the number of eligible pairs whose
     score lies in ``[edges[l, b-1], edges[l, b])`` (-inf below the first edge, +inf above the last), counted inside the sweep
     (``decoder.bincount``) -- no [L', N, N] tensor at any N.  ``edges``: ``[B]`` shared by all outcomes or ``[L', B]``, fp32,
     finite and ascending, 1 <= B <= ``ops.bilinear_bincount_max_edges()``.  ``eligible``: ``"lower"`` (the unordered pairs
     i > j the rank normalisation reads, the default), ``"not_self"`` or ``"all"``.  Cumulative sums of a row are the
     distribution function of the outcome's scores at the edges, from which quantiles follow.
+    ``known``: a ``known_pairs_mask`` -> int64 [2, L', B+1]: the same sweep with the novel pairs (``[0]``, bit clear) and the known
+    pairs (``[1]``, bit set) counted separately; nothing is excluded, ``result.sum(0)`` is the histogram without ``known``
+    (``auroc_bounds_from_counts`` reads this form).
     Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
     lo, hi = _outcomes(model, label_range)
     e = torch.as_tensor(edges, dtype=torch.float32, device=z.device)
@@ -378,7 +381,9 @@ def score_histogram(model, z: torch.Tensor, edges: torch.Tensor, label_range: Op
         e = e[None, :].expand(hi - lo, -1)
     if e.dim() != 2 or e.shape[0] != hi - lo:
         raise ValueError(f"edges: expected [B] or [{hi - lo}, B], got {tuple(e.shape)}")
-    return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible)
+    if known is None:
+        return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible)
+    return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible, split=_exclusion(known, model))
 
 
 def _cuts(thresholds, n_out: int, device) -> torch.Tensor:
@@ -465,21 +470,31 @@ def pairs_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[
 
 
 @torch.no_grad()
-def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optional[Tuple[int, int]] = None,
+                known: Optional[torch.Tensor] = None) -> torch.Tensor:
     """For every query ``scores[l, q]`` the number of strict-lower-triangle pairs (i > j) of outcome l that score strictly less
     -> int64 [L', Q].  Any Q; the queries may be unsorted and repeated.  Per outcome they are sorted and deduplicated, the
     counting sweep (``decoder.bincount``, lower-triangle mode) runs once per chunk of at most ``ops.bilinear_bincount_max_edges()``
     edges, the cumulative sum of a chunk's counts is the answer for its edges (chunks are independent: bin 0 of every chunk
     already holds everything below its first edge), and the answers are scattered back to the queries' places.
+    ``known``: a ``known_pairs_mask`` -> int64 [2, L', Q]: the novel pairs (``[0]``) and the known pairs (``[1]``) below every query,
+    counted separately in the same sweeps; ``result.sum(0)`` is the answer without ``known``.
     Multi-GPU: pass the rank's outcome shard as ``label_range``."""
+    return _count_below(model, z, scores, label_range, known)[0]
+
+
+def _count_below(model, z, scores, label_range, known):
+    """``count_below`` -> (its result, the row sums of the first chunk's count table(s): the number of eligible pairs per outcome
+    [L'], or per class and outcome [2, L']; None when no sweep ran)."""
     lo, hi = _outcomes(model, label_range)
     s = torch.as_tensor(scores, dtype=torch.float32, device=z.device)
     if s.dim() != 2 or s.shape[0] != hi - lo:
         raise ValueError(f"scores: expected [{hi - lo}, Q], got {tuple(s.shape)}")
     L, Q = s.shape
-    less = torch.zeros((L, Q), dtype=torch.int64, device=z.device)
+    split = _exclusion(known, model)
+    less = torch.zeros((L, Q) if split is None else (2, L, Q), dtype=torch.int64, device=z.device)
     if L == 0 or Q == 0:
-        return less
+        return less, None
     if not bool(torch.isfinite(s).all()):
         raise ValueError("scores: queries must be finite")
     sv, order = torch.sort(s, dim=1)
@@ -489,14 +504,103 @@ def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optio
     U = int(pos.max()) + 1
     uniq = sv[:, -1:].expand(L, U).clone()                      # outcomes with fewer distinct values: the largest one repeated (empty bins)
     uniq.scatter_(1, pos, sv)
-    below = torch.empty((L, U), dtype=torch.int64, device=z.device)
+    below = torch.empty(less.shape[:-1] + (U,), dtype=torch.int64, device=z.device)
     step = ops.bilinear_bincount_max_edges()
+    totals = None
     for c0 in range(0, U, step):
         c1 = min(U, c0 + step)
-        counts = model.decoder.bincount(z, z, uniq[:, c0:c1].contiguous(), (lo, hi), eligible="lower")
-        below[:, c0:c1] = torch.cumsum(counts, 1)[:, : c1 - c0]
-    less.scatter_(1, order, torch.gather(below, 1, pos))
-    return less
+        if split is None:
+            counts = model.decoder.bincount(z, z, uniq[:, c0:c1].contiguous(), (lo, hi), eligible="lower")
+        else:
+            counts = model.decoder.bincount(z, z, uniq[:, c0:c1].contiguous(), (lo, hi), eligible="lower", split=split)
+        below[..., c0:c1] = torch.cumsum(counts, -1)[..., : c1 - c0]
+        totals = counts.sum(-1) if totals is None else totals
+    if split is None:
+        less.scatter_(1, order, torch.gather(below, 1, pos))
+    else:
+        less.scatter_(2, order.expand(2, -1, -1), torch.gather(below, 2, pos.expand(2, -1, -1)))
+    return less, totals
+
+
+def recovery_from_counts(less_all: torch.Tensor, less_known: torch.Tensor, total, n_known) -> dict:
+    """How well a score cut recovers the known network, from counts -> dict of ``selected``, ``hits`` (int64) and ``precision``,
+    ``recall``, ``enrichment`` (float64), all of ``less_all``'s shape.  ``less_all`` / ``less_known``: the number of all / of the known
+    pairs scoring strictly below the cut (``count_below(known=)``: ``[0] + [1]`` and ``[1]``); ``total`` / ``n_known``: the number of
+    all / of the known pairs (ints or tensors that broadcast, e.g. ``[L', 1]``).
+      selected = total - less_all            pairs at or above the cut
+      hits = n_known - less_known            known pairs among them
+      precision = hits / selected            (NaN where nothing is selected)
+      recall = hits / n_known                (NaN where nothing is known)
+      enrichment = precision / (n_known / total)       over the base rate of known pairs
+    A pure tensor function (CPU or GPU)."""
+    la, lk = torch.as_tensor(less_all).to(torch.int64), torch.as_tensor(less_known).to(torch.int64)
+    tot = torch.as_tensor(total, device=la.device).to(torch.int64)
+    nk = torch.as_tensor(n_known, device=la.device).to(torch.int64)
+    selected = tot - la
+    hits = nk - lk
+    selected, hits, tot_b, nk_b = torch.broadcast_tensors(selected, hits, tot, nk)
+    nan = torch.full(selected.shape, float("nan"), dtype=torch.float64, device=la.device)
+    precision = torch.where(selected == 0, nan, hits.double() / selected.double())
+    recall = torch.where(nk_b == 0, nan, hits.double() / nk_b.double())
+    enrichment = precision / (nk_b.double() / tot_b.double())
+    return {"selected": selected.contiguous(), "hits": hits.contiguous(), "precision": precision, "recall": recall, "enrichment": enrichment}
+
+
+@torch.no_grad()
+def recovery_at_cuts(model, z: torch.Tensor, known: torch.Tensor, cuts: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> dict:
+    """How well the ranking of ALL N (N - 1) / 2 pairs recovers the known network -> the dict of ``recovery_from_counts``, every entry
+    [L', B]: for each cut ``cuts[l, b]`` (any order, repeats allowed) the pairs of the strict lower triangle scoring at or above it
+    (``selected``), the known ones among them (``hits``) and the exact precision, recall and enrichment -- over every pair, not over
+    sampled negatives, with no [L', N, N] tensor.  ``known``: a ``known_pairs_mask``.  ``count_below(known=)`` followed by
+    ``recovery_from_counts``; the number of known pairs per outcome is read from the same sweeps (the row sum of a count table is
+    its class's size), so a per-outcome mask needs no side information.  A known pair is scored with the sweep's own arithmetic: it
+    cannot fall on the wrong side of a cut taken from ``top_pairs`` / ``score_histogram``."""
+    lo, hi = _outcomes(model, label_range)
+    c = torch.as_tensor(cuts, dtype=torch.float32, device=z.device)
+    if c.dim() != 2 or c.shape[0] != hi - lo:
+        raise ValueError(f"cuts: expected [{hi - lo}, B], got {tuple(c.shape)}")
+    if _exclusion(known, model) is None:
+        raise ValueError("known: expected a mask from known_pairs_mask")
+    less, totals = _count_below(model, z, c, (lo, hi), known)
+    if totals is None:                                          # no outcome or no cut: nothing was swept
+        totals = torch.zeros((2, c.shape[0]), dtype=torch.int64, device=z.device)
+    return recovery_from_counts(less[0] + less[1], less[1], (totals[0] + totals[1])[:, None], totals[1][:, None])
+
+
+def auroc_bounds_from_counts(counts: torch.Tensor):
+    """Bounds on the AUROC of ranking all eligible pairs with the known ones as positives, from the split counts [2, L', B+1] of
+    ``score_histogram(known=)`` -> ``(lower, upper)`` float64 [L'].  With u = counts[0] (novel), k = counts[1] (known), U = sum u,
+    K = sum k:
+      lower = sum_b k[b] (sum_{b' < b} u[b']) / (K U)        the (known, novel) pairs the bins already order correctly
+      upper = lower + sum_b k[b] u[b] / (K U)                plus those that share a bin
+    The exact AUROC (ties counted 1/2) lies in [lower, upper]; an edge between every two distinct scores makes them meet it where no
+    known and novel pair tie.  The sums are int64 (exact below 2^63: every shape the sweep accepts), then one float64 divide; NaN where
+    K == 0 or U == 0.  A pure tensor function (CPU or GPU)."""
+    c = torch.as_tensor(counts)
+    if c.dim() != 3 or c.shape[0] != 2:
+        raise ValueError(f"counts: expected [2, L', B + 1], got {tuple(c.shape)}")
+    u, k = c[0].to(torch.int64), c[1].to(torch.int64)
+    U, K = u.sum(1), k.sum(1)
+    u_below = torch.cumsum(u, 1) - u                           # novel pairs in lower bins
+    sure = (k * u_below).sum(1)
+    tied = (k * u).sum(1)
+    den = (K * U).double()
+    nan = torch.full_like(den, float("nan"))
+    bad = (K == 0) | (U == 0)
+    lower = torch.where(bad, nan, sure.double() / den)
+    upper = torch.where(bad, nan, (sure + tied).double() / den)
+    return lower, upper
+
+
+@torch.no_grad()
+def auroc_bounds(model, z: torch.Tensor, known: torch.Tensor, edges: torch.Tensor, label_range: Optional[Tuple[int, int]] = None):
+    """Per-outcome AUROC bounds of the model's ranking of ALL strict-lower-triangle pairs against the known network ->
+    ``(lower, upper)`` float64 [L']: ``score_histogram(known=)`` followed by ``auroc_bounds_from_counts`` -- one sweep, no [L', N, N]
+    tensor, no sampled negatives.  More (or better placed) ``edges`` tighten the interval; up to
+    ``ops.bilinear_bincount_max_edges()`` per sweep."""
+    if _exclusion(known, model) is None:
+        raise ValueError("known: expected a mask from known_pairs_mask")
+    return auroc_bounds_from_counts(score_histogram(model, z, edges, label_range, eligible="lower", known=known))
 
 
 PROFILE_CHUNK = 65535          # outcomes per call of the profile sweep (count and best share a register there)

@@ -13,7 +13,7 @@ Shapes: "small" = 4096 x 4096 drugs x 896 outcomes in bf16x3 (BASELINE configs[1
                        screened hits, nearly every score takes the two-compare fast path
   histogram_1000   (d) ops.bilinear_bincount with 1000 evenly spaced edges over the score range: every score is searched
   ranks_of_hits    (e) pipeline.normalized_ranks_of(top_pairs values), end to end (sort, dedupe, sweep, cumsum, scatter)
-  dense_bucketize  (f) the baseline: the dense head on blocks of head rows sized to a 16 GB buffer and torch.searchsorted
+  dense_bucketize  (f) the baseline: the dense head on blocks of head rows sized to an 8 GB buffer (2^31 scores) and torch.searchsorted
                        (right=True, the batched bucketize) + torch.bincount over every block -- every score goes to HBM and comes
                        back.  (It does not even mask the upper triangle.)
 All variants run in one process, alternating round by round; a round times each variant over a window of at least --window
@@ -66,7 +66,7 @@ def bench_shape(N, L, prec, rounds, window_s, baseline_rounds):
         screen = torch.sort(hits, dim=1).values.contiguous()
         top = float(ops.bilinear_allpairs(z, z, w, precision=prec, epilogue=ops.EPI_ROWSTATS)[..., 1].max())
         even = torch.linspace(-top, top, B, device="cuda")[None, :].expand(L, -1).contiguous()
-        block = max(1, min(N, (16 << 30) // (L * N * 4)))
+        block = max(1, min(N, (1 << 31) // (L * N)))      # 2^31 scores: torch.searchsorted cannot be launched over 2^32
         buf = torch.empty(L * block * N, dtype=torch.float32, device="cuda")
         offs = (torch.arange(L, device="cuda", dtype=torch.int32) * (B + 1))[:, None]
 
