@@ -571,6 +571,44 @@ size_t mdg_pair_uniformity_workspace_bytes(int64_t m);
 int mdg_pair_uniformity(const float* x, int64_t m, int64_t d, float t, float* out, int* status, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* ---------------------------------------------------------------------- k-nearest neighbours ---- */
+
+/* For every row i of Q fp32 [nq,128] the k best rows j of Lib fp32 [nl,128] (row-major, 16-byte aligned; 1 <= nq, nl < 2^31 - 128)
+ * and their values: vals fp32 [nq,k], idx int32 [nq,k], ordered by (value best-first, then j ascending) -- a total order, so the
+ * result is unique.  Replaces the dense matrix + topk of madrigal/evaluate/eval_utils.py:196-203 (knn_classifier: distance_matrix /
+ * torch.mm, then similarity.topk) and madrigal/evaluate/evaluate.py:411-418 (the two torch.topk of get_inst_dist_topk_accuracy);
+ * nothing of [nq,nl] is stored.  With g = q_i.l_j (the exact-fp32 MFMA chain of mdg_pair_match_counts, bit for bit):
+ *   MDG_KNN_COSINE     (g * 1/|q_i|) * 1/|l_j|, larger is better (the value mdg_pair_match_counts compares)
+ *   MDG_KNN_DOT        g, larger is better
+ *   MDG_KNN_EUCLIDEAN  ranked on d2 = (|q_i|^2 - 2 g) + |l_j|^2 in fp32, smaller is better; vals = sqrt(max(d2, 0))
+ * 1 <= k <= min(mdg_knn_max_k() = 32, candidates per row).  skip: NULL, or int32 [nq]: the library index query i must not return
+ * (-1: none) -- "the query is itself a row of the library" without a mask; then k <= nl - 1.
+ * segments: the library is cut into that many contiguous ranges of whole 128-column tiles (at most ceil(nl / 128) are used), the grid
+ * is (row blocks of 128) x segments, and a merge by the full key forms the result; 1 writes it directly.  The result is the same
+ * bits for every value.  mdg_knn_default_segments (host only, deterministic, assumes the MI355X's 256 CUs): 1 when the row blocks
+ * alone give 2 workgroups per CU, otherwise enough segments to get there, never more than ceil(nl / 128).
+ * q_stats fp32 [2,nq], lib_stats fp32 [2,nl]: written by the pre-pass (|x|^2, then 1/|x|).  status int32 [1]: OR of 1 (NaN / inf
+ * entry or squared norm) and, for MDG_KNN_COSINE, 2 (zero-norm row); results are meaningless when it is not 0.
+ * workspace: mdg_knn_topk_workspace_bytes (host only; 0 for one segment), 16-byte aligned.  No atomics except the status word.
+ * metric | MDG_KNN_NO_LISTS (measurement): the same sweep with the list epilogue compiled out; vals fp32 [segments used, nq] receives
+ * the row maxima of the values, idx may be NULL, no workspace. */
+enum mdg_knn_metric { MDG_KNN_COSINE = 0, MDG_KNN_DOT = 1, MDG_KNN_EUCLIDEAN = 2, MDG_KNN_NO_LISTS = 256 };
+int mdg_knn_max_k(void);
+int mdg_knn_default_segments(int64_t nq, int64_t nl);
+size_t mdg_knn_topk_workspace_bytes(int64_t nq, int64_t nl, int k, int segments);
+int mdg_knn_topk(const float* q, const float* lib, int64_t nq, int64_t nl, int64_t d, int k, int metric, const int32_t* skip,
+                 int segments, float* q_stats, float* lib_stats, float* vals, int32_t* idx, int* status, void* workspace,
+                 size_t workspace_bytes, void* stream);
+/* The vote of the kNN classifier (madrigal/evaluate/eval_utils.py:205-218: gather of the neighbours' labels, one-hot scatter,
+ * exp(distances / T) weights, sum, sort) on the lists of mdg_knn_topk: w_j = exp(vals[i,j] / T) in fp32 for BOTH metrics (the
+ * reference weights Euclidean neighbours by exp(+distance / T) too).  labels uint8 [nl, n_cols].
+ *   num_classes == 2 (binary, n_cols >= 1 label columns): per query and column p1 = sum_j w_j labels[idx[i,j], c] for j ascending,
+ *     p0 = sum_j w_j - p1; sums fp32 [nq, n_cols, 2] = (p0, p1), pred uint8 [nq, n_cols].
+ *   3 <= num_classes <= 64 (n_cols == 1, labels < num_classes): per-class sums fp32 [nq, num_classes], pred uint8 [nq].
+ * pred = the class with the largest sum, the lowest class on a tie. */
+int mdg_knn_vote(const float* vals, const int32_t* idx, const uint8_t* labels, int64_t nq, int64_t nl, int k, int64_t n_cols,
+                 int num_classes, float T, uint8_t* pred, float* sums, void* stream);
+
 /* ---------------------------------------------------------------------- rank normalisation ---- */
 
 size_t mdg_rank_normalize_workspace_bytes(int64_t n_outcomes, int64_t N);

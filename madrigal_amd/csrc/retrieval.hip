@@ -22,9 +22,7 @@
 // distance test |x_j - y_i|^2 < |x_i - y_i|^2 as fmaf(-2, g_ji, |x_j|^2) < fmaf(-2, g_ii, |x_i|^2) (|y_i|^2 cancels).
 // Ties with the true match do not count against it (strict > and <: "ties count as hits"); the true match itself is
 // excluded by index.  Counts are integers summed without atomics, so every output is bit-identical from run to run.
-#include "mdg_common.h"
-
-#include <math.h>
+#include "gram.h"               // gram_step, norm2_step, finite4: shared with knn.hip
 
 namespace {
 
@@ -36,20 +34,6 @@ constexpr int RT_NCOUNT = 6;         // cos_row, cos_col, dist_row, dist_col, sa
 enum { RT_CROSS = 0, RT_SAME = 1, RT_UNIFORM = 2 };
 
 __device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
-
-// one k step of eight: lane half h holds k = 8 q + 4 h + e (e = 0..3) of its row of A and of B.  Every entry of every block
-// runs the same chain (q ascending, then e), so equal rows give bit-equal products wherever they sit in a tile.
-__device__ __forceinline__ f32x16 gram_step(const float4 a, const float4 b, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
-
-__device__ __forceinline__ bool finite4(const float4 v) {
-  return isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w);
-}
 
 struct RtParams {   // per-row quantities of the pre-pass, [n] each
   float *rx, *ry, *nx2, *ny2, *cthr, *drow, *dcol;
@@ -74,11 +58,11 @@ __global__ __launch_bounds__(RT_THREADS) void rt_prep(const float* __restrict__ 
   for (int q = 0; q < 16; ++q) {
     const float4 a = *reinterpret_cast<const float4*>(xr + 8 * q + 4 * h);
     ok = ok && finite4(a);
-    sx = fmaf(a.x, a.x, sx); sx = fmaf(a.y, a.y, sx); sx = fmaf(a.z, a.z, sx); sx = fmaf(a.w, a.w, sx);
+    sx = norm2_step(a, sx);
     if constexpr (HAS_Y) {
       const float4 b = *reinterpret_cast<const float4*>(yr + 8 * q + 4 * h);
       ok = ok && finite4(b);
-      sy = fmaf(b.x, b.x, sy); sy = fmaf(b.y, b.y, sy); sy = fmaf(b.z, b.z, sy); sy = fmaf(b.w, b.w, sy);
+      sy = norm2_step(b, sy);
       acc = gram_step(a, b, acc);
     }
   }

@@ -2383,3 +2383,120 @@ def pair_uniformity(x: torch.Tensor, t: float = 2.0) -> torch.Tensor:
     call("mdg_pair_uniformity", _ptr(x), m, 128, t, _ptr(out), _ptr(status), _ptr(ws), nbytes, _stream(x))
     _pair_status(status, "pair_uniformity")
     return out
+
+
+# ------------------------------------------------------------------------------- k-nearest neighbours
+KNN_METRICS = {"cosine": 0, "dot": 1, "euclidean": 2}
+_KNN_NO_LISTS = 256
+
+
+def knn_max_k() -> int:
+    """Largest k of ``knn_topk`` (32: one list entry per lane of the 32 lanes that share a query row)."""
+    return int(lib().mdg_knn_max_k())
+
+
+def knn_default_segments(nq: int, nl: int) -> int:
+    """Column segments ``knn_topk`` uses when none are given (host only): 1 when the blocks of 128 query rows alone give every
+    CU two workgroups, otherwise enough segments to get there, at most ceil(nl / 128)."""
+    return int(lib().mdg_knn_default_segments(int(nq), int(nl)))
+
+
+def _knn_args(q, lib_, k, metric, skip, segments, what):
+    q, lib_ = _embeds_128(q, "q"), _embeds_128(lib_, "lib")
+    if q.device != lib_.device:
+        raise ValueError(f"{what}: q and lib must live on one device, got {q.device} and {lib_.device}")
+    if metric not in KNN_METRICS:
+        raise ValueError(f"{what}: unknown metric {metric!r}; expected one of {sorted(KNN_METRICS)}")
+    nq, nl = int(q.shape[0]), int(lib_.shape[0])
+    if nq < 1 or nl < 1:
+        raise ValueError(f"{what}: need at least one query and one library row, got {nq} and {nl}")
+    if skip is not None:
+        if not isinstance(skip, torch.Tensor) or not skip.is_cuda or skip.dtype != torch.int32 or skip.shape != (nq,):
+            raise ValueError(f"{what}: skip must be an int32 GPU tensor of shape [{nq}]")
+        skip = skip.contiguous()
+    k = int(k)
+    cand = nl - (1 if skip is not None else 0)
+    if not 1 <= k <= min(knn_max_k(), cand):
+        raise ValueError(f"{what}: need 1 <= k <= min({knn_max_k()}, {cand} candidates per row), got k = {k} (torch.topk raises for "
+                         "k above the candidates)")
+    if segments is None:
+        segments = knn_default_segments(nq, nl)
+    segments = int(segments)
+    if segments < 1:
+        raise ValueError(f"{what}: segments must be at least 1, got {segments}")
+    return q, lib_, nq, nl, k, skip, segments
+
+
+def knn_topk(q: torch.Tensor, lib_: torch.Tensor, k: int, *, metric: str = "cosine", skip: Optional[torch.Tensor] = None,
+             segments: Optional[int] = None):
+    """The k nearest rows of ``lib_`` fp32 [nl,128] for every row of ``q`` fp32 [nq,128], both on the GPU (csrc/knn.hip,
+    mdg_knn_topk) -> ``(vals fp32 [nq,k], idx int32 [nq,k])`` ordered by (value best-first, library index ascending).
+
+    metric: 'cosine' (larger is better; the value ``pair_match_counts`` compares, bit for bit), 'dot', or 'euclidean' (ranked on the
+    fp32 squared distance, the distance is returned).  skip int32 [nq]: the library row query i must not return (-1: none).
+    segments: column segments of the sweep (default ``knn_default_segments``); the result is the same bits for every value.
+    1 <= k <= min(32, nl - (1 if skip is given else 0)).  One host read (the status word): raises ValueError for NaN / inf entries
+    and, for 'cosine', zero-norm rows."""
+    q, lib_, nq, nl, k, skip, segments = _knn_args(q, lib_, k, metric, skip, segments, "knn_topk")
+    dev = q.device
+    vals = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    qstat = torch.empty((2, nq), dtype=torch.float32, device=dev)
+    lstat = torch.empty((2, nl), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws, nbytes = _scratch("mdg_knn_topk_workspace_bytes", dev, nq, nl, k, segments)
+    call("mdg_knn_topk", _ptr(q), _ptr(lib_), nq, nl, 128, k, KNN_METRICS[metric], _ptr(skip), segments, _ptr(qstat), _ptr(lstat), _ptr(vals),
+         _ptr(idx), _ptr(status), _ptr(ws), nbytes, _stream(q))
+    _pair_status(status, "knn_topk")
+    return vals, idx
+
+
+def knn_sweep_rowmax(q: torch.Tensor, lib_: torch.Tensor, *, metric: str = "cosine", segments: Optional[int] = None) -> torch.Tensor:
+    """Measurement aid (scripts/knn_bench.py): the sweep of ``knn_topk`` with the list epilogue compiled out -> fp32
+    [segments used, nq], each segment's largest value per query (for 'euclidean', of the negated squared distance).  Pre-pass,
+    status word and its host read are ``knn_topk``'s, so the difference of the two is the lists and their merge."""
+    q, lib_, nq, nl, _, _, segments = _knn_args(q, lib_, 1, metric, None, segments, "knn_sweep_rowmax")
+    dev = q.device
+    tiles = -(-nl // 128)
+    per = -(-tiles // min(segments, tiles))
+    out = torch.empty((-(-tiles // per), nq), dtype=torch.float32, device=dev)        # ceil(tiles / per): no segment is empty
+    qstat = torch.empty((2, nq), dtype=torch.float32, device=dev)
+    lstat = torch.empty((2, nl), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    call("mdg_knn_topk", _ptr(q), _ptr(lib_), nq, nl, 128, 1, KNN_METRICS[metric] | _KNN_NO_LISTS, None, segments, _ptr(qstat), _ptr(lstat),
+         _ptr(out), None, _ptr(status), None, 0, _stream(q))
+    _pair_status(status, "knn_sweep_rowmax")                                       # the same host read as knn_topk's
+    return out
+
+
+def knn_vote(vals: torch.Tensor, idx: torch.Tensor, labels: torch.Tensor, T: float, num_classes: int):
+    """The kNN classifier's vote on the lists of ``knn_topk`` (csrc/knn.hip, mdg_knn_vote): weights exp(vals / T) in fp32.
+    labels uint8 on the GPU: [nl] class ids (< num_classes <= 64), or [nl, C] binary columns with num_classes == 2.
+    -> ``(pred uint8, sums fp32)``: [nq] and [nq, num_classes] for a label vector, [nq, C] and [nq, C, 2] for label columns.  With
+    num_classes == 2 the sums are p1 = sum_j w_j label_j (j ascending) and p0 = sum_j w_j - p1; otherwise one sum per class.  The
+    prediction is the class with the largest sum, the lowest class on a tie."""
+    vals = _f32_cuda(vals, "vals", 2)
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.shape != vals.shape:
+        raise ValueError(f"knn_vote: idx must be an int32 GPU tensor of vals' shape {tuple(vals.shape)}")
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.uint8 or labels.dim() not in (1, 2):
+        raise ValueError("knn_vote: labels must be a uint8 GPU tensor of shape [nl] or [nl, C]")
+    num_classes = int(num_classes)
+    if not 2 <= num_classes <= 64:
+        raise ValueError(f"knn_vote: num_classes must be in 2..64, got {num_classes}")
+    if labels.dim() == 2 and num_classes != 2:
+        raise ValueError(f"knn_vote: [nl, C] label columns are binary (num_classes = 2), got num_classes = {num_classes}")
+    T = float(T)
+    if T != T or T == 0.0:
+        raise ValueError("knn_vote: T must be a non-zero number")
+    idx, labels = idx.contiguous(), labels.contiguous()
+    nq, k = int(vals.shape[0]), int(vals.shape[1])
+    nl = int(labels.shape[0])
+    C = int(labels.shape[1]) if labels.dim() == 2 else 1
+    if nl < 1 or C < 1 or not 1 <= k <= knn_max_k():
+        raise ValueError(f"knn_vote: need labels for at least one row and 1 <= k <= {knn_max_k()}, got {tuple(labels.shape)} and k = {k}")
+    dev = vals.device
+    cols = (C,) if labels.dim() == 2 else ()
+    pred = torch.empty((nq,) + cols, dtype=torch.uint8, device=dev)
+    sums = torch.empty((nq,) + cols + (2 if num_classes == 2 else num_classes,), dtype=torch.float32, device=dev)
+    call("mdg_knn_vote", _ptr(vals), _ptr(idx), _ptr(labels), nq, nl, k, C, num_classes, T, _ptr(pred), _ptr(sums), _stream(vals))
+    return pred, sums

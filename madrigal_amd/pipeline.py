@@ -26,6 +26,7 @@ import torch
 from . import ops
 from .data import MoleculeBatch
 from .parallel import all_gather_rows, shard_range
+from .retrieval import nearest_neighbors
 
 
 def slice_molecules(mols: MoleculeBatch, lo: int, hi: int) -> MoleculeBatch:
@@ -242,6 +243,20 @@ def top_partners(model, z: torch.Tensor, k: int, label_range: Optional[Tuple[int
         vals[s - lo:e - lo] = v[:, rows]
         idx[s - lo:e - lo] = i[:, rows]
     return vals, idx
+
+
+@torch.no_grad()
+def similar_drugs(z: torch.Tensor, k: int, rows=None, metric: str = "cosine"):
+    """The ``k`` nearest OTHER drugs of every drug in embedding space -> ``(values fp32 [n, k], indices int64 [n, k])``, ordered by
+    (value best-first, index ascending); ``z`` [N,128] from ``generate_embeddings``.  ``rows``: only these drugs (indices into z;
+    n = their number) -- unlike ``top_partners`` the sweep then visits only their rows.  The drug itself is skipped inside the
+    sweep (``ops.knn_topk``'s ``skip``), so 1 <= k <= min(32, N - 1).  metric: 'cosine', 'dot' or 'euclidean' (``retrieval.
+    nearest_neighbors``); nothing of [n, N] is stored."""
+    z = z.detach().float()
+    N = z.shape[0]
+    sel = _index(rows, N, "rows", z.device)
+    skip = (torch.arange(N, device=z.device) if sel is None else sel).to(torch.int32)
+    return nearest_neighbors(z if sel is None else z[sel], z, k, metric=metric, skip=skip)
 
 
 def _best_pairs(v: torch.Tensor, i: torch.Tensor, j: torch.Tensor, K: int, N: int):

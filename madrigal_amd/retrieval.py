@@ -11,6 +11,11 @@ Ties: a competitor exactly as close as the true match does not count against it 
 such ties in an unspecified order; they do not arise with real-valued embeddings.  The accuracies are computed in fp32 with the
 reference's own expressions, so they equal its numbers exactly whenever the counts agree.
 
+Which rows are nearest -- the reference's ``knn_classifier`` (eval_utils.py:177-229) and the index tensors of
+``get_inst_dist_topk_accuracy`` -- is a second sweep (``ops.knn_topk``, csrc/knn.hip) that keeps each query's k best in registers:
+``nearest_neighbors``, ``inst_dist_topk_indices``, ``knn_predict`` / ``knn_classifier``.  Its similarities are the counting sweep's
+bit for bit, and equal values are ordered by ascending index.
+
 CPU tensors are moved to the current CUDA device (as ``metrics.get_metrics`` does with numpy input)."""
 from __future__ import annotations
 
@@ -75,6 +80,70 @@ def get_inst_dist_topk_accuracy(embeds1, embeds2, k: int, metric: str = "cosine"
     acc = topk_from_counts(counts, [("one", int(k))] + [("both", kk) for kk in (20, 5, 1)])
     vals = torch.stack([acc[("one", int(k))], acc[("both", 20)], acc[("both", 5)], acc[("both", 1)]]).tolist()
     return vals[0], vals[1], vals[2], vals[3], None, None
+
+
+def nearest_neighbors(queries, library, k: int, metric: str = "cosine", skip=None):
+    """The ``k`` rows of ``library`` [nl,128] nearest to every row of ``queries`` [nq,128] -> ``(values fp32 [nq,k], indices int64
+    [nq,k])`` on the device, ordered by (value best-first, library index ascending).  metric: 'cosine' or 'dot' (similarities,
+    largest first) or 'euclidean' (distances, smallest first).  ``skip`` [nq]: the library row each query must not return (-1:
+    none), for queries that are themselves in the library.  One sweep (``ops.knn_topk``, csrc/knn.hip): no [nq,nl] matrix exists,
+    so 100 000 queries against 100 000 rows need the two inputs and the result, not 40 GB.  1 <= k <= 32."""
+    q, lib = _dev(queries).float(), _dev(library).float()
+    if skip is not None:
+        skip = _dev(skip).to(device=q.device, dtype=torch.int32).reshape(-1)
+    vals, idx = ops.knn_topk(q, lib.to(q.device), int(k), metric=metric, skip=skip)
+    return vals, idx.long()
+
+
+def inst_dist_topk_indices(embeds1, embeds2, k: int):
+    """evaluate.py:417-418 -> ``(topk_rows, topk_cols)`` int64 [n,k] on the device: the two values ``get_inst_dist_topk_accuracy``
+    leaves out.  Row i of ``topk_rows`` holds the k rows of embeds2 most cosine-similar to embeds1[i], row j of ``topk_cols`` the k
+    rows of embeds1 most similar to embeds2[j], most similar first and, unlike ``torch.topk``, equal similarities by ascending
+    index.  The similarities are the ones ``pair_counts`` compares, bit for bit: index i sits at position cos_row[i] of row i
+    whenever cos_row[i] < k (no competitor ties with the true match)."""
+    x, y = _dev(embeds1).float(), _dev(embeds2).float()
+    _need_k(int(k), int(y.shape[0]), "inst_dist_topk_indices")
+    return nearest_neighbors(x, y, k)[1], nearest_neighbors(y, x, k)[1]
+
+
+def _labels_u8(labels, num_classes: int, what: str) -> torch.Tensor:
+    lab = _dev(labels)
+    if lab.dim() not in (1, 2) or lab.is_floating_point() and bool((lab != lab.round()).any()):
+        raise ValueError(f"{what}: labels must be integers of shape [n] or [n, C], got {tuple(lab.shape)} {lab.dtype}")
+    if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= num_classes):
+        raise ValueError(f"{what}: labels must lie in [0, {num_classes}), got [{int(lab.min())}, {int(lab.max())}]")
+    return lab.to(torch.uint8).contiguous()
+
+
+def knn_predict(train_features, train_labels, test_features, metric: str = "cosine", k: int = 5, T: float = 1, num_classes: int = 2):
+    """The kNN classifier of eval_utils.py:177-229 without the scoring -> ``(predictions uint8, class sums fp32)`` on the device:
+    [n_test] and [n_test, num_classes] for a label vector, [n_test, C] and [n_test, C, 2] for [n_train, C] binary labels (one
+    neighbour search serves every column).  Neighbours by ``nearest_neighbors`` ('cosine' or 'euclidean'), weights
+    exp(value / T) -- for 'euclidean' too, as the reference has it -- and the class with the largest weight sum, the lowest class
+    on a tie (the reference's sort leaves ties open)."""
+    if metric not in ("cosine", "euclidean"):
+        raise NotImplementedError(f"knn_classifier: unknown metric {metric!r}")
+    lab = _labels_u8(train_labels, int(num_classes), "knn_classifier")
+    train = _dev(train_features).float()
+    if lab.shape[0] != train.shape[0]:
+        raise ValueError(f"knn_classifier: {train.shape[0]} training rows but {lab.shape[0]} labels")
+    _need_k(int(k), int(train.shape[0]), "knn_classifier")
+    q = _dev(test_features).float()
+    vals, idx = ops.knn_topk(q, train.to(q.device), int(k), metric=metric)
+    return ops.knn_vote(vals, idx, lab.to(q.device), float(T), int(num_classes))
+
+
+def knn_classifier(train_features, train_labels, test_features, test_labels, metric='cosine', k=5, T=1, num_classes=2):
+    """eval_utils.py:177-229 (kNN ATC classification of the pretrained embeddings) -> top-1 accuracy as a Python float.  With
+    [n, C] binary labels: an fp32 [C] device tensor of per-label accuracies from ONE neighbour search (the reference's docstring
+    asks for per-label reporting and pays for it with C calls).  See ``knn_predict``."""
+    pred, _ = knn_predict(train_features, train_labels, test_features, metric=metric, k=k, T=T, num_classes=num_classes)
+    target = _labels_u8(test_labels, int(num_classes), "knn_classifier").to(pred.device)
+    if target.shape != pred.shape:
+        raise ValueError(f"knn_classifier: test labels of shape {tuple(target.shape)} for predictions of shape {tuple(pred.shape)}")
+    correct = (pred == target).sum(0)
+    n = int(pred.shape[0])
+    return int(correct) / n if pred.dim() == 1 else topk_fraction(correct, n)
 
 
 def foscttm_from_counts(closer: torch.Tensor):
