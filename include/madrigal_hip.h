@@ -609,6 +609,46 @@ int mdg_knn_topk(const float* q, const float* lib, int64_t nq, int64_t nl, int64
 int mdg_knn_vote(const float* vals, const int32_t* idx, const uint8_t* labels, int64_t nq, int64_t nl, int k, int64_t n_cols,
                  int num_classes, float T, uint8_t* pred, float* sums, void* stream);
 
+/* ---------------------------------------------------------------------- GeomCA ---- */
+
+/* The epsilon-graph evaluation of madrigal/evaluate/GeomCA.py over [n,128] fp32 embeddings (row-major, 16-byte aligned, 1 <= n <
+ * 2^31 - 128), decided in squared-distance space: d2(x, y) = max(fmaf(-2, g(x,y), n(x) + n(y)), 0) in fp32, g the exact-fp32 MFMA
+ * chain of mdg_pair_match_counts and n(x) = g(x, x) formed by that chain.  d2 is the same bits seen from either row, and bitwise
+ * equal rows are at d2 == 0 exactly.  No [n,n] matrix and no edge list is stored.  The thresholds are float32(delta * delta) and
+ * float32(epsilon * epsilon), formed by the caller in double.  segments: column segments of a sweep; 0 = the default
+ * (mdg_geomca_default_segments, host only, assumes 256 CUs); results are the same for every value (integer atomics only). */
+int mdg_geomca_default_chunk(void);
+int mdg_geomca_default_segments(int64_t nrow, int64_t ncol);
+/* norms fp32 [n] = n(x) (the diagonal of 32-row Gram tiles).  status int32 [1]: 1 when an entry or a norm is NaN / inf; the results
+ * of the calls below are meaningless then.  Every call below takes the norms of its inputs from here. */
+int mdg_geomca_prep(const float* x, int64_t n, int64_t d, float* norms, int* status, void* stream);
+/* GeomCA.py:333-352 (get_sparse_pnts: gudhi.subsampling.sparsify_point_set): walking the rows in input order, row i is kept iff no
+ * KEPT row j < i has d2(i, j) < delta2 (strict): the lexicographically first delta-separated subset.  kept_idx int32 [n] receives
+ * the kept input rows, ascending, in its first count[0] entries (count: device int32 [1]).  chunk: candidates resolved per step, a
+ * multiple of 128 in 128..512; the result is the same for every chunk.  Launches O(n / chunk), no host read.
+ * workspace: mdg_geomca_sparsify_workspace_bytes (host only): the compacted kept rows and norms, the chunk's flags and bit matrix. */
+size_t mdg_geomca_sparsify_workspace_bytes(int64_t n, int chunk);
+int mdg_geomca_sparsify(const float* x, int64_t n, int64_t d, const float* norms, float delta2, int chunk, int segments, int32_t* kept_idx,
+                        int* count, void* workspace, size_t workspace_bytes, void* stream);
+/* GeomCA.py:354-387 and :423-435 (RipsComplex 1-skeleton, networkx graph, connected_components, extract_subnetworks): vertices
+ * v [n,128], the first n_r of them the R set; edge {i, j}, i != j, iff d2(i, j) <= eps2 (non-strict).  label int32 [n]: the smallest
+ * vertex index of i's connected component; deg_same / deg_cross int32 [n]: i's neighbours in its own set / in the other set.
+ * Hooking + pointer jumping between sweeps; sweeps_host (HOST int [1]) receives the number of sweeps (the last one finds nothing to
+ * change).  Reads one flag per sweep (synchronises the stream).  workspace: mdg_geomca_components_workspace_bytes (host only). */
+size_t mdg_geomca_components_workspace_bytes(int64_t n);
+int mdg_geomca_components(const float* v, int64_t n, int64_t n_r, int64_t d, const float* norms, float eps2, int segments, int32_t* label,
+                          int32_t* deg_same, int32_t* deg_cross, int* sweeps_host, void* workspace, size_t workspace_bytes, void* stream);
+/* GeomCA.py:250-282 (estimate_distance: cdist of two drawn row sets, distances > 0, np.percentile): x [mx,128], y [my,128] are the
+ * gathered rows and ids_x / ids_y int32 the input rows they were drawn from.  Over the pairs with ids_x[a] != ids_y[b]:
+ * counts_host (HOST int64 [2]) = {pairs at d2 == 0, M = pairs at d2 > 0}; values_host (HOST double [3]) = {D[k], D[k + 1], pos}, the
+ * exact order statistics of the positive d2 values at pos = percentile / 100 * (M - 1), k = floor(pos), k + 1 clamped to M - 1
+ * (zeros when M == 0).  A radix select on the fp32 bit pattern, 11 + 11 + 10 bits: three sweeps, one histogram read each
+ * (synchronises the stream).  workspace: mdg_geomca_distance_select_workspace_bytes (host only). */
+size_t mdg_geomca_distance_select_workspace_bytes(void);
+int mdg_geomca_distance_select(const float* x, const float* y, const int32_t* ids_x, const int32_t* ids_y, int64_t mx, int64_t my, int64_t d,
+                               const float* x_norms, const float* y_norms, double percentile, int segments, int64_t* counts_host,
+                               double* values_host, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------- rank normalisation ---- */
 
 size_t mdg_rank_normalize_workspace_bytes(int64_t n_outcomes, int64_t N);

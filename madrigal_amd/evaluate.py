@@ -232,3 +232,44 @@ def evaluate_pt(model, drugs, masks, too_hard_neg_mask, collator, split, wandb, 
         if logger is not None:
             logger.info(f"{split} alignment loss str v {name}: {alignment_l}")
     return all_embeds
+
+
+# ------------------------------------------------------------------------------------------------- final embeddings: GeomCA
+# madrigal/evaluate/evaluate.py:456-504 (evaluate_final_embeds, get_alignment_metrics) on the ``all_embeds`` dicts of evaluate_pt.
+# The reference stacks the shared drugs' rows on the host and runs GeomCA through GUDHI and networkx; here ``retrieval.geomca``
+# runs on the device.  ``save_dir`` is accepted and nothing is written: no plots, pickles or logs.
+def get_alignment_metrics(pair_name, outputs_subset1, outputs_subset2, save_dir, wandb, logger, epoch, parameters=None):
+    """Drop-in for evaluate.py:464-504: GeomCA of the two modalities' embeddings over their shared drugs (``np.intersect1d``:
+    sorted by drug id), one ``wandb.log`` of precision, recall, network consistency, network quality and sample size with
+    ``step=epoch``.  ``outputs_subset*``: {'embeds': CPU or CUDA tensor [n,128], 'drugs': ids [n]}.  ``parameters`` overrides
+    ``retrieval.GEOMCA_DEFAULTS``.  Returns GeomCA's ``(comp_stats, network_stats, network_params)`` (the reference returns None)."""
+    drugs1, drugs2 = np.asarray(outputs_subset1["drugs"]), np.asarray(outputs_subset2["drugs"])
+    pos1 = {d: i for i, d in enumerate(drugs1.tolist())}
+    pos2 = {d: i for i, d in enumerate(drugs2.tolist())}
+    valid_drugs = np.intersect1d(drugs1, drugs2)
+    if valid_drugs.size == 0:
+        raise ValueError(f"get_alignment_metrics: {pair_name}: the two subsets share no drug")
+    rows = []
+    for embeds, pos in ((outputs_subset1["embeds"], pos1), (outputs_subset2["embeds"], pos2)):
+        embeds = torch.as_tensor(embeds)
+        sel = torch.tensor([pos[d] for d in valid_drugs.tolist()], dtype=torch.int64, device=embeds.device)
+        rows.append(embeds.index_select(0, sel))
+    results = RT.geomca(rows[0], rows[1], **(parameters or {}))
+    net = results[1]
+    wandb.log({f"{pair_name} GeomCA precision": net["precision"], f"{pair_name} GeomCA recall": net["recall"],
+               f"{pair_name} GeomCA network consistency": net["network_consistency"],
+               f"{pair_name} GeomCA network quality": net["network_quality"], f"{pair_name} GeomCA sample size": len(valid_drugs)},
+              step=epoch)
+    if logger is not None:
+        logger.info(f"GeomCA evaluation...\n{pair_name} precision: {net['precision']}, recall: {net['recall']}, network consistency: "
+                    f"{net['network_consistency']}, network quality: {net['network_quality']}, sample size: {len(valid_drugs)}")
+    return results
+
+
+def evaluate_final_embeds(train_outputs, val_outputs, save_dir, wandb, logger, epoch):
+    """Drop-in for evaluate.py:456-461: ``get_alignment_metrics`` for every pair of modalities of the train and of the val
+    ``all_embeds`` dict (``evaluate_pt``'s return value), named 'train <m1> v <m2>' / 'val <m1> v <m2>'."""
+    from itertools import combinations
+    for split, outputs in (("train", train_outputs), ("val", val_outputs)):
+        for (key1, subset1), (key2, subset2) in combinations(outputs.items(), 2):
+            get_alignment_metrics(f"{split} {NUMBER2MODALITY[key1]} v {NUMBER2MODALITY[key2]}", subset1, subset2, save_dir, wandb, logger, epoch)

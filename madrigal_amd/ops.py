@@ -2500,3 +2500,133 @@ def knn_vote(vals: torch.Tensor, idx: torch.Tensor, labels: torch.Tensor, T: flo
     sums = torch.empty((nq,) + cols + (2 if num_classes == 2 else num_classes,), dtype=torch.float32, device=dev)
     call("mdg_knn_vote", _ptr(vals), _ptr(idx), _ptr(labels), nq, nl, k, C, num_classes, T, _ptr(pred), _ptr(sums), _stream(vals))
     return pred, sums
+
+
+# ------------------------------------------------------------------------------- GeomCA
+def geomca_default_chunk() -> int:
+    """Candidates ``geomca_sparsify`` resolves per step when ``chunk`` is not given (host only)."""
+    return int(lib().mdg_geomca_default_chunk())
+
+
+def geomca_default_segments(nrow: int, ncol: int) -> int:
+    """Column segments a GeomCA sweep of ``nrow`` rows over ``ncol`` columns uses when none are given (host only)."""
+    return int(lib().mdg_geomca_default_segments(int(nrow), int(ncol)))
+
+
+def _geomca_segments(segments, what: str) -> int:
+    if segments is None:
+        return 0
+    segments = int(segments)
+    if segments < 1:
+        raise ValueError(f"{what}: segments must be at least 1, got {segments}")
+    return segments
+
+
+def _geomca_threshold(value, name: str, what: str) -> float:
+    """float32(value * value), the product formed in float64: the threshold the kernels compare the fp32 d2 with."""
+    value = float(value)
+    if not (value == value and 0.0 <= value < float("inf")):
+        raise ValueError(f"{what}: {name} must be a finite number >= 0, got {value}")
+    thr = float(torch.tensor(value * value, dtype=torch.float64).to(torch.float32))     # round to nearest even
+    if thr == float("inf"):
+        raise ValueError(f"{what}: {name}^2 = {value * value} does not fit float32")
+    return thr
+
+
+def _geomca_ids(ids, m: int, name: str, device) -> torch.Tensor:
+    if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dtype not in (torch.int32, torch.int64) or ids.shape != (m,):
+        raise ValueError(f"geomca_distance_select: {name} must be an int32 or int64 GPU tensor of shape [{m}]")
+    return ids.to(device=device, dtype=torch.int32).contiguous()
+
+
+def geomca_prep(x: torch.Tensor, what: str = "geomca_prep") -> torch.Tensor:
+    """fp32 [n] Gram-chain squared norms n(x) = g(x, x) of x fp32 [n,128] on the GPU (csrc/geomca.hip, mdg_geomca_prep): the
+    diagonal of the same MFMA chain that forms g(x, y), so d2(x, y) = max(fmaf(-2, g, n(x) + n(y)), 0) is exactly 0 for bitwise
+    equal rows.  One host read (the status word): raises ValueError for NaN / inf entries."""
+    x = _embeds_128(x, "x")
+    n = int(x.shape[0])
+    if n < 1:
+        raise ValueError(f"{what}: need at least one row")
+    norms = torch.empty(n, dtype=torch.float32, device=x.device)
+    status = torch.empty(1, dtype=torch.int32, device=x.device)
+    call("mdg_geomca_prep", _ptr(x), n, 128, _ptr(norms), _ptr(status), _stream(x))
+    _pair_status(status, what)
+    return norms
+
+
+def geomca_sparsify(x: torch.Tensor, delta: float, *, chunk: Optional[int] = None, segments: Optional[int] = None) -> torch.Tensor:
+    """GeomCA's geometric sparsification (GeomCA.py:333-352, GUDHI's sparsify_point_set) of x fp32 [n,128] on the GPU
+    (csrc/geomca.hip, mdg_geomca_sparsify) -> int64 [kept], the kept input rows, ascending.  Walking the rows in input order, row
+    i is kept iff no KEPT row j < i has d2(i, j) < float32(delta^2): the lexicographically first delta-separated subset; a dropped
+    row never drops anyone.  chunk: candidates resolved per step (a multiple of 128 in 128..512, default
+    ``geomca_default_chunk()``); segments: column segments of the sweeps; the result is the same for every value of both.  Two
+    host reads (the status word, the kept count).  Raises ValueError for NaN / inf entries."""
+    x = _embeds_128(x, "x")
+    n = int(x.shape[0])
+    if n < 1:
+        raise ValueError("geomca_sparsify: need at least one row")
+    thr = _geomca_threshold(delta, "delta", "geomca_sparsify")
+    chunk = geomca_default_chunk() if chunk is None else int(chunk)
+    if chunk < 128 or chunk > 512 or chunk % 128:
+        raise ValueError(f"geomca_sparsify: chunk must be a multiple of 128 in 128..512, got {chunk}")
+    segments = _geomca_segments(segments, "geomca_sparsify")
+    norms = geomca_prep(x, "geomca_sparsify")
+    dev = x.device
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws, nbytes = _scratch("mdg_geomca_sparsify_workspace_bytes", dev, n, chunk)
+    call("mdg_geomca_sparsify", _ptr(x), n, 128, _ptr(norms), thr, chunk, segments, _ptr(kept), _ptr(count), _ptr(ws), nbytes, _stream(x))
+    return kept[:int(count.item())].long()
+
+
+def geomca_components(v: torch.Tensor, n_r: int, epsilon: float, *, segments: Optional[int] = None):
+    """Connected components and degrees of the epsilon-graph on the vertices v fp32 [n,128] (the first ``n_r`` are the R set) on
+    the GPU (csrc/geomca.hip, mdg_geomca_components; GeomCA.py:354-387, :423-435) -> ``(label int32 [n], deg_same int32 [n],
+    deg_cross int32 [n], sweeps)``.  Edge {i, j}, i != j, iff d2(i, j) <= float32(epsilon^2).  label[i]: the smallest vertex index
+    of i's component; deg_same / deg_cross: i's neighbours in its own / in the other set; sweeps: link sweeps run (hooking and
+    pointer jumping in between; the last sweep finds nothing to change).  The result is the same for every ``segments``.  Raises
+    ValueError for NaN / inf entries."""
+    v = _embeds_128(v, "v")
+    n, n_r = int(v.shape[0]), int(n_r)
+    if n < 1 or not 0 <= n_r <= n:
+        raise ValueError(f"geomca_components: need at least one vertex and 0 <= n_r <= n, got n = {n}, n_r = {n_r}")
+    thr = _geomca_threshold(epsilon, "epsilon", "geomca_components")
+    segments = _geomca_segments(segments, "geomca_components")
+    norms = geomca_prep(v, "geomca_components")
+    dev = v.device
+    label, deg_same, deg_cross = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    sweeps = ctypes.c_int(0)
+    ws, nbytes = _scratch("mdg_geomca_components_workspace_bytes", dev, n)
+    call("mdg_geomca_components", _ptr(v), n, n_r, 128, _ptr(norms), thr, segments, _ptr(label), _ptr(deg_same), _ptr(deg_cross),
+         ctypes.addressof(sweeps), _ptr(ws), nbytes, _stream(v))
+    return label, deg_same, deg_cross, int(sweeps.value)
+
+
+def geomca_distance_select(x: torch.Tensor, y: torch.Tensor, ids_x: torch.Tensor, ids_y: torch.Tensor, percentile: float, *,
+                           segments: Optional[int] = None):
+    """The order statistics GeomCA's epsilon estimate needs (GeomCA.py:250-282: cdist, distances > 0, np.percentile) without the
+    distance matrix (csrc/geomca.hip, mdg_geomca_distance_select).  x fp32 [mx,128], y fp32 [my,128]: the drawn rows; ids_x, ids_y:
+    the input rows they were drawn from.  Over the pairs with ids_x[a] != ids_y[b] -> ``(zeros, M, d2_lo, d2_hi, pos)``: the pairs
+    at d2 == 0, the pairs at d2 > 0, and the exact order statistics D[k], D[k + 1] (k + 1 clamped to M - 1) of the positive fp32 d2
+    values at numpy's linear-interpolation position pos = percentile / 100 * (M - 1), k = floor(pos).  A radix select on the fp32
+    bit pattern: three sweeps, three small host reads.  M == 0 returns zeros for the values.  Raises ValueError for NaN / inf."""
+    x, y = _embeds_128(x, "x"), _embeds_128(y, "y")
+    if x.device != y.device:
+        raise ValueError(f"geomca_distance_select: x and y must live on one device, got {x.device} and {y.device}")
+    mx, my = int(x.shape[0]), int(y.shape[0])
+    if mx < 1 or my < 1:
+        raise ValueError(f"geomca_distance_select: need at least one row on each side, got {mx} and {my}")
+    percentile = float(percentile)
+    if not 0.0 <= percentile <= 100.0:
+        raise ValueError(f"geomca_distance_select: percentile must lie in [0, 100], got {percentile}")
+    segments = _geomca_segments(segments, "geomca_distance_select")
+    dev = x.device
+    ids_x, ids_y = _geomca_ids(ids_x, mx, "ids_x", dev), _geomca_ids(ids_y, my, "ids_y", dev)
+    xn = geomca_prep(x, "geomca_distance_select")
+    yn = xn if y.data_ptr() == x.data_ptr() and mx == my else geomca_prep(y, "geomca_distance_select")
+    counts = (ctypes.c_int64 * 2)()
+    values = (ctypes.c_double * 3)()
+    ws, nbytes = _scratch("mdg_geomca_distance_select_workspace_bytes", dev)
+    call("mdg_geomca_distance_select", _ptr(x), _ptr(y), _ptr(ids_x), _ptr(ids_y), mx, my, 128, _ptr(xn), _ptr(yn), percentile, segments,
+         ctypes.addressof(counts), ctypes.addressof(values), _ptr(ws), nbytes, _stream(x))
+    return int(counts[0]), int(counts[1]), float(values[0]), float(values[1]), float(values[2])

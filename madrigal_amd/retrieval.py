@@ -171,3 +171,116 @@ def alignment_loss(x1, x2, alpha=2):
     """eval_utils.py:153-156: mean_i |x^1_i - x^2_i|^alpha -> 0-dim fp32 device tensor (per-row terms of ``ops.pair_match_counts``)."""
     align = pair_counts(x1, x2)["align"]
     return align.mean() if alpha == 2 else align.sqrt().pow(alpha).mean()
+
+
+# ------------------------------------------------------------------------------------------------- GeomCA
+# madrigal/evaluate/GeomCA.py with the parameters of get_alignment_metrics (evaluate.py:481-496; random_seed = SEED = 42).  The
+# reference copies the embeddings to the host and goes through GUDHI (k-d tree sparsification, Rips complex) and networkx; here the
+# geometry is three kinds of sweeps over squared distances (ops.geomca_*, csrc/geomca.hip) and only O(n) index arrays reach the host.
+GEOMCA_DEFAULTS = dict(Rdist_ratio=1.0, Rdist_percentile=5, gamma=1, reduceR=True, reduceE=True, sparsify=True, n_Rsamples=None,
+                       n_Esamples=None, comp_consistency_threshold=0.0, comp_quality_threshold=0.0, random_seed=42)
+_GEOMCA_IGNORED = ("experiment_path", "experiment_filename_prefix", "subfolder", "log_reduced")      # nothing is written
+
+
+def geomca_epsilon(R: torch.Tensor, Rdist_ratio: float, Rdist_percentile: float) -> float:
+    """GeomCA.estimate_distance (GeomCA.py:250-282): m = int(nR * Rdist_ratio) rows drawn twice with ``np.random.choice`` from
+    numpy's global generator, in the reference's order; the percentile of the positive distances among the m x m pairs, by numpy's
+    linear interpolation between two exact order statistics of the fp32 squared distances (``ops.geomca_distance_select``).  Pairs
+    whose two draws are the same row are left out (their distance is 0 in the reference)."""
+    n = int(R.shape[0])
+    m = int(n * Rdist_ratio)
+    if m < 1:
+        raise ValueError(f"geomca: Rdist_ratio = {Rdist_ratio} leaves no estimation points of {n} rows")
+    i1 = torch.from_numpy(np.random.choice(n, m)).to(R.device)
+    i2 = torch.from_numpy(np.random.choice(n, m)).to(R.device)
+    _, M, lo, hi, pos = ops.geomca_distance_select(R.index_select(0, i1), R.index_select(0, i2), i1, i2, float(Rdist_percentile))
+    if M == 0:
+        raise ValueError("geomca: every estimation pair is at distance 0; epsilon cannot be estimated (np.percentile of an empty array)")
+    a, b = float(np.sqrt(lo)), float(np.sqrt(hi))
+    return a + (b - a) * (pos - float(np.floor(pos)))
+
+
+def geomca_scores(label, deg_same, deg_cross, n_r: int, comp_consistency_threshold: float = 0.0, comp_quality_threshold: float = 0.0):
+    """Component and network scores (GeomCA.py:392-471, :215-223) from the arrays of ``ops.geomca_components`` ->
+    ``(comp_stats, network_stats)``.  Components by size descending, then smallest vertex ascending."""
+    label, ds, dc = (np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t).astype(np.int64) for t in (label, deg_same, deg_cross))
+    n = label.size
+    n_e = n - n_r
+    roots, inv, sizes = np.unique(label, return_inverse=True, return_counts=True)           # roots ascend
+    inv = inv.reshape(-1)
+    is_r = np.arange(n) < n_r
+    r_cnt = np.bincount(inv, weights=is_r, minlength=roots.size).astype(np.int64)
+    e_cnt = sizes - r_cnt
+    deg2 = np.bincount(inv, weights=ds + dc, minlength=roots.size).astype(np.int64)       # every edge counted from both ends
+    cross2 = np.bincount(inv, weights=dc, minlength=roots.size).astype(np.int64)
+    if (deg2 % 2).any() or (cross2 % 2).any():
+        raise RuntimeError("geomca: the degree sums of a component are odd (the neighbour relation is not symmetric)")
+    members = np.split(np.argsort(inv, kind="stable"), np.cumsum(sizes)[:-1])
+    comp_stats = {}
+    net = {"num_R_points_in_qualitycomp": 0, "num_E_points_in_qualitycomp": 0, "precision": None, "recall": None,
+           "network_consistency": None, "network_quality": None}
+    for ci, c in enumerate(np.lexsort((roots, -sizes))):
+        r, e, edges, cross = int(r_cnt[c]), int(e_cnt[c]), int(deg2[c] // 2), int(cross2[c] // 2)
+        consistency = 1 - abs(r - e) / (r + e)
+        quality = cross / edges if edges != 0 else 0
+        mem = members[c]
+        comp_stats[ci] = {"Ridx": mem[:r], "Eidx": mem[r:] - n_r, "comp_consistency": consistency, "comp_quality": quality,
+                          "num_edges": edges, "num_RE_edges": cross}
+        if consistency > comp_consistency_threshold and quality > comp_quality_threshold:
+            net["num_R_points_in_qualitycomp"] += r
+            net["num_E_points_in_qualitycomp"] += e
+    edges, cross = int(deg2.sum() // 2), int(cross2.sum() // 2)
+    net["precision"] = net["num_E_points_in_qualitycomp"] / n_e
+    net["recall"] = net["num_R_points_in_qualitycomp"] / n_r
+    net["network_consistency"] = 1 - abs(n_r - n_e) / (n_r + n_e)
+    net["network_quality"] = cross / edges if edges != 0 else 0
+    return comp_stats, net
+
+
+def geomca(R, E, **parameters):
+    """``GeomCA(R, E, param_dict).get_connected_components()`` (madrigal/evaluate/GeomCA.py) on the device ->
+    ``(comp_stats, network_stats, network_params)`` with the reference's keys.  R [nR,128], E [nE,128]; parameters as in the
+    reference's ``param_dict`` (defaults ``GEOMCA_DEFAULTS``: those of get_alignment_metrics); ``epsilon`` given skips the estimate.
+
+    comp_stats[i] (components by size descending, then smallest vertex): ``Ridx``, ``Eidx`` (indices into the sparse sets, ascending),
+    ``comp_consistency``, ``comp_quality`` and, in place of the networkx ``comp_graph``, ``num_edges`` / ``num_RE_edges``.
+    network_stats: ``num_R_points_in_qualitycomp``, ``num_E_points_in_qualitycomp``, ``precision``, ``recall``,
+    ``network_consistency``, ``network_quality``.  network_params: the reference's seven entries and ``sparseR_index`` /
+    ``sparseE_index``, the kept input rows (int64 numpy).  The path parameters are accepted and nothing is written.  The random
+    draws (the estimate's two, then R's and E's samples when ``sparsify`` is False) come from numpy's global generator after
+    ``np.random.seed(random_seed)``, as in the reference.  An empty reduced set raises ValueError (the reference divides by zero)."""
+    unknown = set(parameters) - set(GEOMCA_DEFAULTS) - set(_GEOMCA_IGNORED) - {"epsilon"}
+    if unknown:
+        raise ValueError(f"geomca: unknown parameters {sorted(unknown)}")
+    p = dict(GEOMCA_DEFAULTS, **parameters)
+    R, E = _dev(R).float().contiguous(), _dev(E).float().contiguous()
+    E = E.to(R.device)
+    np.random.seed(p["random_seed"])
+    if p.get("epsilon") is not None:
+        epsilon = float(p["epsilon"])
+    else:
+        epsilon = geomca_epsilon(R, p["Rdist_ratio"], p["Rdist_percentile"])
+    delta = epsilon * p["gamma"]
+
+    def reduce_(X, flag, n_samples):
+        if not flag:
+            return torch.arange(X.shape[0], device=X.device)
+        if p["sparsify"]:
+            return ops.geomca_sparsify(X, delta)
+        if n_samples is None:
+            raise ValueError("geomca: sparsify=False needs n_Rsamples / n_Esamples")
+        return torch.from_numpy(np.random.choice(np.arange(X.shape[0]), n_samples)).to(X.device)
+
+    ri = reduce_(R, p["reduceR"], p["n_Rsamples"])
+    ei = reduce_(E, p["reduceE"], p["n_Esamples"])
+    n_r, n_e = int(ri.numel()), int(ei.numel())
+    if n_r == 0 or n_e == 0:
+        raise ValueError(f"geomca: an empty reduced set ({n_r} R points, {n_e} E points)")
+    V = torch.cat([R.index_select(0, ri), E.index_select(0, ei)])
+    label, deg_same, deg_cross, _ = ops.geomca_components(V, n_r, epsilon)
+    comp_stats, network_stats = geomca_scores(label, deg_same, deg_cross, n_r, p["comp_consistency_threshold"], p["comp_quality_threshold"])
+    network_params = {"num_R_points": n_r, "num_E_points": n_e, "num_RE_points": n_r + n_e, "epsilon": epsilon, "gamma": p["gamma"],
+                      "comp_consistency_threshold": p["comp_consistency_threshold"],
+                      "comp_quality_threshold": p["comp_quality_threshold"],
+                      "sparseR_index": ri.cpu().numpy().astype(np.int64), "sparseE_index": ei.cpu().numpy().astype(np.int64)}
+    return comp_stats, network_stats, network_params
