@@ -34,6 +34,7 @@ extern "C" {
 #define MDG_ELAUNCH (-3)  /* HIP launch failed */
 #define MDG_EUNSUPPORTED (-4)
 #define MDG_GATHER_MAX_SOURCES 19 /* source matrices of one mdg_gather_rows_multi call */
+#define MDG_COLLATE_MAX_SEGMENTS 4 /* row-gather segments of one mdg_collate_rows call */
 
 /* Arithmetic of the matrix products.  Inputs and outputs stay fp32. */
 enum mdg_precision {
@@ -992,6 +993,46 @@ int mdg_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx
 int mdg_layernorm_bwd_add(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* gamma, const float* extra,
                           int64_t ldextra, float* dx, int64_t lddx, float* dgamma, float* dbeta, int64_t rows, int64_t d, float eps,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- on-device batch collation from a device-resident drug store (madrigal_amd/collate.py) ----------------------------
+ * The reference collates every batch on the host (madrigal/data/data.py:1479-1501: all_molecules[ids],
+ * tabular_mod_stores[mod][ids], 16 x tx_store[...][ids]).  The store keeps every drug's modalities on the device: molecules
+ * packed (atom_ptr / edge_ptr [n_mols + 1]), the edges of each molecule stably sorted by destination atom, with the
+ * store-wide CSR rowptr over destination atoms and the augmented edge rows of the aggregation plan.  Three entry points
+ * build the batch of ids[0], ids[1], ... (any order, duplicates allowed).  Every output element has exactly one writer
+ * (no atomics): results are deterministic. */
+/* Offsets (data.py:1479-1501, the bookkeeping of all_molecules[ids]): rows[i] = id2row[ids[i]], or -1 where ids[i] lies
+ * outside [0, n_table) or names an absent drug (id2row < 0); out_atom_ptr / out_edge_ptr [n_ids + 1] = exclusive scans of
+ * the per-drug atom / edge counts (0 for an id outside the store), correct for any n_ids (two launches: per-workgroup sums,
+ * then each workgroup adds the sums before it); totals[0] = atoms, [1] = edges, [2] = ids outside the store (the status:
+ * 0 = every id known), [3] = position of the first such id.  workspace: mdg_collate_offsets_workspace_bytes(n_ids). */
+size_t mdg_collate_offsets_workspace_bytes(int64_t n_ids);
+int mdg_collate_offsets(const int64_t* ids, int64_t n_ids, const int64_t* id2row, int64_t n_table, const int64_t* atom_ptr,
+                        const int64_t* edge_ptr, int64_t n_mols, int64_t* rows, int64_t* out_atom_ptr, int64_t* out_edge_ptr,
+                        int64_t* totals, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Molecules (data.py:1479-1501, all_molecules[ids], plus the CSR plan graph_plans.molecule_plan would sort for): one launch
+ * over the output rows (tiles of atoms, then tiles of edges; a row finds its drug by bisection of out_atom_ptr / out_edge_ptr).
+ * n_atoms / n_edges are totals[0] / totals[1] of mdg_collate_offsets; every rows[i] must be a store row.  Writes
+ * node_feature [n_atoms, 67], node2graph [n_atoms], edge_list [n_edges, 3] (source and destination rebased as
+ * old - atom_ptr[row] + out_atom_ptr[b], bond type copied), edge_feature [n_edges, 18], edge_weight [n_edges], and the plan:
+ * rowptr [n_atoms + 1] (store_rowptr[a] - edge_ptr[row] + out_edge_ptr[b]; rowptr[n_atoms] = n_edges), col [n_edges] (the
+ * rebased sources), edge_feat_aug [n_edges, 20], w [n_edges] (nullable: the weights again, for stores with non-unit weights). */
+int mdg_collate_molecules(const int64_t* rows, const int64_t* out_atom_ptr, const int64_t* out_edge_ptr, int64_t n_ids,
+                          int64_t n_atoms, int64_t n_edges, const int64_t* atom_ptr, const int64_t* edge_ptr,
+                          const float* store_node_feature, const int64_t* store_edge_list, const float* store_edge_feature,
+                          const float* store_edge_weight, const float* store_edge_feat_aug, const int64_t* store_rowptr,
+                          float* node_feature, int64_t* node2graph, int64_t* edge_list, float* edge_feature, float* edge_weight,
+                          int64_t* rowptr, int64_t* col, float* edge_feat_aug, float* w, void* stream);
+
+/* Tabular rows (data.py:1479-1501, tabular_mod_stores[mod][ids] and the 16 tx_store[...][ids]): for each of n_segments
+ * segments, out[s][b, :] = src[s][rows[b], :] for the segment's n_sources stacked equal-shaped sources (src [n_sources,
+ * n_store_rows, width], out [n_sources, n_ids, width], both dense: exact width, no padding), all segments in one launch.
+ * The *_host arguments are HOST arrays of n_segments entries.  A negative row is skipped (its output rows stay unwritten).
+ * Rows are read with the widest load the segment's width and base addresses allow (16, 8 or 4 bytes). */
+int mdg_collate_rows(const float* const* src_host, float* const* out_host, const int64_t* n_sources_host,
+                     const int64_t* width_host, int n_segments, int64_t n_store_rows, const int64_t* rows, int64_t n_ids,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -2630,3 +2630,89 @@ def geomca_distance_select(x: torch.Tensor, y: torch.Tensor, ids_x: torch.Tensor
     call("mdg_geomca_distance_select", _ptr(x), _ptr(y), _ptr(ids_x), _ptr(ids_y), mx, my, 128, _ptr(xn), _ptr(yn), percentile, segments,
          ctypes.addressof(counts), ctypes.addressof(values), _ptr(ws), nbytes, _stream(x))
     return int(counts[0]), int(counts[1]), float(values[0]), float(values[1]), float(values[2])
+
+
+# ------------------------------------------------------------------------------- on-device batch collation (csrc/collate.hip)
+COLLATE_MAX_SEGMENTS = 4
+
+
+def _i64_cuda(t: torch.Tensor, name: str, dev) -> torch.Tensor:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.device == dev):
+        raise ValueError(f"{name}: expected a 1-D int64 cuda tensor on {dev}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def collate_offsets(ids: torch.Tensor, id2row: torch.Tensor, atom_ptr: torch.Tensor, edge_ptr: torch.Tensor):
+    """ids [B] -> ``(rows [B], out_atom_ptr [B+1], out_edge_ptr [B+1], totals [4])`` (mdg_collate_offsets): the store row of
+    every id (-1 outside the store), the exclusive scans of the per-drug atom / edge counts, and atoms | edges | ids outside
+    the store | position of the first of them.  All int64 on the device: two launches, no host read."""
+    dev = ids.device
+    ids, id2row = _i64_cuda(ids, "collate_offsets: ids", dev), _i64_cuda(id2row, "collate_offsets: id2row", dev)
+    atom_ptr, edge_ptr = _i64_cuda(atom_ptr, "collate_offsets: atom_ptr", dev), _i64_cuda(edge_ptr, "collate_offsets: edge_ptr", dev)
+    B, M = int(ids.numel()), int(atom_ptr.numel()) - 1
+    if B < 1 or M < 0 or edge_ptr.numel() != M + 1:
+        raise ValueError(f"collate_offsets: {B} ids, atom_ptr of {atom_ptr.numel()} and edge_ptr of {edge_ptr.numel()} entries")
+    buf = torch.empty(3 * B + 6, dtype=torch.int64, device=dev)
+    rows, out_atom_ptr, out_edge_ptr, totals = buf[:B], buf[B:2 * B + 1], buf[2 * B + 1:3 * B + 2], buf[3 * B + 2:]
+    ws, nbytes = _scratch("mdg_collate_offsets_workspace_bytes", dev, B)
+    call("mdg_collate_offsets", _ptr(ids), B, _ptr(id2row), id2row.numel(), _ptr(atom_ptr), _ptr(edge_ptr), M, _ptr(rows),
+         _ptr(out_atom_ptr), _ptr(out_edge_ptr), _ptr(totals), _ptr(ws), nbytes, _stream(ids))
+    return rows, out_atom_ptr, out_edge_ptr, totals
+
+
+def collate_molecules(rows, out_atom_ptr, out_edge_ptr, n_atoms: int, n_edges: int, atom_ptr, edge_ptr, node_feature, edge_list,
+                      edge_feature, edge_weight, edge_feat_aug, rowptr, want_w: bool) -> dict:
+    """The packed molecules of store rows ``rows`` and their aggregation plan in one launch (mdg_collate_molecules).  The
+    ``out_*`` arrays and the sizes come from ``collate_offsets``; the rest is the store (edges sorted by destination atom).
+    -> fresh tensors ``node_feature node2graph edge_list edge_feature edge_weight rowptr col edge_feat_aug w`` (w None
+    unless ``want_w``)."""
+    dev = rows.device
+    B, A, E = int(rows.numel()), int(n_atoms), int(n_edges)
+    nf, ef, ew, aug = (_f32_cuda(x, "collate_molecules: " + n) for x, n in
+                       ((node_feature, "node_feature"), (edge_feature, "edge_feature"), (edge_weight, "edge_weight"), (edge_feat_aug, "edge_feat_aug")))
+    if nf.dim() != 2 or nf.shape[1] != 67 or ef.shape[1:] != (18,) or aug.shape[1:] != (20,) or edge_list.shape[1:] != (3,) or \
+            not (ef.shape[0] == aug.shape[0] == ew.shape[0] == edge_list.shape[0]) or rowptr.numel() != nf.shape[0] + 1:
+        raise ValueError("collate_molecules: the store's arrays do not fit together")
+    if edge_list.dtype != torch.int64 or not edge_list.is_contiguous() or edge_list.device != dev:
+        raise ValueError("collate_molecules: edge_list must be a contiguous int64 [E,3] tensor on the store's device")
+    out = {"node_feature": torch.empty((A, 67), dtype=torch.float32, device=dev),
+           "node2graph": torch.empty(A, dtype=torch.int64, device=dev),
+           "edge_list": torch.empty((E, 3), dtype=torch.int64, device=dev),
+           "edge_feature": torch.empty((E, 18), dtype=torch.float32, device=dev),
+           "edge_weight": torch.empty(E, dtype=torch.float32, device=dev),
+           "rowptr": torch.empty(A + 1, dtype=torch.int64, device=dev),
+           "col": torch.empty(E, dtype=torch.int64, device=dev),
+           "edge_feat_aug": torch.empty((E, 20), dtype=torch.float32, device=dev),
+           "w": torch.empty(E, dtype=torch.float32, device=dev) if want_w else None}
+    call("mdg_collate_molecules", _ptr(rows), _ptr(out_atom_ptr), _ptr(out_edge_ptr), B, A, E,
+         _ptr(_i64_cuda(atom_ptr, "collate_molecules: atom_ptr", dev)), _ptr(_i64_cuda(edge_ptr, "collate_molecules: edge_ptr", dev)),
+         _ptr(nf), _ptr(edge_list), _ptr(ef), _ptr(ew), _ptr(aug), _ptr(_i64_cuda(rowptr, "collate_molecules: rowptr", dev)),
+         *[_ptr(out[k]) for k in ("node_feature", "node2graph", "edge_list", "edge_feature", "edge_weight", "rowptr", "col", "edge_feat_aug", "w")],
+         _stream(rows))
+    return out
+
+
+def collate_rows(tables, rows: torch.Tensor) -> list:
+    """``[t[:, rows, :] for t in tables]`` in one launch (mdg_collate_rows): every table is a dense fp32 [S, M, W] stack of S
+    equal-shaped sources over the same M store rows (up to 4 tables, any S and W); the results are dense [S, B, W], exact width.
+    A negative row leaves its output rows unwritten (the caller checks the ids before it uses them)."""
+    tables = list(tables)
+    if not 1 <= len(tables) <= COLLATE_MAX_SEGMENTS:
+        raise ValueError(f"collate_rows: 1 to {COLLATE_MAX_SEGMENTS} tables, got {len(tables)}")
+    dev = rows.device
+    rows = _i64_cuda(rows, "collate_rows: rows", dev)
+    B, M = int(rows.numel()), int(tables[0].shape[1]) if tables[0].dim() == 3 else -1
+    for j, t in enumerate(tables):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous()
+                and t.device == dev and t.shape[1] == M and t.shape[0] >= 1 and t.shape[2] >= 1):
+            raise ValueError(f"collate_rows: tables[{j}] must be a contiguous fp32 cuda [S, {M}, W] tensor on {dev}")
+    if B < 1 or M < 1:
+        raise ValueError(f"collate_rows: {B} rows of {M} store rows")
+    outs = [torch.empty((t.shape[0], B, t.shape[2]), dtype=torch.float32, device=dev) for t in tables]
+    K = len(tables)
+    a_s = (ctypes.c_void_p * K)(*[t.data_ptr() for t in tables])
+    a_o = (ctypes.c_void_p * K)(*[o.data_ptr() for o in outs])
+    a_n = (ctypes.c_int64 * K)(*[t.shape[0] for t in tables])
+    a_w = (ctypes.c_int64 * K)(*[t.shape[2] for t in tables])
+    call("mdg_collate_rows", a_s, a_o, a_n, a_w, K, M, _ptr(rows), B, _stream(rows))
+    return outs
