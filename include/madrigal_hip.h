@@ -115,6 +115,23 @@ int mdg_bilinear_allpairs_ld(const float* z_head, const float* z_tail, const flo
                              int64_t n_tail, int64_t n_labels, int64_t D, int precision, int epilogue, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* The same tensor in 16 bits: out[(l * n_head + i) * ldo + j] = the fp32 score (MDG_EPI_STORE) or 1 / (1 + expf(-score))
+ * (MDG_EPI_STORE_SIGMOID) of mdg_bilinear_allpairs' general sweep in `precision` -- the same accumulator bits in all four modes --
+ * rounded ONCE, to nearest even, to IEEE half (MDG_SCORE_F16; overflow becomes +-inf) or bfloat16 (MDG_SCORE_BF16): bit for bit
+ * the fp32 tensor cast afterwards, with 2 B per score leaving the chip instead of 4 + a cast pass.  For callers that keep or ship
+ * the tensor itself: one chunk of the memmap loop madrigal/evaluate/predict.py:420-429 (decoder of madrigal/models/models.py:
+ * 537-547) at half the HBM, PCIe and disk bytes.
+ *   out: 2-byte aligned, ldo >= n_tail in ELEMENTS, any pitch.  Rows that all start on 4 bytes (out % 4 == 0 and an even ldo;
+ *   ldo = n_tail rounded up to 64 puts them on 128-byte lines) are written as whole lines of packed column pairs; any other
+ *   layout is written correctly with 2-byte stores, several times slower.  Nothing outside columns [0, n_tail) of a row is
+ *   touched, padding included.  z_head == z_tail is allowed and takes the same general sweep (no mirrored store).
+ *   epilogue: MDG_EPI_STORE or MDG_EPI_STORE_SIGMOID only.  n_labels <= 65535 per call, D == 128, 256 * ldo * 2 < 2^31.
+ *   Workspace: mdg_bilinear_allpairs_workspace_bytes (the same operand images).  No atomics: bit-identical between launches. */
+enum mdg_score_type { MDG_SCORE_F16 = 1, MDG_SCORE_BF16 = 2 };
+int mdg_bilinear_allpairs16_ld(const float* z_head, const float* z_tail, const float* w_sym, void* out, int64_t ldo, int64_t n_head,
+                               int64_t n_tail, int64_t n_labels, int64_t D, int precision, int epilogue, int score_type,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* Checkpoint ensemble of the all-pairs head: out[l,i,j] = mean_k sigmoid(z_head_k[i]^T W_sym_k[l] z_tail_k[j]).
  * Replaces get_twosides_scores_wrapper / get_drugbank_scores_wrapper, madrigal/evaluate/predict.py:466-499, 582-614.
  * z_head_host / z_tail_host / w_sym_host: HOST arrays of n_models (1..8) device pointers, model k's z_head [n_head,D],

@@ -1670,9 +1670,9 @@ class BilinearDDIScorer(nn.Bilinear):
             return self._sym_cache[1]
         return self.weight.detach()
 
-    def bilinear(self, input1, input2, weight, epilogue=ops.EPI_STORE, out=None):
+    def bilinear(self, input1, input2, weight, epilogue=ops.EPI_STORE, out=None, out_dtype=None):
         ops.forward_only(input1, input2)
-        return ops.bilinear_allpairs(input1, input2, weight, precision=_state["precision"], epilogue=epilogue, out=out)
+        return ops.bilinear_allpairs(input1, input2, weight, precision=_state["precision"], epilogue=epilogue, out_dtype=out_dtype, out=out)
 
     def _exclude_planes(self, exclude, label_range):
         """An exclusion mask with one plane per outcome of the head, sliced like the weight (a shared plane serves every range)."""
@@ -1754,12 +1754,14 @@ class BilinearDDIScorer(nn.Bilinear):
         reads exactly these entries of the dense result)."""
         return ag.bilinear_gather(input1, input2, self.weight, plan, _state["precision"])
 
-    def forward(self, input1, input2, label_range: tuple = None, epilogue=ops.EPI_STORE, out=None):
+    def forward(self, input1, input2, label_range: tuple = None, epilogue=ops.EPI_STORE, out=None, out_dtype=None):
+        """``out_dtype`` (extension, inference only): ``torch.float16`` / ``torch.bfloat16`` -- the logits (or, with
+        ``EPI_STORE_SIGMOID``, the probabilities) rounded once to 16 bits inside the head (``ops.bilinear_allpairs``)."""
         if ag.needs_grad(input1, input2) or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             # drop-in path of the reference's own training loop: a differentiable dense [L,Nh,Nt] result (memory and
             # backward cost proportional to L*Nh*Nt, as in the reference; score_triples() is the fast path)
-            if epilogue != ops.EPI_STORE or out is not None:
-                raise ValueError("epilogue / out are inference-only arguments")
+            if epilogue != ops.EPI_STORE or out is not None or out_dtype not in (None, torch.float32):
+                raise ValueError("epilogue / out / out_dtype are inference-only arguments")
             w = self.weight
             if label_range is not None:
                 assert len(label_range) == 2
@@ -1769,7 +1771,7 @@ class BilinearDDIScorer(nn.Bilinear):
         if label_range is not None:
             assert len(label_range) == 2
             w = w[label_range[0]:label_range[1]]
-        return self.bilinear(input1, input2, w, epilogue, out)
+        return self.bilinear(input1, input2, w, epilogue, out, out_dtype)
 
 
 # ------------------------------------------------------------------------------------- position encodings

@@ -96,14 +96,28 @@ def symmetrize(w_original: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
     return out
 
 
+SCORE_TYPES = {torch.float16: 1, torch.bfloat16: 2}      # enum mdg_score_type
+
+
 def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, *, precision="bf16x3",
-                      epilogue: int = EPI_STORE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      epilogue: int = EPI_STORE, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """All-pairs scores S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j]  -> [L,Nh,Nt] fp32
     (or [L,Nh,2] row statistics with ``EPI_ROWSTATS``).  madrigal/models/models.py:537-547.
 
     ``EPI_TRIKEYS`` (one drug set against itself, ``z_head is z_tail``): an int32 tensor whose strict lower triangle holds the
     order keys of the scores, for ``rank_normalize`` (which reads nothing else); everything above the diagonal blocks is left
-    unwritten -- half the store stream of ``EPI_STORE``."""
+    unwritten -- half the store stream of ``EPI_STORE``.
+
+    ``out_dtype`` = ``torch.float16`` / ``torch.bfloat16`` (or an ``out`` of that dtype; ``EPI_STORE`` / ``EPI_STORE_SIGMOID`` only):
+    the tensor in 16 bits, rounded once to nearest even inside the head's epilogue -- bit for bit the fp32 result of the general
+    sweep ``.to(out_dtype)`` (fp16 overflow becomes +-inf), half the bytes written and no fp32 tensor next to it.  Without ``out``
+    it comes in the ``empty_scores(dtype=...)`` layout.  ``z_head is z_tail`` takes the general sweep here (no mirrored store)."""
+    if out_dtype is None:
+        out_dtype = out.dtype if (isinstance(out, torch.Tensor) and out.dtype in SCORE_TYPES) else torch.float32
+    if out_dtype != torch.float32 and out_dtype not in SCORE_TYPES:
+        raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
+    if out_dtype in SCORE_TYPES:
+        return _bilinear_allpairs16(z_head, z_tail, w_sym, precision, epilogue, out_dtype, out)
     zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
     D = zh.shape[1]
     if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
@@ -133,6 +147,43 @@ def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
         ws, nbytes = _scratch("mdg_bilinear_allpairs_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
         call("mdg_bilinear_allpairs_ld", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt,
              hi - lo, D, prec, int(epilogue), _ptr(ws), nbytes, _stream(zh), what="mdg_bilinear_allpairs")
+    return out
+
+
+def _bilinear_allpairs16(z_head, z_tail, w_sym, precision, epilogue, out_dtype, out) -> torch.Tensor:
+    """The 16-bit destination of ``bilinear_allpairs`` (mdg_bilinear_allpairs16_ld)."""
+    if epilogue not in (EPI_STORE, EPI_STORE_SIGMOID):
+        raise ValueError(f"out_dtype {out_dtype}: only EPI_STORE and EPI_STORE_SIGMOID have a 16-bit form (row statistics and "
+                         "lower-triangle keys are fp32 / int32 products)")
+    if isinstance(out, torch.Tensor) and out.dtype != out_dtype:
+        raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
+    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
+    D = zh.shape[1]
+    if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
+        raise ValueError(f"feature dims disagree: z_head {tuple(zh.shape)}, z_tail {tuple(zt.shape)}, w {tuple(w.shape)}")
+    if zh.device != zt.device or zh.device != w.device:
+        raise ValueError("z_head, z_tail and w_sym must be on the same device")
+    L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
+    shape = (L, Nh, Nt)
+    if out is None:
+        out = empty_scores(L, Nh, Nt, zh.device, dtype=out_dtype)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda):
+            raise ValueError(f"out: expected a {out_dtype} GPU tensor")
+        # contiguous, or a view of row-padded storage (empty_scores): unit inner stride and one pitch for every row
+        if tuple(out.shape) != shape or (out.numel() and (out.stride(2) != 1 or out.stride(1) < Nt or out.stride(0) != Nh * out.stride(1))):
+            raise ValueError(f"out: expected {shape}, contiguous or row-pitched (empty_scores), got {tuple(out.shape)} strides {tuple(out.stride())}")
+    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
+    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    if not out.numel():
+        return out
+    ldo = out.stride(1)
+    for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
+        hi = min(L, lo + 65535)
+        ws, nbytes = _scratch("mdg_bilinear_allpairs_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
+        call("mdg_bilinear_allpairs16_ld", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, out.data_ptr() + lo * out.stride(0) * 2, ldo, Nh, Nt,
+             hi - lo, D, prec, int(epilogue), SCORE_TYPES[out_dtype], _ptr(ws), nbytes, _stream(zh))
     return out
 
 
@@ -608,14 +659,19 @@ def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", o
     return out
 
 
-def empty_scores(L: int, Nh: int, Nt: int, device) -> torch.Tensor:
+def empty_scores(L: int, Nh: int, Nt: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """An uninitialised [L,Nh,Nt] fp32 score (or rank) tensor in the layout the head writes fastest: rows padded to a multiple of
     32 floats, so that every row starts on a 128-byte line whatever Nt is (the real drug counts -- 11 607 in
     generate_embeddings.ipynb -- are not multiples of anything).  For Nt % 32 == 0 this is a plain contiguous tensor; otherwise a
-    [:, :, :Nt] view of the padded storage: same values and indexing, ``.contiguous()`` compacts it."""
-    unit = 32                                                     # floats: one 128-byte line (scripts/head_ragged_bench.py compared 4 .. 64)
+    [:, :, :Nt] view of the padded storage: same values and indexing, ``.contiguous()`` compacts it.
+
+    ``dtype`` = ``torch.float16`` / ``torch.bfloat16`` (the 16-bit destinations of ``bilinear_allpairs``): the pitch unit is 64
+    elements, still one 128-byte line."""
+    if dtype != torch.float32 and dtype not in SCORE_TYPES:
+        raise ValueError(f"dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {dtype}")
+    unit = 32 if dtype == torch.float32 else 64                   # elements: one 128-byte line (scripts/head_ragged_bench.py compared 4 .. 64 floats)
     pitch = (Nt + unit - 1) // unit * unit
-    return torch.empty((L, Nh, pitch), dtype=torch.float32, device=device)[:, :, :Nt]
+    return torch.empty((L, Nh, pitch), dtype=dtype, device=device)[:, :, :Nt]
 
 
 # ------------------------------------------------------------------------------- dense blocks
@@ -1385,6 +1441,10 @@ def rank_normalize(scores: torch.Tensor, out: Optional[torch.Tensor] = None, max
 
     ``scores`` of dtype int32 = the lower-triangle order keys of ``bilinear_allpairs(..., epilogue=EPI_TRIKEYS)``: same ranks,
     and without ``out`` they are written over the keys (the returned fp32 tensor shares the keys' memory).
+
+    16-bit scores (``bilinear_allpairs(..., out_dtype=torch.float16 / torch.bfloat16)``) are refused with a ``ValueError``: rounding
+    to 11 or 8 significant bits makes scores tie that differ in fp32, and tied scores share a rank here, so the ranks of a 16-bit
+    tensor are not the ranks of the model ("Ties in rank normalisation").  Ranks come from fp32 scores or their keys.
 
     ``fallback_flags`` (diagnostics): a list that receives, per chunk that took the MSD fast path, an int32 tensor with one entry
     per outcome -- non-zero where the fast path handed the outcome to the four-pass LSD sort (same ranks either way)."""

@@ -80,8 +80,13 @@ def generate_embeddings(model, batch: dict, batch_kg: dict, masks: Optional[torc
 
 @torch.no_grad()
 def score_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int]] = None, out=None,
-                    host_chunk: int = 16, epilogue: int = ops.EPI_STORE, head_rows: Optional[Tuple[int, int]] = None):
+                    host_chunk: int = 16, epilogue: int = ops.EPI_STORE, head_rows: Optional[Tuple[int, int]] = None,
+                    out_dtype=None):
     """Scores of every ordered drug pair for outcomes ``label_range`` (default: all) -> [L',N,N] fp32.
+
+    ``out_dtype`` = ``torch.float16`` / ``torch.bfloat16`` (or an ``out`` of a 16-bit type): the tensor in 16 bits, rounded once inside
+    the head (``ops.bilinear_allpairs``) -- half the HBM and, with a host destination (a ``np.float16`` array or memmap; numpy has
+    no bfloat16), half the PCIe and disk bytes: the staging buffers and copies are 16-bit too.
 
     ``head_rows`` = (r0, r1): the row-sharded head -- only head drugs [r0, r1) against ALL tail drugs -> [L', r1 - r0, N]
     (``decoder(z[r0:r1], z, ...)``, the general sweep; HBM destination only).  ``shard_range(N, rank, world)`` gives a rank's rows;
@@ -94,26 +99,35 @@ def score_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int
     L_all = dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
     lo, hi = (0, L_all) if label_range is None else label_range
     N = z.shape[0]
+    if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
+    dtype = torch.float32 if out_dtype is None else out_dtype          # of a tensor allocated here
+    kw = {} if out_dtype is None else {"out_dtype": out_dtype}
     if head_rows is not None:
         r0, r1 = head_rows
         if not (0 <= r0 <= r1 <= N):
             raise ValueError(f"head_rows {head_rows} outside [0, {N}]")
         if out is None:
-            out = ops.empty_scores(hi - lo, r1 - r0, N, z.device)
+            out = ops.empty_scores(hi - lo, r1 - r0, N, z.device, dtype=dtype)
         if not isinstance(out, torch.Tensor):
             raise ValueError("head_rows: HBM destination only")
         if r1 == r0:
             return out
-        return dec(z[r0:r1], z, (lo, hi), epilogue=epilogue, out=out)
+        return dec(z[r0:r1], z, (lo, hi), epilogue=epilogue, out=out, **kw)
     if out is None:
-        out = ops.empty_scores(hi - lo, N, N, z.device)      # rows on 128-byte lines whatever N is (a [:, :, :N] view when N % 32 != 0)
+        out = ops.empty_scores(hi - lo, N, N, z.device, dtype=dtype)      # rows on 128-byte lines whatever N is (a [:, :, :N] view when N % 32 (64) != 0)
     if isinstance(out, torch.Tensor):
-        return dec(z, z, (lo, hi), epilogue=epilogue, out=out)
-    if tuple(out.shape) != (hi - lo, N, N) or out.dtype != np.float32:
-        raise ValueError(f"out: expected float32 array of shape {(hi - lo, N, N)}")
+        return dec(z, z, (lo, hi), epilogue=epilogue, out=out, **kw)
+    if out_dtype == torch.bfloat16:
+        raise ValueError("out_dtype torch.bfloat16 needs an HBM destination: numpy has no bfloat16 (use torch.float16 for a host array / memmap)")
+    host_dtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}.get(out.dtype)
+    if tuple(out.shape) != (hi - lo, N, N) or host_dtype is None:
+        raise ValueError(f"out: expected a float32 or float16 array of shape {(hi - lo, N, N)}")
+    if out_dtype is not None and out_dtype != host_dtype:
+        raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
     copy_stream = torch.cuda.Stream(device=z.device)
-    dev_buf = [ops.empty_scores(host_chunk, N, N, z.device) for _ in range(2)]     # row-pitched on the device, compacted by the copy
-    pin_buf = [torch.empty((host_chunk, N, N), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+    dev_buf = [ops.empty_scores(host_chunk, N, N, z.device, dtype=host_dtype) for _ in range(2)]     # row-pitched on the device, compacted by the copy
+    pin_buf = [torch.empty((host_chunk, N, N), dtype=host_dtype, pin_memory=True) for _ in range(2)]
     done = [None, None]
     pending = [None, None]
     k = 0
