@@ -294,6 +294,34 @@ int mdg_bilinear_profile(const float* z_head, const float* z_tail, const float* 
                          int64_t n_labels, int64_t D, int precision, int eligible, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* Streaming per-pair top-k over the OUTCOME axis of a score or rank tensor (ABI 24): one chunk x [n_labels, n_head, n_tail] is
+ * folded into a running state vals fp32 / idx int32 [k, n_head, n_tail], per pair (i, j) the k best (value, outcome id) of
+ * everything folded so far.  Replaces the per-pair "highest 5" reductions the reference runs over its stored [L,N,N] rank tensor:
+ * notebooks/fig5/fig5_t2d_mash.ipynb:1442-1448 (np.mean(np.partition(lst, len(lst)-5)[-5:])), :2034-2039 (highest_5_ddi_classes /
+ * highest_5_scores / highest_5_mean) and, with largest = 0, the lowest 5 at :2050.
+ *   x: element (l, i, j) at x[l * x_outcome_stride + i * ldx + j]; x_type 0 = fp32, MDG_SCORE_F16, MDG_SCORE_BF16 (16-bit values are
+ *   widened to fp32 exactly); ldx >= n_tail; aligned to its element size.  labels int32 [n_labels] or NULL: the global outcome id of
+ *   each plane (NULL: label_base + l); a plane with a negative label is skipped (the reference's to_delete_classes).  shift, scale
+ *   fp32 [n_labels], each or both NULL: the value folded is (x - shift[l]) * scale[l], a subtract, then a multiply, each rounded to
+ *   fp32 (never an FMA; NULL = 0 / 1, which leaves x's bits).  Their values are NOT checked here (callers pass finite shifts and
+ *   finite scales > 0): the call enqueues on `stream`, needs no workspace and does not synchronise.
+ *   State: element (s, i, j) of vals / idx at [s * state_plane_stride + i * lds + j] (one plane stride and one pitch for both,
+ *   lds >= n_tail), 1 <= k <= 8.  fresh != 0: the incoming state is ignored.  largest 1 / 0.  eligible: MDG_TOPK_ALL, or
+ *   MDG_TOPK_LOWER (only entries with i > j).
+ * Semantics, exact and independent of how the outcomes are split into calls and of the order of the calls: slot s of a pair holds
+ * the s-th element of all folded (value, id) under ONE total order -- value descending, then id ascending (largest = 0: value
+ * ascending, then id ascending).  Empty slots hold (-inf, -1) ((+inf, -1) with largest = 0).  A NaN is never kept, nor is a value
+ * equal to the sentinel value.  Values are copies (or the two-step expression above), so results compare bit for bit.  With LOWER
+ * and fresh the entries with i <= j receive the sentinels; without fresh they are left untouched.  Nothing outside columns
+ * [0, n_tail) of the k * n_head state rows is written, pitch padding included.  n_labels == 0 with fresh writes the sentinels.
+ *   Rows of x and of the state that all start on 16 bytes (bases, pitches and strides) move 16 bytes per lane; any other layout
+ *   takes an element path, correct and several times slower.  n_head * ceil(n_tail / 256) workgroups must fit 2^31 - 1.
+ * Deterministic: a lane owns its pairs' lists in registers over the whole chunk; no atomics, no LDS. */
+int mdg_outcome_topk_update(const void* x, int x_type, int64_t x_outcome_stride, int64_t ldx, const int32_t* labels,
+                            int64_t label_base, const float* shift, const float* scale, float* vals, int32_t* idx,
+                            int64_t state_plane_stride, int64_t lds, int64_t n_head, int64_t n_tail, int64_t n_labels, int k,
+                            int fresh, int largest, int eligible, void* stream);
+
 /* ------------------------------------------------------------------------ dense blocks ---- */
 
 /* Y = alpha * act( (X W^T + bias) * scale + shift ) + beta * R      X [M,K] ldx, W [N,K] ldw (nn.Linear

@@ -610,6 +610,136 @@ def profile_merge(a, b, label_offset_b: int):
     return ca + cb, torch.where(take_b, gb, ba), torch.where(take_b, mb, ma)
 
 
+OUTCOME_TOPK_MAX_K = 8
+_X_TYPES = {torch.float32: 0, **SCORE_TYPES}                # x_type of mdg_outcome_topk_update
+
+
+def _byte_span(t: torch.Tensor):
+    """[first, past-the-last) byte address a strided tensor can touch."""
+    last = sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if not (a.numel() and b.numel()):
+        return False
+    (a0, a1), (b0, b1) = _byte_span(a), _byte_span(b)
+    return a0 < b1 and b0 < a1
+
+
+def _per_outcome(t, name: str, Lc: int, device) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (Lc,):
+        raise ValueError(f"{name}: expected a float32 tensor [{Lc}] (one per outcome of x)")
+    if not t.is_cuda or t.device != device:
+        raise ValueError(f"{name}: must live on the device of x ({device}), got {t.device}")
+    return t.contiguous()
+
+
+def outcome_topk(x: torch.Tensor, k: int, *, labels=None, label_base: int = 0, shift: Optional[torch.Tensor] = None,
+                 scale: Optional[torch.Tensor] = None, largest: bool = True, eligible: str = "all", state=None):
+    """Per-pair top-k over the OUTCOME axis, streamed -> ``(vals fp32, idx int32)``, each [k, Nh, Nt]: the chunk ``x`` [Lc, Nh, Nt]
+    (float32, float16 or bfloat16; contiguous, row-pitched as from ``empty_scores``, or any view with unit inner stride -- nothing is
+    copied) is folded into a running per-pair sorted list of the k best (value, outcome id).  Slot s of pair (i, j) holds the s-th
+    element of everything folded so far under one total order: value descending, then outcome id ascending (``largest=False``:
+    value ascending, then id ascending); empty slots hold (-inf, -1) ((+inf, -1)).  The result does not depend on how the outcomes
+    are split into calls nor on the order of the calls, and the values are copies: compare with ``torch.equal``.  This is the
+    reference's ``np.partition(lst, len(lst)-5)[-5:]`` per drug pair (notebooks/fig5/fig5_t2d_mash.ipynb:1442-1448, 2034-2039) with
+    the outcomes attaining it, in ``k * Nh * Nt * 8`` bytes of state plus one chunk.
+
+    ``state``: None -- fresh row-pitched tensors are allocated and ``[:, :, :Nt]`` views returned; or the ``(vals, idx)`` of an
+    earlier call, updated in place and returned (its ``k`` must be ``k``).  ``labels``: int32 [Lc] (a list or an int64 tensor is
+    converted), the global outcome id of each plane, in any order; a negative label skips the plane.  Without it plane l has id
+    ``label_base + l``.  ``shift`` / ``scale``: fp32 [Lc], each optional; the value folded is ``(x - shift[l]) * scale[l]``, a
+    subtract, then a multiply, in fp32 (16-bit inputs are widened exactly first).  ``shift`` must be finite and ``scale`` finite and
+    > 0: checking that reads two flags back, ONE host synchronisation per call that passes either.  A NaN value is never kept, nor
+    is a value equal to the sentinel value.  ``eligible``: ``"all"`` or ``"lower"`` (only i > j; a fresh state gets the sentinels
+    elsewhere, an updated state is left untouched there).  Empty Nh, Nt or Lc launches nothing.  Deterministic: no atomics.
+    Merge the states of disjoint outcome shards with ``outcome_topk_merge``."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= OUTCOME_TOPK_MAX_K:
+        raise ValueError(f"k: expected an int in 1..{OUTCOME_TOPK_MAX_K}, got {k!r}")
+    if not isinstance(x, torch.Tensor):
+        raise ValueError("x: expected a torch.Tensor")
+    if not x.is_cuda:
+        raise ValueError(f"x: must live on the GPU (got {x.device}); the HIP path has no CPU fallback")
+    if x.dtype not in _X_TYPES:
+        raise ValueError(f"x: expected float32, float16 or bfloat16, got {x.dtype}")
+    if x.dim() != 3:
+        raise ValueError(f"x: expected [Lc, Nh, Nt], got shape {tuple(x.shape)}")
+    if eligible not in ("all", "lower"):
+        raise ValueError(f"unknown eligible {eligible!r}; expected 'all' or 'lower'")
+    Lc, Nh, Nt = x.shape
+    if x.numel() and (x.stride(2) != 1 or x.stride(1) < Nt or x.stride(0) < 0):
+        raise ValueError(f"x: expected unit inner stride and a row pitch >= Nt (contiguous or row-pitched), got strides {tuple(x.stride())}")
+    if isinstance(label_base, bool) or not isinstance(label_base, int) or label_base < 0 or label_base + Lc > 2 ** 31 - 1:
+        raise ValueError(f"label_base: outcome ids [{label_base!r}, {label_base!r} + {Lc}) must lie in the int32 range")
+    lab = None
+    if labels is not None:
+        lab = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(labels)
+        if lab.dtype not in (torch.int32, torch.int64) or tuple(lab.shape) != (Lc,):
+            raise ValueError(f"labels: expected {Lc} integer outcome ids (int32 [Lc]), got {lab.dtype} {tuple(lab.shape)}")
+        if lab.dtype == torch.int64:
+            if lab.numel() and int(lab.max()) > 2 ** 31 - 1:
+                raise ValueError("labels: outcome ids over the int32 range")
+            lab = lab.clamp(min=-1).to(torch.int32)
+        lab = lab.to(x.device).contiguous()
+    sh, sc = _per_outcome(shift, "shift", Lc, x.device), _per_outcome(scale, "scale", Lc, x.device)
+    if Lc and (sh is not None or sc is not None):
+        ok = [torch.isfinite(t).all() if t is sh else (torch.isfinite(t) & (t > 0)).all() for t in (sh, sc) if t is not None]
+        ok = torch.stack(ok).tolist()                      # the one host read
+        if sh is not None and not ok[0]:
+            raise ValueError("shift: every entry must be finite")
+        if sc is not None and not ok[-1]:
+            raise ValueError("scale: every entry must be finite and > 0")
+    fresh = state is None
+    if fresh:
+        pitch = (Nt + 31) // 32 * 32                       # rows on 128-byte lines: the pitch rule of _profile_out
+        if Lc == 0:
+            vals = torch.full((k, Nh, pitch), float("-inf") if largest else float("inf"), dtype=torch.float32, device=x.device)[:, :, :Nt]
+            idx = torch.full((k, Nh, pitch), -1, dtype=torch.int32, device=x.device)[:, :, :Nt]
+            return vals, idx
+        vals = torch.empty((k, Nh, pitch), dtype=torch.float32, device=x.device)[:, :, :Nt]
+        idx = torch.empty((k, Nh, pitch), dtype=torch.int32, device=x.device)[:, :, :Nt]
+    else:
+        if not (isinstance(state, (tuple, list)) and len(state) == 2):
+            raise ValueError("state: expected the (vals, idx) pair of an earlier call")
+        vals, idx = state
+        for t, dt, name in ((vals, torch.float32, "vals"), (idx, torch.int32, "idx")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == x.device and t.dtype == dt and tuple(t.shape) == (k, Nh, Nt)):
+                raise ValueError(f"state: {name} must be a {dt} GPU tensor of shape {(k, Nh, Nt)} on {x.device}")
+            if t.numel() and (t.stride(2) != 1 or t.stride(1) < Nt or (k > 1 and t.stride(0) < Nh * t.stride(1))):
+                raise ValueError(f"state: {name} must be contiguous or row-pitched (strides {tuple(t.stride())})")
+        if vals.numel() and vals.stride() != idx.stride():
+            raise ValueError(f"state: vals and idx must share one plane stride and one row pitch (strides {tuple(vals.stride())} and "
+                             f"{tuple(idx.stride())})")
+        if _overlap(vals, x) or _overlap(idx, x) or _overlap(vals, idx):
+            raise ValueError("state: vals and idx must not alias x or each other")
+    if Nh == 0 or Nt == 0 or Lc == 0:
+        return vals, idx
+    call("mdg_outcome_topk_update", _ptr(x), _X_TYPES[x.dtype], x.stride(0), x.stride(1), _ptr(lab), label_base, _ptr(sh), _ptr(sc),
+         _ptr(vals), _ptr(idx), vals.stride(0), vals.stride(1), Nh, Nt, Lc, k, int(fresh), int(bool(largest)), TOPK_ELIGIBLE[eligible],
+         _stream(x))
+    return vals, idx
+
+
+def outcome_topk_merge(a, b, *, largest: bool = True):
+    """Merge two ``outcome_topk`` states over DISJOINT outcome sets and the same pairs -> ``(vals, idx)`` [k, Nh, Nt], k that of
+    ``a`` (and ``b``): the k best of both under the same total order (value descending -- ascending with ``largest=False``, which must
+    be the direction both states were built with --, then outcome id ascending; sentinels last).  For outcome-sharded ranks.
+    Pure torch, any device; the arguments are left unchanged."""
+    (va, ia), (vb, ib) = a, b
+    if va.shape != ia.shape or vb.shape != ib.shape or va.shape != vb.shape:
+        raise ValueError(f"outcome_topk_merge: two (vals, idx) states of one shape, got {tuple(va.shape)} / {tuple(ia.shape)} and "
+                         f"{tuple(vb.shape)} / {tuple(ib.shape)}")
+    k = va.shape[0]
+    v, i = torch.cat([va, vb], 0), torch.cat([ia, ib], 0)
+    by_id = torch.sort(torch.where(i < 0, torch.full_like(i, 2 ** 31 - 1), i), dim=0, stable=True).indices
+    v, i = v.gather(0, by_id), i.gather(0, by_id)
+    by_val = torch.sort(v, dim=0, descending=bool(largest), stable=True).indices[:k]
+    return v.gather(0, by_val), i.gather(0, by_val)
+
+
 ENSEMBLE_PRECISIONS ={"f32": PREC_F32, "bf16x3": PREC_BF16X3}
 
 

@@ -742,6 +742,187 @@ def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, l
     return out_c, out_h, out_t, out_b, out_m
 
 
+# ---- per-pair highest outcomes of a rank or score tensor, streamed (ops.outcome_topk) ----
+HOST_OUTCOME_CHUNK = 16          # outcomes per staged chunk of a host tensor, as score_all_pairs' host_chunk
+
+
+def _kept_labels(keep, n_all: int, lo: int, hi: int) -> torch.Tensor:
+    """int64 CPU [hi - lo]: the model's outcome id of each outcome of [lo, hi), -1 where ``keep`` (ids or a bool mask over all
+    ``n_all`` outcomes; None keeps everything) drops it."""
+    ids = torch.arange(lo, hi)
+    if keep is None:
+        return ids
+    kp = torch.as_tensor(keep).cpu()
+    if kp.dtype == torch.bool:
+        if tuple(kp.shape) != (n_all,):
+            raise ValueError(f"keep: a bool mask must have one entry per outcome of the head ([{n_all}]), got {tuple(kp.shape)}")
+        mask = kp
+    else:
+        if kp.dtype not in (torch.int32, torch.int64) or kp.dim() != 1:
+            raise ValueError(f"keep: expected outcome ids or a bool mask, got {kp.dtype} {tuple(kp.shape)}")
+        if kp.numel() and (int(kp.min()) < 0 or int(kp.max()) >= n_all):
+            raise ValueError(f"keep: outcome ids must lie in [0, {n_all})")
+        mask = torch.zeros(n_all, dtype=torch.bool)
+        mask[kp.long()] = True
+    return torch.where(mask[lo:hi], ids, torch.full_like(ids, -1))
+
+
+def _with_mean(state, k: int, Nh: int, Nt: int, device, largest: bool):
+    if state is None:                                    # nothing was folded: the sentinels
+        state = ops.outcome_topk(torch.empty((0, Nh, Nt), dtype=torch.float32, device=device), k, largest=largest)
+    return state[0], state[1], state[0].mean(0)
+
+
+@torch.no_grad()
+def highest_outcomes_of(x, k: int = 5, *, labels=None, largest: bool = True, eligible: str = "all", chunk: Optional[int] = None,
+                        max_bytes: int = 8 << 30):
+    """The k highest values over the OUTCOMES of a stored rank or score tensor ``x`` [L, N, N], per drug pair ->
+    ``(vals fp32 [k,N,N], idx int32 [k,N,N], mean fp32 [N,N])``: the reference's ``highest_5_scores``, ``highest_5_ddi_classes`` and
+    ``highest_5_mean`` (notebooks/fig5/fig5_t2d_mash.ipynb:2034-2039; ``np.mean(np.partition(lst, len(lst)-5)[-5:])`` at :1442-1448)
+    for every pair at once, ordered (value descending, outcome ascending); ``largest=False`` gives the lowest k (:2050).
+    ``mean = vals.mean(0)``: -inf (+inf) where fewer than k outcomes were kept.
+
+    ``x``: a CUDA tensor (float32 / float16 / bfloat16, contiguous or row-pitched) -- folded where it lies, nothing is copied
+    (``chunk``: outcomes per fold, default all in one call) -- or a numpy array / ``np.memmap`` of float32 or float16, the
+    reference's ``np.load(..., mmap_mode="r")`` rank file: chunks of ``chunk`` outcomes (default 16, fewer if two device chunks
+    exceed ``max_bytes``) go host -> pinned staging -> device on a copy stream while the previous chunk is folded.
+    ``labels``: the outcome id of each plane of ``x`` (default 0..L-1); a negative id drops the plane (the reference's
+    ``to_delete_classes``), and a host chunk with nothing kept is not copied.  ``eligible``: ``"all"`` or ``"lower"`` (i > j)."""
+    on_gpu = isinstance(x, torch.Tensor)
+    if on_gpu and not x.is_cuda:
+        raise ValueError("x: a torch tensor must live on the GPU (pass host data as a numpy array or np.memmap)")
+    if not on_gpu and not (isinstance(x, np.ndarray) and x.dtype in (np.float32, np.float16)):
+        raise ValueError("x: expected a CUDA tensor, or a float32 / float16 numpy array or memmap")
+    if x.ndim != 3:
+        raise ValueError(f"x: expected [L, Nh, Nt], got shape {tuple(x.shape)}")
+    L, Nh, Nt = x.shape
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
+        raise ValueError(f"chunk: expected a positive int, got {chunk!r}")
+    lab = None
+    if labels is not None:
+        lab = torch.as_tensor(labels).cpu()
+        if lab.dtype not in (torch.int32, torch.int64) or tuple(lab.shape) != (L,):
+            raise ValueError(f"labels: expected {L} integer outcome ids, got {lab.dtype} {tuple(lab.shape)}")
+    if on_gpu:
+        dev = x.device
+        step = max(L, 1) if chunk is None else chunk
+        state = None
+        for s in range(0, L, step):
+            e = min(L, s + step)
+            kw = {"label_base": s} if lab is None else {"labels": lab[s:e].to(dev)}
+            state = ops.outcome_topk(x[s:e], k, largest=largest, eligible=eligible, state=state, **kw)
+        return _with_mean(state, k, Nh, Nt, dev, largest)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    dtype = torch.float32 if x.dtype == np.float32 else torch.float16
+    pitch = ops.empty_scores(0, Nh, Nt, dev, dtype=dtype).stride(1) if Nt else 1
+    step = HOST_OUTCOME_CHUNK if chunk is None else chunk
+    step = max(1, min(step, max(L, 1), int(max_bytes) // max(2 * Nh * pitch * x.dtype.itemsize, 1)))
+    cur, copy_stream = torch.cuda.current_stream(dev), torch.cuda.Stream(device=dev)
+    dev_buf = [ops.empty_scores(step, Nh, Nt, dev, dtype=dtype) for _ in range(2)]          # row-pitched on the device, spread by the copy
+    pin_buf = [torch.empty((step, Nh, Nt), dtype=dtype, pin_memory=True) for _ in range(2)]
+    copy_stream.wait_stream(cur)                           # the device chunks come from this stream's pool
+    folded = [None, None]
+    state, n = None, 0
+    for s in range(0, L, step):
+        e = min(L, s + step)
+        if lab is not None and not bool((lab[s:e] >= 0).any()):
+            continue
+        b = n & 1
+        n += 1
+        if folded[b] is not None:                          # staging pair b is free once the fold that read it has finished
+            folded[b].synchronize()
+        pin_buf[b][: e - s].numpy()[...] = x[s:e]          # host read of chunk n overlaps the copy and the fold of chunk n - 1
+        with torch.cuda.stream(copy_stream):
+            dev_buf[b][: e - s].copy_(pin_buf[b][: e - s], non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(copy_stream)
+        cur.wait_event(ready)
+        kw = {"label_base": s} if lab is None else {"labels": lab[s:e].to(dev)}
+        state = ops.outcome_topk(dev_buf[b][: e - s], k, largest=largest, eligible=eligible, state=state, **kw)
+        folded[b] = torch.cuda.Event()
+        folded[b].record(cur)
+    copy_stream.synchronize()
+    return _with_mean(state, k, Nh, Nt, dev, largest)
+
+
+def _outcome_chunks(lab: torch.Tensor, lo: int, hi: int, chunk: int):
+    """(s, e, labels int32 CPU) of every outcome chunk of [lo, hi) that keeps at least one outcome."""
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        part = lab[s - lo:e - lo]
+        if bool((part >= 0).any()):
+            yield s, e, part.to(torch.int32)
+
+
+@torch.no_grad()
+def highest_outcomes(model, z: torch.Tensor, k: int = 5, *, of: str = "ranks", keep=None, label_range: Optional[Tuple[int, int]] = None,
+                     scale=None, shift=None, largest: bool = True, max_bytes: int = 8 << 30):
+    """The k highest outcomes of every drug pair, straight from the model -> ``(vals fp32 [k,N,N], idx int32 [k,N,N], mean fp32
+    [N,N])``, ``idx`` the MODEL's outcome indices: ``highest_outcomes_of`` without the [L,N,N] tensor ever existing.  Per outcome
+    chunk the tensor is produced and folded into the per-pair lists (``ops.outcome_topk``), so memory is ``16 k N^2`` bytes of
+    state (8 k stored, read and written once per chunk) plus one chunk.
+
+    ``of="ranks"``: the normalised ranks of ``rank_all_pairs`` (ranks are per outcome, so chunking over outcomes is exact) -- the
+    reference's highest-5 mean of one seed.  ``of="scores"``: the head's fp32 scores, folded as ``(S - shift[l]) * scale[l]``
+    (``shift`` / ``scale``: None, a number or [L'], e.g. an outcome's mean and one over its spread, to make logits comparable
+    across outcomes; ``scale`` finite and > 0).  ``keep``: outcome ids or a bool mask over all outcomes of the head; dropped
+    outcomes (the reference's ``to_delete_classes``) never enter a list, and a chunk with nothing kept is not computed at all.
+    ``label_range``: only these outcomes (an outcome shard; merge shards with ``ops.outcome_topk_merge``).
+
+    The chunk holds as many outcomes as ``max_bytes`` (default 8 GiB, as elsewhere here) allows.  Every fold reads and writes the
+    state, ``16 k`` bytes per pair per call against ``4`` bytes per pair per outcome, so small chunks are dominated by state
+    traffic: leave room for >= 64 outcomes per chunk when memory allows."""
+    if of not in ("ranks", "scores"):
+        raise ValueError(f"of: expected 'ranks' or 'scores', got {of!r}")
+    if of == "ranks" and (scale is not None or shift is not None):
+        raise ValueError("shift / scale apply to of='scores' (normalised ranks are comparable across outcomes as they are)")
+    lo, hi = _outcomes(model, label_range)
+    N, dev = z.shape[0], z.device
+    lab = _kept_labels(keep, _n_outcomes(model), lo, hi)
+    sh = None if shift is None else _cuts(shift, hi - lo, dev)
+    sc = None if scale is None else _cuts(scale, hi - lo, dev)
+    plane = N * ops.empty_scores(0, N, N, dev).stride(1) * 4 if N else 1
+    chunk = max(1, min(max(hi - lo, 1), int(max_bytes) // plane))
+    buf = ops.empty_scores(chunk, N, N, dev)
+    state = None
+    for s, e, part in _outcome_chunks(lab, lo, hi, chunk):
+        if of == "ranks":
+            x = rank_all_pairs(model, z, (s, e), out=buf[: e - s])
+        else:
+            x = score_all_pairs(model, z, (s, e), out=buf[: e - s])
+        state = ops.outcome_topk(x, k, labels=part.to(dev), shift=None if sh is None else sh[s - lo:e - lo],
+                                 scale=None if sc is None else sc[s - lo:e - lo], largest=largest, state=state)
+    return _with_mean(state, k, N, N, dev, largest)
+
+
+@torch.no_grad()
+def ensemble_highest_outcomes(models, zs, k: int = 5, *, keep=None, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 8 << 30):
+    """The paper's ranking of candidate combinations, end to end -> ``(vals, idx, mean)`` as ``highest_outcomes``: per outcome
+    chunk the normalised ranks of every seed (``rank_all_pairs``), their geometric mean re-ranked (``ops.ensemble_ranks``,
+    generate_embeddings.ipynb cells 18-20), folded into the per-pair highest-k lists -- the ``highest_5_mean`` of
+    notebooks/fig5/fig5_t2d_mash.ipynb:2034-2039 over the seed-ensembled rank tensor, which at 11 607 drugs x 158 outcomes does not
+    fit next to its inputs.  ``models`` / ``zs``: the seeds' models and embeddings of the same drugs.  A chunk holds one rank tensor
+    per seed, their geometric mean and its ranks within ``max_bytes`` (the note on small chunks in ``highest_outcomes`` applies).
+    A pure composition of public functions."""
+    models, zs = list(models), list(zs)
+    if not models or len(models) != len(zs):
+        raise ValueError(f"ensemble_highest_outcomes: {len(models)} models and {len(zs)} embeddings")
+    lo, hi = _outcomes(models[0], label_range)
+    N, dev = zs[0].shape[0], zs[0].device
+    for m, zz in zip(models, zs):
+        if _n_outcomes(m) != _n_outcomes(models[0]) or zz.shape[0] != N:
+            raise ValueError("ensemble_highest_outcomes: every seed needs the same outcomes and the same drugs")
+    lab = _kept_labels(keep, _n_outcomes(models[0]), lo, hi)
+    plane = N * ops.empty_scores(0, N, N, dev).stride(1) * 4 if N else 1
+    chunk = max(1, min(max(hi - lo, 1), int(max_bytes) // ((len(models) + 2) * plane)))          # the seeds' ranks, their gmean, its ranks
+    state = None
+    for s, e, part in _outcome_chunks(lab, lo, hi, chunk):
+        ens = ops.ensemble_ranks([rank_all_pairs(m, zz, (s, e)) for m, zz in zip(models, zs)])
+        state = ops.outcome_topk(ens, k, labels=part.to(dev), state=state)
+        del ens
+    return _with_mean(state, k, N, N, dev, True)
+
+
 def ranks_from_counts(less: torch.Tensor, N: int) -> torch.Tensor:
     """Normalised rank of a pair with ``less`` pairs of its outcome scoring below it, among the N (N - 1) / 2 pairs of N drugs
     -> float32: ``(less + 1) / (N (N - 1) / 2)``, divided in float64 and rounded to float32 once -- the arithmetic of
