@@ -512,6 +512,24 @@ int mdg_hgt_attention_rows(const float* q_base, const int64_t* q_off, const floa
                            const int64_t* item_ptr, float* out, int64_t ldo, int64_t n_dst, int heads, int apply_gelu,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same attention carried out in node-feature space (inference; 4 heads of 32).  Where the relation-transformed key and
+ * value of an edge are affine images of the source node's 128-float feature row, the logits are u . x + c with the
+ * destination-side block ut [n_dst, n_rel, 4, 132] = [ K^T q (128) | q . kappa | 0 0 0 ] per (destination, relation, head), and
+ * the result is st [n_rel, n_dst, 4, 132] (relation-major: one [n_dst, 528] operand per relation for the value block) =
+ * [ sum_e p_h(e) x_src(e) (128) | sum_e p_h(e) | 0 0 0 ] over the edges of each relation, p the per-head softmax over ALL
+ * incoming edges of the destination (exp / (sum + 1e-16)); rows of relations or destinations without edges are zero.
+ * x [n_rows, ldx >= 128] stacked feature rows; src[e] (32-bit) = row of edge e, the nnz edges sorted by (destination,
+ * relation); work items of one (item_dst, item_rel) each; rel_ptr [n_dst * n_rel + 1] = first item of every (destination,
+ * relation).  Deterministic.
+ * mdg_hgt_sum_relations: out [n_rows,128] = act(sum of the n_rel slabs of part [n_rel, n_rows, 128], in order), act = GELU
+ * (erf, the dense blocks' MDG_ACT_GELU) or none: the per-relation products of the value block summed. */
+size_t mdg_hgt_attention_feat_workspace_bytes(int64_t n_items);
+int mdg_hgt_attention_feat(const float* x, int64_t ldx, int64_t n_rows, const float* ut, const int32_t* src, int64_t nnz,
+                           const int64_t* item_dst, const int32_t* item_rel, const int64_t* item_begin, const int64_t* item_end,
+                           int64_t n_items, const int64_t* rel_ptr, float* st, int64_t n_dst, int n_rel, int heads,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int mdg_hgt_sum_relations(const float* part, int64_t n_rows, int n_rel, int apply_gelu, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------ losses ---- */
 
 /* InfoNCE finish of SimCLR_NovelDDI.contrastive_loss (madrigal/models/simclr.py:74-108): given

@@ -286,6 +286,288 @@ __global__ __launch_bounds__(256) void hgt_combine_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// The same attention in NODE-FEATURE space (inference, H = 4, D = 32).  k'_{r,h}(x) = K_{r,h} x + kappa_{r,h} and
+// v'_{r,h}(x) = V_{r,h} x + nu_{r,h} are fixed affine images of the 128-float feature row x of the source node, so
+//     logit_h(e: src -> d, relation r) = u_{d,r,h} . x_src + c_{d,r,h}             (u = K^T q_d, c = q_d . kappa: the destination side)
+//     S_{d,r,h} = sum_{e in r} p_h(e) x_src(e),   w_{d,r,h} = sum_{e in r} p_h(e)  (p: softmax over ALL in-edges of d, every relation)
+// and the caller's dense block  [S | w] -> V S + nu w  gives the aggregate.  One 512-byte row is gathered per edge instead of the
+// 1 KB k' | v' pair, and the per-relation images of every node are never computed.  Work items are relation-pure: <= CHUNK edges of
+// one (destination, relation).  Per item the wave holds the four u rows (16 VGPRs) and carries four f32x4 sums per gathered row.
+//
+// Lane roles: sub = lane & 31 owns columns 4 sub .. 4 sub + 3 of the row; hl = sub >> 3 is the head whose softmax the lane runs.
+// Everything per head is kept ROTATED by the lane's own head -- slot j of a lane belongs to head hl ^ j -- so that both cross-lane
+// exchanges below are plain lane ^ 8 / lane ^ 16 moves with no selects: the reduce-scatter of the four dot products (slots 2, 3
+// go to lane ^ 16, slot 1 to lane ^ 8, then three steps inside the 8 lanes of a head) and the all-gather of the four weights.
+// ---------------------------------------------------------------------------------------------
+struct HgtFeatArgs {
+  const float* x; int64_t ldx;          // stacked node-feature rows [n_rows, >=128]
+  const float* ut;                      // [n_dst, R, 4, 132]: u (128) | c | 0 0 0 per (destination, relation, head)
+  const int32_t* src;                   // [nnz] row of x per edge, sorted by (destination, relation)
+  const int64_t* item_dst; const int32_t* item_rel; const int64_t* item_begin; const int64_t* item_end;   // [n_items]
+  float* part_acc;                      // [n_items,4,128]
+  float* part_ml;                       // [n_items,4,2]
+  int64_t n_items;
+  int R;
+};
+
+constexpr int HGT_FEAT_ROW = 132;       // floats per (destination, relation, head) row of U~ and S~
+
+// DPP moves inside a row of 16 lanes (all lanes of the wave are active where these are used)
+template <int CTRL>
+__device__ __forceinline__ float hgt_dpp(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float hgt_xor1(float v) { return hgt_dpp<0xB1>(v); }     // quad_perm:[1,0,3,2]
+__device__ __forceinline__ float hgt_xor2(float v) { return hgt_dpp<0x4E>(v); }     // quad_perm:[2,3,0,1]
+__device__ __forceinline__ float hgt_mir8(float v) { return hgt_dpp<0x141>(v); }    // row_half_mirror: the other quad of the 8 lanes
+__device__ __forceinline__ float hgt_xor8(float v) { return hgt_dpp<0x128>(v); }    // row_ror:8
+__device__ __forceinline__ float hgt_xor16(float v) { return __shfl_xor(v, 16, 64); }
+
+__device__ __forceinline__ float hgt_dot4f(const f32x4& a, const f32x4& b) { return fmaf(a[3], b[3], fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0]))); }
+__device__ __forceinline__ void hgt_axpy4(f32x4& acc, float w, const f32x4& x) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = fmaf(w, x[c], acc[c]);
+}
+// the lane's value for its own head -> the values of heads hl, hl ^ 1, hl ^ 2, hl ^ 3
+__device__ __forceinline__ void hgt_gather_heads(float v, float (&o)[4]) {
+  o[0] = v;
+  o[1] = hgt_xor8(v);
+  o[2] = hgt_xor16(v);
+  o[3] = hgt_xor16(o[1]);
+}
+
+// one half's share of the group of 8 edges at eb (edges eb + half, eb + half + 2, ..): the rows' numbers, then the rows.  Past the
+// item's end the predicate is off and row src[e0] (cached) is read.
+__device__ __forceinline__ void hgt_feat_idx(const HgtFeatArgs& p, int64_t eb, int64_t e0, int64_t e1, int half, uint32_t (&row)[4], bool (&ok)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t e = eb + half + 2 * k;
+    ok[k] = e < e1;
+    row[k] = static_cast<uint32_t>(p.src[ok[k] ? e : e0]);      // (never negative; unsigned: widening it costs no instruction after the load)
+  }
+}
+__device__ __forceinline__ void hgt_feat_rows(const HgtFeatArgs& p, const uint32_t (&row)[4], int sub, f32x4 (&x)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = *reinterpret_cast<const f32x4*>(p.x + static_cast<int64_t>(row[k]) * p.ldx + 4 * sub);
+}
+
+// one group: four dot products per row, their reduce-scatter, the online softmax of the lane's head, the weights' all-gather,
+// four sums per row.  Fixed order.
+__device__ __forceinline__ void hgt_feat_group(const f32x4 (&u)[4], float c, const f32x4 (&x)[4], const bool (&ok)[4], float& m, float& l,
+                                               f32x4 (&acc)[4]) {
+  float a[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float r0 = hgt_dot4f(u[0], x[k]) + hgt_xor16(hgt_dot4f(u[2], x[k]));
+    const float r1 = hgt_dot4f(u[1], x[k]) + hgt_xor16(hgt_dot4f(u[3], x[k]));
+    float s = r0 + hgt_xor8(r1);
+    s += hgt_xor1(s);
+    s += hgt_xor2(s);
+    s += hgt_mir8(s);
+    a[k] = ok[k] ? s + c : -INFINITY;
+  }
+  const float mn = fmaxf(fmaxf(m, a[0]), fmaxf(fmaxf(a[1], a[2]), a[3]));
+  const float base = (mn == -INFINITY) ? 0.f : mn;                 // a half without an edge yet: every exponential below is 0
+  const float f = expf(m - base);
+  float w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) w[k] = expf(a[k] - base);
+  l = l * f + ((w[0] + w[1]) + (w[2] + w[3]));
+  m = mn;
+  float fj[4];
+  hgt_gather_heads(f, fj);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = acc[j] * fj[j];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float wj[4];
+    hgt_gather_heads(w[k], wj);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hgt_axpy4(acc[j], wj[j], x[k]);
+  }
+}
+
+__global__ __launch_bounds__(256) void hgt_attention_feat_kernel(const HgtFeatArgs p) {
+  const int lane = threadIdx.x & 63, sub = lane & 31, half = lane >> 5;
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (item >= p.n_items) return;                                   // (uniform per wave)
+  const int hl = sub >> 3;
+  const int64_t dst = p.item_dst[item], e0 = p.item_begin[item], e1 = p.item_end[item];
+  const float* urow = p.ut + (dst * p.R + p.item_rel[item]) * (4 * HGT_FEAT_ROW);
+  f32x4 u[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) u[j] = *reinterpret_cast<const f32x4*>(urow + (hl ^ j) * HGT_FEAT_ROW + 4 * sub);
+  const float c = urow[hl * HGT_FEAT_ROW + 128];
+  float m = -INFINITY, l = 0.f;
+  f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // Groups of 8 edges, four rows per half.  The trip counts are the WAVE's (an absent edge is a predicate, its weight 0), so every
+  // lane is active at the cross-lane moves.  Every gather is a dependent src -> row pair of loads and a group's arithmetic is
+  // about as long as one of them, so the loads run ahead: while group g is multiplied, the rows of g + 1 (two buffers take turns)
+  // and the row numbers of g + 2 are in flight.
+  f32x4 xa[4], xb[4];
+  uint32_t ra[4], rb[4];
+  bool oka[4], okb[4], okn[4];
+  hgt_feat_idx(p, e0, e0, e1, half, ra, oka);
+  hgt_feat_idx(p, e0 + 8, e0, e1, half, rb, okb);
+  hgt_feat_rows(p, ra, sub, xa);
+  for (int64_t eb = e0; eb < e1; eb += 16) {
+    hgt_feat_rows(p, rb, sub, xb);
+    hgt_feat_idx(p, eb + 16, e0, e1, half, ra, okn);
+    __builtin_amdgcn_sched_barrier(0);                              // the loads stay ahead of the arithmetic
+    hgt_feat_group(u, c, xa, oka, m, l, acc);
+    hgt_feat_rows(p, ra, sub, xa);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) oka[k] = okn[k];
+    const bool second = eb + 8 < e1;                                // (uniform per wave)
+    bool okc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) okc[k] = okb[k];
+    hgt_feat_idx(p, eb + 24, e0, e1, half, rb, okb);
+    __builtin_amdgcn_sched_barrier(0);
+    if (second) hgt_feat_group(u, c, xb, okc, m, l, acc);
+  }
+  // merge the two halves in a fixed order (half 0 first): both compute bit-identical sums.  Half 0 holds edge e0, so mn is finite.
+  {
+    const float mo = __shfl_xor(m, 32, 64), lo = __shfl_xor(l, 32, 64);
+    const float mn = fmaxf(m, mo);
+    const float f0 = (m == -INFINITY) ? 0.f : expf(m - mn), f1 = (mo == -INFINITY) ? 0.f : expf(mo - mn);
+    const float la = half ? lo : l, lb = half ? l : lo;
+    const float fa = half ? f1 : f0, fb = half ? f0 : f1;
+    l = la * fa + lb * fb;
+    m = mn;
+    float faj[4], fbj[4];
+    hgt_gather_heads(fa, faj);
+    hgt_gather_heads(fb, fbj);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x4 ao;
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc) ao[cc] = __shfl_xor(acc[j][cc], 32, 64);
+      const f32x4 xa = half ? ao : acc[j], xb = half ? acc[j] : ao;
+      acc[j] = xa * faj[j] + xb * fbj[j];
+    }
+  }
+  if (half == 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(p.part_acc + item * 512 + (hl ^ j) * 128 + 4 * sub) = acc[j];
+    if ((sub & 7) == 0) {
+      p.part_ml[(item * 4 + hl) * 2 + 0] = m;
+      p.part_ml[(item * 4 + hl) * 2 + 1] = l;
+    }
+  }
+}
+
+// One workgroup per destination: four groups of 128 threads, thread (h, sub) of a group owns columns 4 sub .. of head h.  First
+// the destination's (m_h, L_h) over all its items -- item i0 + k belongs to thread slot k % 128, the slots are folded in a fixed
+// tree -- then per (relation, head) the rescaled sums and masses, normalised by L_h + 1e-16, into the RELATION-MAJOR
+// S~[r, d, h, :] = [ S (128) | w | 0 0 0 ] (the V~ block then runs as one product per relation: K = 528 each instead of one
+// product of K = R * 528 that fills 20 workgroups); zeros where a relation (or the destination) has no edge.
+// rel_ptr [n_dst * R + 1]: the items of (d, r) are rel_ptr[d R + r] .. rel_ptr[d R + r + 1].  Relations of at most HGT_COOP
+// items go round the groups (relation r to group r % 4, its items summed in order); a hub relation is summed by ALL groups --
+// group g takes its items g, g + 4, .. in order, the four partial sums are added in order g = 0..3.  Which of the two a relation
+// takes depends on its item count alone (uniform per workgroup: the barriers are safe).  Fixed orders: deterministic.
+__global__ __launch_bounds__(512) void hgt_combine_feat_kernel(const float* __restrict__ part_acc, const float* __restrict__ part_ml,
+                                                               const int64_t* __restrict__ rel_ptr, float* __restrict__ st, int R,
+                                                               int64_t n_dst) {
+  __shared__ float sh_acc[4][512];
+  __shared__ float sh_w[4][4];
+  __shared__ float sh_red[8][4];
+  __shared__ float sh_ML[2][4];
+  const int g = threadIdx.x >> 7, t = threadIdx.x & 127, h = t >> 5, sub = t & 31;
+  const int64_t d = blockIdx.x;
+  const int64_t* rp = rel_ptr + d * R;
+  const int64_t i0 = rp[0], i1 = rp[R];
+  {
+    // pass 1: thread (slot = tid / 4, head hh = tid % 4); in-wave fold over the 16 slots of a wave, then over the 8 waves
+    const int hh = threadIdx.x & 3, wave = threadIdx.x >> 6;
+    float mloc = -INFINITY;
+    for (int64_t it = i0 + (threadIdx.x >> 2); it < i1; it += 128) mloc = fmaxf(mloc, part_ml[(it * 4 + hh) * 2]);
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) mloc = fmaxf(mloc, __shfl_xor(mloc, o, 64));
+    if ((threadIdx.x & 63) < 4) sh_red[wave][hh] = mloc;
+    __syncthreads();
+    float Mh = sh_red[0][hh];
+#pragma unroll
+    for (int wv = 1; wv < 8; ++wv) Mh = fmaxf(Mh, sh_red[wv][hh]);
+    __syncthreads();                                                // sh_red is written again below
+    float lloc = 0.f;
+    for (int64_t it = i0 + (threadIdx.x >> 2); it < i1; it += 128) {
+      const float mi = part_ml[(it * 4 + hh) * 2];
+      lloc += part_ml[(it * 4 + hh) * 2 + 1] * ((mi == -INFINITY) ? 0.f : expf(mi - Mh));
+    }
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) lloc += __shfl_xor(lloc, o, 64);
+    if ((threadIdx.x & 63) < 4) sh_red[wave][hh] = lloc;
+    __syncthreads();
+    if (threadIdx.x < 4) {
+      float Lh = sh_red[0][hh];
+      for (int wv = 1; wv < 8; ++wv) Lh += sh_red[wv][hh];
+      sh_ML[0][hh] = Mh;
+      sh_ML[1][hh] = Lh;
+    }
+    __syncthreads();
+  }
+  const float M = sh_ML[0][h], L = sh_ML[1][h];
+  const float denom = L + 1e-16f;                                   // torch_geometric.utils.softmax: exp / (sum + 1e-16)
+  for (int r = 0; r < R; ++r) {
+    const int64_t j0 = rp[r], j1 = rp[r + 1];
+    const bool coop = (j1 - j0) > HGT_COOP;                         // (uniform per workgroup)
+    if (!coop && (r & 3) != g) continue;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float w = 0.f;
+    const int64_t step = coop ? 4 : 1;
+#pragma unroll 4
+    for (int64_t it = j0 + (coop ? g : 0); it < j1; it += step) {
+      const float mi = part_ml[(it * 4 + h) * 2];
+      const float gi = (mi == -INFINITY) ? 0.f : expf(mi - M);
+      hgt_axpy4(acc, gi, *reinterpret_cast<const f32x4*>(part_acc + it * 512 + 4 * t));
+      w = fmaf(gi, part_ml[(it * 4 + h) * 2 + 1], w);
+    }
+    if (coop) {
+      *reinterpret_cast<f32x4*>(&sh_acc[g][4 * t]) = acc;
+      if (sub == 0) sh_w[g][h] = w;
+      __syncthreads();
+      if (g == 0) {
+        acc = *reinterpret_cast<const f32x4*>(&sh_acc[0][4 * t]);
+        w = sh_w[0][h];
+        for (int gg = 1; gg < 4; ++gg) {
+          acc += *reinterpret_cast<const f32x4*>(&sh_acc[gg][4 * t]);
+          w += sh_w[gg][h];
+        }
+      }
+    }
+    if (!coop || g == 0) {
+      f32x4 o = {0.f, 0.f, 0.f, 0.f};
+      float wo = 0.f;
+      if (L > 0.f) {
+        o = acc / denom;
+        wo = w / denom;
+      }
+      float* row = st + ((r * n_dst + d) * 4 + h) * HGT_FEAT_ROW;
+      *reinterpret_cast<f32x4*>(row + 4 * sub) = o;
+      if (sub == 0) *reinterpret_cast<f32x4*>(row + 128) = f32x4{wo, 0.f, 0.f, 0.f};
+    }
+    if (coop) __syncthreads();                                      // the shared partials are free again
+  }
+}
+
+// out[i] = act( sum_r part[r][i] ), r in order: the per-relation products of the V~ block summed, GELU on the way out
+__global__ __launch_bounds__(256) void hgt_sum_relations_kernel(const float* __restrict__ part, float* __restrict__ out, int64_t n4, int R,
+                                                                int apply_gelu) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n4) return;
+  f32x4 s = reinterpret_cast<const f32x4*>(part)[i];
+  for (int r = 1; r < R; ++r) s += reinterpret_cast<const f32x4*>(part)[r * n4 + i];
+  if (apply_gelu) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s[c] = mdg_gelu(s[c]);
+  }
+  reinterpret_cast<f32x4*>(out)[i] = s;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Backward of the HGT edge attention.  With g = d out_i (before the GELU), pre_i = sum_e alpha_e v'_e (kept from the
 // forward pass) and delta[h] = g[h] . pre_i[h]  (= sum_e alpha_e dalpha_e):
 //     dalpha_e[h] = g[h] . v'_e[h],   da_e[h] = alpha_e[h] (dalpha_e[h] - delta[h])
@@ -604,6 +886,53 @@ extern "C" int mdg_hgt_attention_rows(const float* q_base, const int64_t* q_off,
   hipLaunchKernelGGL(hgt_combine_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n_dst, 8))), dim3(256), 0, st, part_acc, part_ml, item_ptr,
                      out, ldo, n_dst, heads, apply_gelu, static_cast<float*>(nullptr));
   MDG_CHECK_LAUNCH("mdg_hgt_attention_rows");
+  return MDG_OK;
+}
+
+extern "C" size_t mdg_hgt_attention_feat_workspace_bytes(int64_t n_items) {
+  if (n_items <= 0) return 0;
+  return static_cast<size_t>(n_items) * (4 * 128 + 4 * 2) * sizeof(float);
+}
+
+// Edge attention in node-feature space (see hgt_attention_feat_kernel): S~ [n_rel, n_dst, 4, 132] from the stacked feature rows,
+// the destination-side block U~ and a relation-pure plan.  The tables are the caller's: every src[e] < n_rows, every item_dst <
+// n_dst, every item_rel < n_rel, item ranges inside [0, nnz), rel_ptr non-decreasing from 0 to n_items (graph_plans checks them).
+extern "C" int mdg_hgt_attention_feat(const float* x, int64_t ldx, int64_t n_rows, const float* ut, const int32_t* src, int64_t nnz,
+                                      const int64_t* item_dst, const int32_t* item_rel, const int64_t* item_begin,
+                                      const int64_t* item_end, int64_t n_items, const int64_t* rel_ptr, float* st, int64_t n_dst,
+                                      int n_rel, int heads, void* workspace, size_t workspace_bytes, void* stream) {
+  MDG_CHECK_ARG(heads == 4, "mdg_hgt_attention_feat: built for 4 heads of 32 (got %d)", heads);
+  MDG_CHECK_ARG(n_dst >= 0 && n_items >= 0 && nnz >= 0 && n_rows >= 0 && n_rel >= 1, "mdg_hgt_attention_feat: negative size");
+  MDG_CHECK_ARG(n_dst <= 0x7FFFFFFF && n_items <= 4 * static_cast<int64_t>(0x7FFFFFFF), "mdg_hgt_attention_feat: too many destinations / items for one launch");
+  if (n_dst == 0) return MDG_OK;
+  MDG_CHECK_ARG(ut && st && rel_ptr && (n_items == 0 || (x && src && item_dst && item_rel && item_begin && item_end && nnz > 0 && n_rows > 0)),
+                "mdg_hgt_attention_feat: null pointer");
+  MDG_CHECK_ARG(ldx % 4 == 0 && ldx >= 128 && (!x || mdg_aligned16(x)) && mdg_aligned16(ut) && mdg_aligned16(st), "mdg_hgt_attention_feat: bad stride / alignment");
+  const size_t need = mdg_hgt_attention_feat_workspace_bytes(n_items);
+  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
+    mdg_set_error("mdg_hgt_attention_feat: workspace of %zu bytes required, got %zu", need, workspace_bytes);
+    return MDG_EWORKSPACE;
+  }
+  hipStream_t st_ = static_cast<hipStream_t>(stream);
+  float* part_acc = static_cast<float*>(workspace);
+  float* part_ml = part_acc ? part_acc + n_items * 512 : nullptr;
+  if (n_items > 0) {
+    HgtFeatArgs a{x, ldx, ut, src, item_dst, item_rel, item_begin, item_end, part_acc, part_ml, n_items, n_rel};
+    hipLaunchKernelGGL(hgt_attention_feat_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n_items, 4))), dim3(256), 0, st_, a);
+  }
+  hipLaunchKernelGGL(hgt_combine_feat_kernel, dim3(static_cast<unsigned>(n_dst)), dim3(512), 0, st_, part_acc, part_ml, rel_ptr, st, n_rel, n_dst);
+  MDG_CHECK_LAUNCH("mdg_hgt_attention_feat");
+  return MDG_OK;
+}
+
+// out [n_rows,128] = act(sum over the n_rel slabs of part [n_rel, n_rows, 128]), slabs added in order
+extern "C" int mdg_hgt_sum_relations(const float* part, int64_t n_rows, int n_rel, int apply_gelu, float* out, void* stream) {
+  MDG_CHECK_ARG(n_rows >= 0 && n_rel >= 1, "mdg_hgt_sum_relations: negative size");
+  if (n_rows == 0) return MDG_OK;
+  MDG_CHECK_ARG(part && out && mdg_aligned16(part) && mdg_aligned16(out), "mdg_hgt_sum_relations: null or unaligned pointer");
+  hipLaunchKernelGGL(hgt_sum_relations_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n_rows * 32, 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     part, out, n_rows * 32, n_rel, apply_gelu);
+  MDG_CHECK_LAUNCH("mdg_hgt_sum_relations");
   return MDG_OK;
 }
 

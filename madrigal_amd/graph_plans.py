@@ -112,6 +112,42 @@ def transposed_csr(rowptr: torch.Tensor, col, w, n_src: int, mean: bool = False)
     return {"rowptr": _rowptr(src[order], n_src), "col": row_of_edge[order].contiguous(), "w": wt}
 
 
+def hgt_feat_plan(edges, n_dst: int, n_rows: int, device) -> dict:
+    """Relation-pure work items of the feature-space HGT attention (mdg_hgt_attention_feat).
+
+    ``edges``: one (src_row, dst) pair of int64 tensors per relation, in relation order -- src_row the row of the source node in
+    the stacked feature buffer of ``n_rows`` rows, dst the destination's number in [0, n_dst).  The edges of all relations are
+    stably sorted by (destination, relation) and cut into work items of <= HGT_CHUNK edges that never span two relations or two
+    destinations.  Tables: ``src`` [nnz] int32; ``item_dst`` / ``item_begin`` / ``item_end`` int64 and ``item_rel`` int32 per
+    item; ``rel_ptr`` [n_dst * R + 1] first item of every (destination, relation); ``item_ptr`` [n_dst + 1] = rel_ptr[::R]."""
+    R = len(edges)
+    if R < 1:
+        raise ValueError("hgt_feat_plan: no relation")
+    if n_rows >= 2 ** 31:
+        raise ValueError("hgt_feat_plan: 32-bit source rows need fewer than 2^31 feature rows")
+    srcs = [s.to(device).long() for s, _ in edges]
+    keys = [d.to(device).long() * R + r for r, (_, d) in enumerate(edges)]
+    src, key = torch.cat(srcs), torch.cat(keys)
+    if src.numel():
+        lo, hi, klo, khi = (int(v) for v in torch.stack([src.min(), src.max(), key.min(), key.max()]).tolist())
+        if lo < 0 or hi >= n_rows or klo < 0 or khi >= n_dst * R:
+            raise ValueError("hgt_feat_plan: an edge names a source row or a destination outside the tables")
+    order = torch.argsort(key, stable=True)
+    src, key = src[order].to(torch.int32).contiguous(), key[order]
+    key_ptr = _rowptr(key, n_dst * R)
+    cnt = key_ptr[1:] - key_ptr[:-1]
+    chunks = (cnt + HGT_CHUNK - 1) // HGT_CHUNK
+    rel_ptr = torch.zeros(n_dst * R + 1, dtype=torch.int64, device=device)
+    torch.cumsum(chunks, 0, out=rel_ptr[1:])
+    item_key = torch.repeat_interleave(torch.arange(n_dst * R, device=device), chunks)
+    k = torch.arange(item_key.numel(), device=device) - rel_ptr[item_key]
+    item_begin = key_ptr[item_key] + k * HGT_CHUNK
+    item_end = torch.minimum(item_begin + HGT_CHUNK, key_ptr[item_key + 1])
+    return {"src": src, "item_dst": (item_key // R).contiguous(), "item_rel": (item_key % R).to(torch.int32).contiguous(),
+            "item_begin": item_begin.contiguous(), "item_end": item_end.contiguous(), "rel_ptr": rel_ptr,
+            "item_ptr": rel_ptr[::R].contiguous(), "n_dst": int(n_dst), "n_rel": R, "n_rows": int(n_rows)}
+
+
 def hgt_plan(edge_index_dict, edge_types: Sequence[Tuple[str, str, str]], sizes: Dict[str, int], device, used=None, dst_range=None) -> dict:
     """Layout + CSR plan of one HGTConv call.
 
@@ -174,4 +210,5 @@ def hgt_plan(edge_index_dict, edge_types: Sequence[Tuple[str, str, str]], sizes:
         item_end = torch.minimum(item_begin + HGT_CHUNK, rowptr[item_dst + 1])
         per_dst[t] = {"col": col, "rowptr": rowptr, "item_ptr": item_ptr, "item_dst": item_dst.contiguous(),
                       "item_begin": item_begin.contiguous(), "item_end": item_end.contiguous()}
-    return {"used": used, "slot": slot, "nrel": nrel, "width": width, "base": base, "total_floats": total, "per_dst": per_dst}
+    return {"used": used, "slot": slot, "nrel": nrel, "width": width, "base": base, "total_floats": total, "per_dst": per_dst,
+            "edge_index": {et: edge_index_dict[et] for et in used}}       # the caller's tensors (no copy): hgt_feat_plan is built from them on demand

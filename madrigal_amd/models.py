@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import autograd as ag
 from . import ops
 from .data import CELL_LINES, MOL_DIM, NUM_MODALITIES, NUM_NON_TX_MODALITIES
-from .graph_plans import hgt_plan, molecule_plan, transposed_csr
+from .graph_plans import hgt_feat_plan, hgt_plan, molecule_plan, transposed_csr
 
 TX_INPUT_DIM = 978
 CELL_LINES_CAPITALIZED = [c.upper() for c in CELL_LINES]
@@ -728,6 +728,119 @@ class HGTConv(nn.Module):
             res[t] = torch.cat(cut, dim=0)
         return res
 
+    def _attend_projected(self, X_all, types_p, plan, tabs, dev):
+        """q | k' v' .. of every node in one grouped launch, then the edge attention over the gathered k' | v' rows."""
+        # stacked composite weights (rebuilt only when a parameter changes)
+        srcs = [p for t in types_p for p in (self.kqv_lin.lins[t].weight, self.kqv_lin.lins[t].bias)] + [self.k_rel.weight, self.v_rel.weight] + \
+               [self.p_rel["__".join(et)] for et in plan["used"]]
+
+        def build_w():
+            wb = [self._composite_projection(t, plan) for t in types_p]
+            return torch.cat([w for w, _ in wb], 0).contiguous(), torch.cat([b for _, b in wb], 0).contiguous()
+        W_all, b_all = _cached(self, ("proj_all", tuple(types_p), tuple(plan["used"])), srcs, build_w)
+        buf = torch.empty(max(plan["total_floats"], 128), dtype=torch.float32, device=dev)
+        ops.linear_grouped(X_all, W_all, b_all, tabs["proj"], buf, precision=_state["precision"])
+        rows_dst = tabs["rows_dst"]
+        agg_all = torch.empty((rows_dst, self.out_channels), dtype=torch.float32, device=dev)
+        if tabs["att"] is not None:
+            probe = self.__dict__.get("_attention_probe")            # bench.py: HIP events around this launch + its edge count
+            if probe is not None:
+                probe["start"].record(torch.cuda.current_stream(dev))
+            ops.hgt_attention_rows(buf, tabs["att"], self.heads, agg_all, apply_gelu=True)
+            if probe is not None:
+                probe["end"].record(torch.cuda.current_stream(dev))
+                probe["edges"], probe["dst_rows"], probe["buffer_floats"] = int(tabs["att"]["col"].numel()), int(rows_dst), int(plan["total_floats"])
+        return agg_all
+
+    # Feature-space attention (inference; DESIGN 4ad): a conv with ONE destination type whose sources all carry 128-wide rows
+    # attends over the gathered FEATURE rows -- the per-relation key / value images of every node are never computed.  It pays
+    # where the two [n_dst, R, 4, 132] blocks it streams are small against the gathers it halves: at least this many edges per
+    # (destination, relation) row on average (a row costs 2 112 B in four passes, an edge saves a 512 B gather).
+    attend_in_feature_space = True
+    feature_space_min_edges_per_row = 64
+
+    def _feature_space_ok(self, cin, dst_types, plan, sizes) -> bool:
+        F = self.out_channels
+        if not self.attend_in_feature_space or len(dst_types) != 1 or cin != F or F != 128 or self.heads * 32 != F:
+            return False
+        if _state["precision"] not in ("f32", "bf16x3"):             # bf16 already gathers 512 B per edge, from the 16-bit mirror
+            return False
+        t = dst_types[0]
+        rels = [et for et in plan["used"] if et[2] == t]
+        nnz = int(plan["per_dst"][t]["col"].numel())
+        return bool(rels) and nnz > 0 and sizes[t] * len(rels) * self.feature_space_min_edges_per_row <= nnz
+
+    def _feature_space_composites(self, t: str, rels):
+        """(W_u, b_u, W_v) of destination type t over the relations ``rels``, composed in fp64 on the host:
+        U~ = x_d W_u^T + b_u  [R, H, 132] = [K_{r,h}^T q_{d,h} | q_{d,h} . kappa_{r,h} | 0 0 0]   and
+        agg = S~ W_v^T  with block (r, h) of W_v = [V_{r,h} | nu_{r,h} | 0 0 0] feeding the 32 output columns of head h."""
+        F, H = self.out_channels, self.heads
+        D, P = F // H, ops.HGT_FEAT_ROW
+        f64 = lambda p: p.detach().to("cpu", torch.float64)          # noqa: E731
+        lin_t = self.kqv_lin.lins[t]
+        Wq, bq = f64(lin_t.weight)[F:2 * F], f64(lin_t.bias)[F:2 * F]
+        kr, vr, Rn = f64(self.k_rel.weight), f64(self.v_rel.weight), len(self.edge_types)
+        W_u = torch.zeros(len(rels), H, P, F, dtype=torch.float64)
+        b_u = torch.zeros(len(rels), H, P, dtype=torch.float64)
+        W_v = torch.zeros(F, len(rels), H, P, dtype=torch.float64)
+        for i, et in enumerate(rels):
+            W, b = f64(self.kqv_lin.lins[et[0]].weight), f64(self.kqv_lin.lins[et[0]].bias)
+            r = self.edge_types.index(et)
+            pr = f64(self.p_rel["__".join(et)]).view(H) / math.sqrt(D)
+            for h in range(H):
+                hs = slice(h * D, (h + 1) * D)
+                A_k, A_v = kr[h * Rn + r] * pr[h], vr[h * Rn + r]              # k'_h = k_h A_k, v'_h = v_h A_v (row vectors)
+                K, kap = A_k.t() @ W[0:F][hs], A_k.t() @ b[0:F][hs]              # [D,F], [D]
+                V, nu = A_v.t() @ W[2 * F:3 * F][hs], A_v.t() @ b[2 * F:3 * F][hs]
+                W_u[i, h, :F] = K.t() @ Wq[hs]
+                b_u[i, h, :F] = K.t() @ bq[hs]
+                W_u[i, h, F] = kap @ Wq[hs]
+                b_u[i, h, F] = kap @ bq[hs]
+                W_v[hs, i, h, :F] = V
+                W_v[hs, i, h, F] = nu
+        return W_u.view(-1, F), b_u.view(-1), W_v.view(F, -1)
+
+    def _feature_space_weights(self, t: str, rels):
+        """The composites as fp32 device tensors, rebuilt only when a parameter changes."""
+        lin_t = self.kqv_lin.lins[t]
+        stypes = sorted({et[0] for et in rels})
+        srcs = [lin_t.weight, lin_t.bias] + [p for s in stypes for p in (self.kqv_lin.lins[s].weight, self.kqv_lin.lins[s].bias)] + \
+               [self.k_rel.weight, self.v_rel.weight] + [self.p_rel["__".join(et)] for et in rels]
+
+        def build():
+            W_u, b_u, W_v = self._feature_space_composites(t, rels)
+            F, Rn = self.out_channels, len(rels)
+            W_v = W_v.view(F, Rn, -1).permute(1, 0, 2).reshape(Rn * F, -1)        # one [128, 528] block per relation, stacked
+            return tuple(w.to(torch.float32).to(lin_t.weight.device).contiguous() for w in (W_u, b_u, W_v))
+        return _cached(self, ("feat_space", t, tuple(rels)), srcs, build)
+
+    def _attend_feature_space(self, X_all, row0, t, plan, sizes, dev):
+        """gelu(sum_e alpha_e v'_e) of destination type t from the stacked feature rows: U~ (one dense block of the destination
+        rows), the feature-space attention and its combine, the V~ block as one product per relation, their sum and the GELU."""
+        rels = [et for et in plan["used"] if et[2] == t]
+        fkey = ("feat_plan", t, tuple(sorted(row0.items())))
+        fp = plan.get(fkey)
+        if fp is None:
+            edges = [(row0[et[0]] + plan["edge_index"][et][0].to(dev).long(), plan["edge_index"][et][1].to(dev).long()) for et in rels]
+            fp = plan[fkey] = hgt_feat_plan(edges, sizes[t], int(X_all.shape[0]), dev)
+        W_u, b_u, W_v = self._feature_space_weights(t, rels)
+        n, Rn = sizes[t], len(rels)
+        ut = _lin(X_all[row0[t]: row0[t] + n], W_u, b_u).view(n, Rn, self.heads, ops.HGT_FEAT_ROW)
+        probe = self.__dict__.get("_attention_probe")
+        if probe is not None:
+            probe["start"].record(torch.cuda.current_stream(dev))
+        st = ops.hgt_attention_feat(X_all, ut, fp, self.heads)
+        if probe is not None:
+            probe["end"].record(torch.cuda.current_stream(dev))
+            probe["edges"], probe["dst_rows"], probe["buffer_floats"] = int(fp["src"].numel()), int(n), 2 * int(ut.numel())
+        # the V~ block as one product per relation (S~ is relation-major) in ONE grouped launch, then their sum and the GELU
+        if "v_tiles" not in fp:
+            F = self.out_channels
+            fp["v_tiles"] = ops.group_tile_table([dict(m_base=r * n, rows=n, n_base=r * F, n=F, y_off=r * n * F, ldy=F) for r in range(Rn)], dev)
+        part = torch.empty((Rn, n, self.out_channels), dtype=torch.float32, device=dev)
+        ops.linear_grouped(st.view(Rn * n, -1), W_v, None, fp["v_tiles"], part, precision=_state["precision"])
+        return ops.hgt_sum_relations(part, apply_gelu=True)
+
     def _forward_grouped(self, x_dict, plan, sizes, want, dev):
         """Inference conv with the per-node-type layers grouped: the composite projections of all node types are ONE launch
         (mdg_linear_grouped over the stacked inputs and the stacked composite weights) and so are the output projections with
@@ -757,14 +870,6 @@ class HGTConv(nn.Module):
         for t in types_p:
             row0[t] = r
             r += sizes[t]
-        # stacked composite weights (rebuilt only when a parameter changes) and the tile tables (per plan)
-        srcs = [p for t in types_p for p in (self.kqv_lin.lins[t].weight, self.kqv_lin.lins[t].bias)] + [self.k_rel.weight, self.v_rel.weight] + \
-               [self.p_rel["__".join(et)] for et in plan["used"]]
-
-        def build_w():
-            wb = [self._composite_projection(t, plan) for t in types_p]
-            return torch.cat([w for w, _ in wb], 0).contiguous(), torch.cat([b for _, b in wb], 0).contiguous()
-        W_all, b_all = _cached(self, ("proj_all", tuple(types_p), tuple(plan["used"])), srcs, build_w)
         dst_types = [t for t in self.node_types if t in self.dst_node_types and t in x_dict and t in want and sizes[t] > 0]
         gated = cin == F
         tkey = ("tables", tuple(types_p), tuple(dst_types), tuple(sizes[t] for t in types_p), cin)
@@ -794,18 +899,11 @@ class HGTConv(nn.Module):
             pieces["item_ptr"].append(torch.tensor([n_it], dtype=torch.int64, device=dev))
             att = {k: torch.cat(v).contiguous() for k, v in pieces.items()} if dst_types else None
             tabs = plan[tkey] = {"proj": ops.group_tile_table(groups, dev), "drow": drow, "rows_dst": d0, "out": None, "alphas": None, "att": att}
-        buf = torch.empty(max(plan["total_floats"], 128), dtype=torch.float32, device=dev)
-        ops.linear_grouped(X_all, W_all, b_all, tabs["proj"], buf, precision=_state["precision"])
         drow, rows_dst = tabs["drow"], tabs["rows_dst"]
-        agg_all = torch.empty((rows_dst, F), dtype=torch.float32, device=dev)
-        if tabs["att"] is not None:
-            probe = self.__dict__.get("_attention_probe")            # bench.py: HIP events around this launch + its edge count
-            if probe is not None:
-                probe["start"].record(torch.cuda.current_stream(dev))
-            ops.hgt_attention_rows(buf, tabs["att"], self.heads, agg_all, apply_gelu=True)
-            if probe is not None:
-                probe["end"].record(torch.cuda.current_stream(dev))
-                probe["edges"], probe["dst_rows"], probe["buffer_floats"] = int(tabs["att"]["col"].numel()), int(rows_dst), int(plan["total_floats"])
+        if self._feature_space_ok(cin, dst_types, plan, sizes):
+            agg_all = self._attend_feature_space(X_all, row0, dst_types[0], plan, sizes, dev)
+        else:
+            agg_all = self._attend_projected(X_all, types_p, plan, tabs, dev)
         alphas = tuple(self._skip_alpha(t) if gated else 1.0 for t in dst_types)
         if tabs["out"] is None or tabs["alphas"] != alphas:             # the gates sit in the table: rebuilt when a skip parameter changes
             groups = [dict(m_base=drow[t], rows=sizes[t], n_base=F * i, n=F, y_off=drow[t] * F, ldy=F, alpha=a, beta=1.0 - a,

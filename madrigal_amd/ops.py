@@ -1481,6 +1481,41 @@ def hgt_attention_rows(buf: torch.Tensor, plan_all: dict, heads: int, out: torch
     return out
 
 
+HGT_FEAT_ROW = 132       # floats per (destination, relation, head) row of the feature-space blocks: 128 | 1 | 3 zeros
+
+
+def hgt_attention_feat(x: torch.Tensor, ut: torch.Tensor, plan: dict, heads: int = 4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Edge attention in node-feature space (inference).  ``x`` [n_rows, 128]: the stacked feature rows the plan's
+    ``src`` indexes; ``ut`` [n_dst, R, 4, 132] = [K^T q | q . kappa | 0 0 0]; ``plan``: graph_plans.hgt_feat_plan.  Returns the
+    relation-major S~ [R, n_dst, 4, 132] = [sum_e p_h(e) x_src(e) | sum_e p_h(e) | 0 0 0], p the softmax over all in-edges."""
+    n_dst, R = int(plan["n_dst"]), int(plan["n_rel"])
+    if x.dim() != 2 or x.shape[1] != 128 or x.stride(1) != 1 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError("hgt_attention_feat: x must be fp32 cuda [n_rows,128] with unit inner stride")
+    if x.shape[0] != plan["n_rows"]:
+        raise ValueError(f"hgt_attention_feat: the plan indexes {plan['n_rows']} feature rows, x has {x.shape[0]}")
+    if heads != 4 or tuple(ut.shape) != (n_dst, R, 4, HGT_FEAT_ROW) or not ut.is_contiguous() or ut.dtype != torch.float32 or ut.device != x.device:
+        raise ValueError(f"hgt_attention_feat: ut must be contiguous fp32 [{n_dst},{R},4,{HGT_FEAT_ROW}] on x's device (4 heads)")
+    if out is None:
+        out = torch.empty((R, n_dst, 4, HGT_FEAT_ROW), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (R, n_dst, 4, HGT_FEAT_ROW) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != x.device:
+        raise ValueError(f"hgt_attention_feat: out must be contiguous fp32 [{R},{n_dst},4,{HGT_FEAT_ROW}] on x's device")
+    n_items = int(plan["item_dst"].numel())
+    ws, nbytes = _scratch("mdg_hgt_attention_feat_workspace_bytes", x.device, n_items)
+    call("mdg_hgt_attention_feat", _ptr(x), x.stride(0), x.shape[0], _ptr(ut), _ptr(plan["src"]), int(plan["src"].numel()), _ptr(plan["item_dst"]),
+         _ptr(plan["item_rel"]), _ptr(plan["item_begin"]), _ptr(plan["item_end"]), n_items, _ptr(plan["rel_ptr"]), _ptr(out), n_dst, R, heads,
+         _ptr(ws), nbytes, _stream(x))
+    return out
+
+
+def hgt_sum_relations(part: torch.Tensor, apply_gelu: bool = True) -> torch.Tensor:
+    """act(sum_r part[r]) of ``part`` [R, n, 128], slabs added in order; act = the erf GELU of the dense blocks, or none."""
+    if part.dim() != 3 or part.shape[0] < 1 or part.shape[2] != 128 or not part.is_contiguous() or not part.is_cuda or part.dtype != torch.float32:
+        raise ValueError("hgt_sum_relations: part must be contiguous fp32 cuda [R,n,128]")
+    out = torch.empty((part.shape[1], 128), dtype=torch.float32, device=part.device)
+    call("mdg_hgt_sum_relations", _ptr(part), part.shape[1], part.shape[0], 1 if apply_gelu else 0, _ptr(out), _stream(part))
+    return out
+
+
 def l2_normalize(x: torch.Tensor) -> torch.Tensor:
     """F.normalize(x, p=2, dim=-1)."""
     forward_only(x)

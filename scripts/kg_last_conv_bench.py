@@ -3,8 +3,11 @@ read), inference, alone on the device: each conv as a whole and, inside it, its 
 ``_attention_probe`` events), so that the two ``hgt_attention_kernel`` launches of a step -- the first conv over every destination
 type, the last conv over the drug destinations only -- are known apart and the last conv splits into projection + output
 blocks | attention.  Device events, median of --reps forwards; the plan of each conv also gives its edge and destination counts.
+Measured twice: with the k' | v' rows of every node projected (``attend_in_feature_space`` off) and with the last conv attending
+in node-feature space (its "attention" is then the feature-space kernel and its combine; the two dense blocks beside it count
+as the rest), and the drug rows of the two are compared.
 
-    python scripts/kg_last_conv_bench.py [--out profiles/kgfold_before_last_conv.json] [--nodes 130000] [--edges 8000000] [--reps 20]"""
+    python scripts/kg_last_conv_bench.py [--out profiles/featspace_last_conv.json] [--nodes 130000] [--edges 8000000] [--reps 20]"""
 import argparse
 import json
 import os
@@ -19,7 +22,7 @@ from madrigal_amd import configs, data as D, models as M      # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/kgfold_before_last_conv.json")
+    ap.add_argument("--out", default="profiles/featspace_last_conv.json")
     ap.add_argument("--drugs", type=int, default=4096)
     ap.add_argument("--nodes", type=int, default=130_000)
     ap.add_argument("--edges", type=int, default=8_000_000)
@@ -49,29 +52,38 @@ def main():
         whole[1].record()
         return out["drug"]
 
-    times = {f"conv{i}": [] for i in range(len(convs))}
-    times.update({f"conv{i}_attention": [] for i in range(len(convs))})
-    times["both_convs"] = []
-    with torch.no_grad(), M.precision(a.precision):
-        for i, conv in enumerate(convs):
-            conv.__dict__["_attention_probe"] = probes[i]
-        for rep in range(a.reps + 3):
-            rows = forward()
-            torch.cuda.synchronize()
-            if rep < 3:
-                continue
-            for i in range(len(convs)):
-                times[f"conv{i}"].append(marks[i][0].elapsed_time(marks[i][1]))
-                times[f"conv{i}_attention"].append(probes[i]["start"].elapsed_time(probes[i]["end"]))
-            times["both_convs"].append(whole[0].elapsed_time(whole[1]))
-        for conv in convs:
-            conv.__dict__.pop("_attention_probe", None)
-    res = {"device": torch.cuda.get_device_name(0), "precision": a.precision, "nodes": a.nodes, "reps": a.reps, "drug_rows": int(rows.shape[0]),
-           "ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()},
-           "attention_launch": {f"conv{i}": {"edges": p["edges"], "destination_rows": p["dst_rows"], "projection_buffer_MB": p["buffer_floats"] * 4 / 1e6}
-                                for i, p in enumerate(probes)}}
-    for i in range(len(convs)):
-        res["ms"][f"conv{i}_projection_and_output_blocks"] = {"median": res["ms"][f"conv{i}"]["median"] - res["ms"][f"conv{i}_attention"]["median"]}
+    def measure(feature_space: bool) -> dict:
+        times = {f"conv{i}": [] for i in range(len(convs))}
+        times.update({f"conv{i}_attention": [] for i in range(len(convs))})
+        times["both_convs"] = []
+        with torch.no_grad(), M.precision(a.precision):
+            for i, conv in enumerate(convs):
+                conv.__dict__["_attention_probe"] = probes[i]
+                conv.attend_in_feature_space = feature_space
+            for rep in range(a.reps + 3):
+                rows = forward()
+                torch.cuda.synchronize()
+                if rep < 3:
+                    continue
+                for i in range(len(convs)):
+                    times[f"conv{i}"].append(marks[i][0].elapsed_time(marks[i][1]))
+                    times[f"conv{i}_attention"].append(probes[i]["start"].elapsed_time(probes[i]["end"]))
+                times["both_convs"].append(whole[0].elapsed_time(whole[1]))
+            for conv in convs:
+                conv.__dict__.pop("_attention_probe", None)
+        res = {"ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()},
+               "attention_launch": {f"conv{i}": {"edges": p["edges"], "destination_rows": p["dst_rows"], "buffer_MB": p["buffer_floats"] * 4 / 1e6}
+                                    for i, p in enumerate(probes)}}
+        for i in range(len(convs)):
+            res["ms"][f"conv{i}_everything_but_attention"] = {"median": res["ms"][f"conv{i}"]["median"] - res["ms"][f"conv{i}_attention"]["median"]}
+        return res, rows.clone()
+
+    # the last conv with its k' | v' rows projected for every node (attend_in_feature_space off), then attending in feature space
+    projected, rows_p = measure(False)
+    feature, rows_f = measure(True)
+    res = {"device": torch.cuda.get_device_name(0), "precision": a.precision, "nodes": a.nodes, "reps": a.reps, "drug_rows": int(rows_p.shape[0]),
+           "projected": projected, "feature_space": feature,
+           "max_abs_difference_over_scale": float((rows_f - rows_p).abs().max() / rows_p.abs().max())}
     print(json.dumps(res, indent=1))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
