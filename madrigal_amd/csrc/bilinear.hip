@@ -19,7 +19,7 @@
 // k ordering: fp32 MFMA consumes k = 8q+4h+e (q: 16-byte chunk pair, h: lane half, e: element) for
 // BOTH operands -- any permutation of k is legal as long as A and B agree -- which turns the
 // per-MFMA scalar operand into one ds_read_b128 per four MFMAs.
-#include "bilinear_tiles.h"
+#include "sweep_reduce.h"      // mma16x16, f32x4v: shared with the in-sweep products
 #include <stdlib.h>
 
 namespace {
@@ -421,16 +421,6 @@ __global__ __launch_bounds__(64 * NW, 2) void bilinear_allpairs_kernel(const Bil
 // envelope (MI355X_MICROARCH.md, DVFS give-back (7): the 16x16x32 form delivers ~1.15x the FLOP/s of 32x32x16 at equal
 // cycles per FLOP because the card holds a higher clock under it).  Per stage and wave: 16 ds_read_b128 (one per 16-column
 // tile and 32-deep k step), each feeding the 4 row tiles: 64 MFMAs.
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-template <int MODE>
-__device__ __forceinline__ f32x4v mma16x16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  if constexpr (MODE == MDG_PREC_F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // A operand of the 16x16x32 form for the 32 rows of a wave, from the wave's [32][64] fp32 slab of T (columns 64 st .. +63):
 // lane (c16, g4) holds row 16 rt + c16, k = 32 ks + 8 g4 .. +7.
 template <int MODE>
@@ -925,8 +915,6 @@ __global__ void round_f16_kernel(const float* __restrict__ x, _Float16* __restri
   o[0] = static_cast<_Float16>(v.x); o[1] = static_cast<_Float16>(v.y); o[2] = static_cast<_Float16>(v.z); o[3] = static_cast<_Float16>(v.w);
   reinterpret_cast<f16x4*>(y)[i] = o;
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 template <int MODE, int NW>
 int launch_allpairs_nw(const BilinearArgs& a, int epilogue, hipStream_t st) {

@@ -279,4 +279,62 @@ __device__ __forceinline__ void compute_tile_spread(const AFrag<MODE>& A, const 
 // accumulator register v of lane (r,h) is element [row (v&3)+8(v>>2)+4h][col r] of the 32x32 tile
 __device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
 
+// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
+template <int MODE>
+__global__ void operand_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float4 v = reinterpret_cast<const float4*>(x)[i];
+  const float f[4] = {v.x, v.y, v.z, v.w};
+  if constexpr (MODE == MDG_PREC_F16) {
+    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+    f16x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
+    reinterpret_cast<f16x4*>(hi)[i] = o;
+  } else {
+    bf16x4 hv, lw;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      __bf16 a, b;
+      mdg_split_bf16(f[c], a, b);
+      hv[c] = a;
+      lw[c] = b;
+    }
+    reinterpret_cast<bf16x4*>(hi)[i] = hv;
+    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
+  }
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+// Workspace of the images, laid out zhi | whi | zlo | wlo (the lo halves in bf16x3 only), every part 256-byte aligned; fp32 needs none.
+inline size_t head_images_workspace_bytes(int64_t n_tail, int64_t n_labels, int64_t D_, int precision) {
+  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
+  const size_t z = align256(static_cast<size_t>(n_tail) * D_ * 2), w = align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
+  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+}
+
+// Points the two operands at what the kernels of MODE read: the caller's fp32 arrays, or their images, made in `ws` on the stream
+// (two launches; the caller checks them).
+template <int MODE>
+void make_head_images(TileSrc& zt, TileSrc& w, const float* z_tail, const float* w_sym, int64_t n_tail, int64_t n_labels, char* ws, hipStream_t st) {
+  if constexpr (MODE == MDG_PREC_F32) {
+    zt.f32 = z_tail;
+    w.f32 = w_sym;
+  } else {
+    const size_t zb = align256(static_cast<size_t>(n_tail) * D * 2), wb = align256(static_cast<size_t>(n_labels) * D * D * 2);
+    const bool x3 = MODE == MDG_PREC_BF16X3;
+    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
+    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
+    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
+    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
+    const int64_t z4 = n_tail * D / 4, w4 = n_labels * D * D / 4;
+    hipLaunchKernelGGL(operand_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
+    hipLaunchKernelGGL(operand_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
+    zt.hi = zhi; zt.lo = zlo;
+    w.hi = whi; w.lo = wlo;
+  }
+}
+
 }  // namespace

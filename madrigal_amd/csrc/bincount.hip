@@ -6,10 +6,10 @@
 //
 // The histogram part of the reducing epilogue (top-k is topk.hip): nothing of [L,N,N] is materialised.  With the edges at the
 // scores of screened hits, the cumulative counts are the hits' exact ranks among all pairs (notebooks/normalize_scores.py:36-74);
-// with evenly spaced edges they are a score histogram.  The score arithmetic is the sweep's own -- the two kernels below are
-// the row-statistics sweeps of bilinear.hip exactly as topk.hip carries them (same prologue, same staging, same MFMA sequence
-// per accumulator element), with the epilogue replaced, so every counted score equals the general sweep's bit for bit in
-// f32 / bf16x3 (bf16 / f16: the 16x16x32 regrouping, <= 2e-6 of the scale, as for top-k).
+// with evenly spaced edges they are a score histogram.  The two kernels below are the row-statistics sweeps of bilinear.hip
+// as topk.hip carries them (same prologue, same staging, same MFMA sequence per accumulator element) with the epilogue replaced, so
+// every counted score equals the general sweep's bit for bit in f32 / bf16x3 (bf16 / f16: the 16x16x32 regrouping, <= 2e-6 of the
+// scale, as for top-k).  The launch side is shared with topk.hip and select.hip (sweep_reduce.h).
 //
 // Epilogue.  One workgroup = one outcome (blockIdx.y), so the edge table is workgroup-uniform: the B edges and B + 1 u32
 // counters sit in LDS behind the three stage buffers (96 KB + 8 KB + 16 B of 160 KB).
@@ -28,24 +28,18 @@
 //
 // SPLIT instantiations (mdg_bilinear_bincount_split): the same counts kept in TWO tables, by the element's bit of a
 // known-pair bitmap (pairmask.hip) -- table 0: eligible pairs whose bit is clear, table 1: eligible pairs whose bit is set.  Nothing
-// is excluded: the two tables sum to the counts above.  The words of a tile reach LDS by one or two more LDS-DMAs in the tile's group
-// (pairmask.h, as in topk.hip / select.hip); the slots sit right behind the stage buffers, the edges and the two counter tables
-// behind them.  A (sub-)tile whose words are all zero for the wave takes the path above into table 0; otherwise the ballots of the
+// is excluded: the two tables sum to the counts above.  The mask slots of the ring sit right behind the stage buffers, the edges and
+// the two counter tables behind them.  A (sub-)tile whose words are all zero for the wave takes the path above into table 0; otherwise the ballots of the
 // fast path are split by the ballot of the bit and the slow path adds to cnt + bit * stride + bin.  An ineligible element has its
 // bit forced clear, so that its -inf and the correction for it both land in table 0.  The SPLIT = false kernels are what they were.
-#include "pairmask.h"
+#include "sweep_reduce.h"
 
 namespace {
 
 constexpr int BINCOUNT_MAX_EDGES = 1024;
-constexpr int BINCOUNT_LDS_BYTES = 3 * STAGE_BYTES + BINCOUNT_MAX_EDGES * 4 + (BINCOUNT_MAX_EDGES + 4) * 4;
 constexpr int BINCOUNT_TABLE = BINCOUNT_MAX_EDGES + 4;      // SPLIT: words from table 0 to table 1
-// LDS of a SPLIT sweep: per stage buffer and wave, NMW mask slots of 256 bytes behind the three stage buffers (the arrangement of
-// topk.hip / select.hip), then the edges and the two counter tables.
-template <int NMW> constexpr int bincount_mask_stage = 8 * NMW * PAIRMASK_SLOT;
-template <bool SPLIT, int NMW> constexpr int bincount_tables_off = 3 * STAGE_BYTES + (SPLIT ? 3 * bincount_mask_stage<NMW> : 0);
-template <bool SPLIT, int NMW>
-constexpr int bincount_lds_bytes = SPLIT ? bincount_tables_off<true, NMW> + BINCOUNT_MAX_EDGES * 4 + 2 * BINCOUNT_TABLE * 4 : BINCOUNT_LDS_BYTES;
+// LDS behind the ring's (sweep_lds_bytes: the stage buffers, SPLIT: and the mask slots): the edges, then one or two counter tables.
+template <bool SPLIT> constexpr int bincount_tables_bytes = BINCOUNT_MAX_EDGES * 4 + (SPLIT ? 2 : 1) * BINCOUNT_TABLE * 4;
 
 struct BincountArgs {
   const float* z_head;
@@ -66,15 +60,6 @@ template <> struct BincountKArgs<true> : BincountArgs { PairMask mask; };
 __device__ __forceinline__ bool bincount_eligible(int mode, int64_t row, int64_t col, int64_t n_head, int64_t n_tail) {
   const bool pair = mode == MDG_TOPK_NOT_SELF ? col != row : col < row;                 // (bitwise: selects, no branches)
   return (row < n_head) & (col < n_tail) & ((mode == MDG_TOPK_ALL) | pair);
-}
-
-// column tiles a workgroup with head rows [row0, row0 + BM) has to visit: LOWER needs columns j <= last row - 1 only
-__device__ __forceinline__ int bincount_tiles(const BincountArgs& p, int64_t row0, int BM) {
-  const int nst = static_cast<int>((p.n_tail + BN - 1) / BN);
-  if (p.eligible != MDG_TOPK_LOWER) return nst;
-  const int64_t last = (row0 + BM < p.n_head ? row0 + BM : p.n_head) - 1;      // columns [0, last) are eligible for some row
-  const int need = static_cast<int>((last + BN - 1) / BN);
-  return need < 1 ? 1 : (need < nst ? need : nst);
 }
 
 // The wave's two fast-path counts and the edge / counter tables in LDS.
@@ -219,6 +204,9 @@ __device__ __forceinline__ void bincount_end(const BinState& b, const BinSplit& 
   }
 }
 
+// The two kernels below carry the sweep itself -- prologue, three-buffer LDS-DMA ring with its hand-counted waits, mask-word DMAs --
+// as topk.hip, select.hip and bincount.hip each do: sharing that text between them was tried and measured 0.2 - 2.9 % slower in some
+// instantiations whichever way it was spelled, so a change to the ring is made in all three files.
 // ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the counting epilogue ---------------------------------------
 // SPLIT: the 64 words [row block of the wave][columns of the tile] ride with the tile: one more LDS-DMA per wave and tile group into
 // a slot of the wave's own, so a group is NDMA + 1 = 5 instructions and the wait keeps 5 in flight.  Lane (r, h) reads words r and
@@ -236,7 +224,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount_kernel(const Bincoun
   const int64_t row0 = rbk * BM;
   BinState bs;
   BinSplit sp{0u, 0u};
-  bincount_begin<SPLIT>(bs, p, smem + bincount_tables_off<SPLIT, 1>, l, tid);
+  bincount_begin<SPLIT>(bs, p, smem + sweep_lds_bytes<SPLIT, 1>, l, tid);
 
   // ---------------- prologue: T = z_head[rows] . W_sym[l], kept as the A operand (as in bilinear.hip) -------------
   AFrag<MODE> At;
@@ -278,14 +266,14 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount_kernel(const Bincoun
   }
 
   // ---------------- sweep: three stage buffers, prefetch distance two, ascending column tiles -------------
-  const int nst = bincount_tiles(p, row0, BM);
+  const int nst = sweep_tiles(p.eligible, row0, BM, p.n_head, p.n_tail);
   const int64_t wrow0 = row0 + wave * 32;        // this wave's rows: wrow0 .. wrow0 + 31
   const int mode = p.eligible;
   constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
   static_assert(NDMA == 4, "vmcnt immediate below");
-  // SPLIT: the wave's mask slot of stage buffer b is mslot + b * bincount_mask_stage<1>; every group of DMAs below (tile + words) is
+  // SPLIT: the wave's mask slot of stage buffer b is mslot + b * sweep_mask_stage<1>; every group of DMAs below (tile + words) is
   // issued together, so "the last group in flight" is 5 instructions instead of 4 and nothing else about the chain changes.
-  constexpr int MSTAGE = bincount_mask_stage<1>;
+  constexpr int MSTAGE = sweep_mask_stage<1>;
   const char* const mslot = smem + 3 * STAGE_BYTES + wave * PAIRMASK_SLOT;
   const unsigned* mplane = nullptr;
   if constexpr (SPLIT) mplane = p.mask.words + l * p.mask.plane_stride;             // workgroup-uniform
@@ -359,16 +347,6 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount_kernel(const Bincoun
 }
 
 // ---- bf16 / f16: bilinear_rowstats16_kernel (v_mfma_f32_16x16x32, 64 rows per wave) with the counting epilogue -----------------
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-template <int MODE>
-__device__ __forceinline__ f32x4v bincount_mma16x16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  if constexpr (MODE == MDG_PREC_F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // SPLIT: the wave's 64 rows are two row blocks of the mask, so two mask DMAs per tile group (2 + 2 = 4 in flight) and eight words per
 // lane and tile: word [ct][rt >> 1] holds the rows of acc[rt] at bits 16 (rt & 1) + 4 g4 + i.  Decided per 16-column sub-tile.
 template <int MODE, bool SPLIT>
@@ -383,7 +361,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount16_kernel(const Binco
   const int64_t row0 = rbk * BM;
   BinState bs;
   BinSplit sp{0u, 0u};
-  bincount_begin<SPLIT>(bs, p, smem + bincount_tables_off<SPLIT, 2>, l, tid);
+  bincount_begin<SPLIT>(bs, p, smem + sweep_lds_bytes<SPLIT, 2>, l, tid);
   // ---- prologue: T = z_head[rows] . W_sym[l] (32x32x16 products, as every other path), re-laid out for 16x16x32 ----
   bf16x8 A16[4][4];                                  // [row tile of 16][k step of 32]: lane (c16, g4) holds row c16, k = 32 ks + 8 g4 ..+7
 #pragma unroll
@@ -433,10 +411,10 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount16_kernel(const Binco
     __syncthreads();
   }
   // ---- sweep ----
-  const int nst = bincount_tiles(p, row0, BM);
+  const int nst = sweep_tiles(p.eligible, row0, BM, p.n_head, p.n_tail);
   const int64_t wrow0 = row0 + wave * 64;            // this wave's rows: wrow0 .. wrow0 + 63
   const int mode = p.eligible;
-  constexpr int MSTAGE = bincount_mask_stage<2>;
+  constexpr int MSTAGE = sweep_mask_stage<2>;
   const char* const mslot = smem + 3 * STAGE_BYTES + wave * 2 * PAIRMASK_SLOT;
   const unsigned* mplane = nullptr;
   if constexpr (SPLIT) mplane = p.mask.words + l * p.mask.plane_stride;             // workgroup-uniform
@@ -483,7 +461,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount16_kernel(const Binco
       for (int ks = 0; ks < 4; ++ks) {
         const bf16x8 b = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(16 * ct + c16, 4 * ks + g4));
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = bincount_mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
       }
       const int64_t col = tcol0 + 16 * ct + c16;
       // SPLIT: decided per 16-column sub-tile (wave-uniform); word g holds rows 32 g .. 32 g + 31, i.e. acc[2 g] and acc[2 g + 1]
@@ -525,73 +503,13 @@ __global__ __launch_bounds__(512, 1) void bilinear_bincount16_kernel(const Binco
   bincount_end<SPLIT>(bs, sp, p, l, tid);
 }
 
-// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
-template <int MODE>
-__global__ void bincount_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float4 v = reinterpret_cast<const float4*>(x)[i];
-  const float f[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (MODE == MDG_PREC_F16) {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-    f16x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
-    reinterpret_cast<f16x4*>(hi)[i] = o;
-  } else {
-    bf16x4 hv, lw;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      __bf16 a, b;
-      mdg_split_bf16(f[c], a, b);
-      hv[c] = a;
-      lw[c] = b;
-    }
-    reinterpret_cast<bf16x4*>(hi)[i] = hv;
-    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
-  }
-}
-
-inline size_t bincount_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
 template <int MODE, bool SPLIT>
 int launch_bincount(BincountKArgs<SPLIT>& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st, const char* fn) {
-  if constexpr (MODE == MDG_PREC_F32) {
-    a.zt.f32 = z_tail;
-    a.w.f32 = w_sym;
-  } else {
-    const size_t zb = bincount_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = bincount_align256(static_cast<size_t>(n_labels) * D * D * 2);
-    const bool x3 = MODE == MDG_PREC_BF16X3;
-    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
-    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
-    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
-    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
-    const int64_t z4 = a.n_tail * D / 4, w4 = n_labels * D * D / 4;
-    hipLaunchKernelGGL(bincount_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
-    hipLaunchKernelGGL(bincount_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
-    MDG_CHECK_LAUNCH(fn);
-    a.zt.hi = zhi; a.zt.lo = zlo;
-    a.w.hi = whi; a.w.lo = wlo;
-  }
-  if constexpr (SPLIT) {                          // more dynamic LDS than the unsplit sweeps use: raise the kernel's limit once
-    static bool attr_done = false;
-    if (!attr_done) {
-      if constexpr (kSingle16<MODE>)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_bincount16_kernel<MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bincount_lds_bytes<true, 2>);
-      else
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_bincount_kernel<MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bincount_lds_bytes<true, 1>);
-      attr_done = true;
-    }
-  }
-  if constexpr (kSingle16<MODE>) {
-    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_bincount16_kernel<MODE, SPLIT>), grid, dim3(512), (bincount_lds_bytes<SPLIT, 2>), st, a);
-  } else {
-    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_bincount_kernel<MODE, SPLIT>), grid, dim3(512), (bincount_lds_bytes<SPLIT, 1>), st, a);
-  }
+  make_head_images<MODE>(a.zt, a.w, z_tail, w_sym, a.n_tail, n_labels, ws, st);
   MDG_CHECK_LAUNCH(fn);
-  return MDG_OK;
+  constexpr int tables = bincount_tables_bytes<SPLIT>;
+  if constexpr (kSingle16<MODE>) return sweep_launch<SPLIT, 2>(bilinear_bincount16_kernel<MODE, SPLIT>, a, n_labels, tables, st, fn);
+  else return sweep_launch<SPLIT, 1>(bilinear_bincount_kernel<MODE, SPLIT>, a, n_labels, tables, st, fn);
 }
 
 // Both entry points: the checks, the zeroing of `tables` count tables on the stream, the launch.  SPLIT: the sweep keeps two tables by
@@ -600,33 +518,23 @@ template <bool SPLIT>
 int bincount_run(const char* fn, int tables, const float* z_head, const float* z_tail, const float* w_sym, const float* edges, int64_t* counts,
                  int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_edges, int precision, int eligible, void* workspace,
                  size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride) {
-  MDG_CHECK_ARG(D_ == D, "%s: D must be %d (got %lld)", fn, D, (long long)D_);
+  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  if (rc != MDG_OK) return rc;
   MDG_CHECK_ARG(n_edges >= 1 && n_edges <= BINCOUNT_MAX_EDGES, "%s: n_edges must be in 1..%d (got %d)", fn, BINCOUNT_MAX_EDGES, n_edges);
-  MDG_CHECK_ARG(n_head >= 0 && n_tail >= 0 && n_labels >= 0, "%s: negative size", fn);
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 23), "%s: n_tail %lld does not fit the 32-bit workgroup counters (< 2^23)", fn, (long long)n_tail);
-  MDG_CHECK_ARG(n_labels <= 65535, "%s: n_labels %lld > 65535 per call", fn, (long long)n_labels);
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || eligible == MDG_TOPK_NOT_SELF || eligible == MDG_TOPK_LOWER, "%s: unknown eligible mode %d", fn,
-                eligible);
   MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail,
                 "%s: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)", fn, (long long)n_head, (long long)n_tail);
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16 || precision == MDG_PREC_F16,
-                "%s: unknown precision %d", fn, precision);
+  BincountKArgs<SPLIT> a{};
   if constexpr (SPLIT) {
-    MDG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, "%s: mask must be 4-byte aligned", fn);
-    MDG_CHECK_ARG(plane_stride == 0 || plane_stride >= mdg_pair_mask_plane_words(n_head, n_tail),
-                  "%s: plane_stride %lld is neither 0 (shared plane) nor >= the %lld words of a plane", fn, (long long)plane_stride,
-                  (long long)mdg_pair_mask_plane_words(n_head, n_tail));
+    const int mrc = sweep_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
+    if (mrc != MDG_OK) return mrc;
   }
   if (n_labels == 0) return MDG_OK;
   MDG_CHECK_ARG(edges && counts, "%s: null pointer", fn);
   const bool empty = n_head == 0 || n_tail == 0;          // no pair at all: every count is 0
-  MDG_CHECK_ARG(empty || (z_head && z_tail && w_sym), "%s: null pointer", fn);
-  MDG_CHECK_ARG(empty || (mdg_aligned16(z_head) && mdg_aligned16(z_tail) && mdg_aligned16(w_sym)),
-                "%s: z_head, z_tail and w_sym must be 16-byte aligned", fn);
-  const size_t need = empty ? 0 : mdg_bilinear_bincount_workspace_bytes(n_head, n_tail, n_labels, D_, n_edges, precision);
-  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-    mdg_set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", fn, need, workspace_bytes);
-    return MDG_EWORKSPACE;
+  if (!empty) {
+    const int orc = sweep_check_operands(fn, z_head, z_tail, w_sym, true, n_tail, n_labels, precision, workspace, workspace_bytes);
+    if (orc != MDG_OK) return orc;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(counts, 0, static_cast<size_t>(tables) * n_labels * (n_edges + 1) * sizeof(int64_t), st) != hipSuccess) {
@@ -635,13 +543,6 @@ int bincount_run(const char* fn, int tables, const float* z_head, const float* z
     return MDG_ELAUNCH;
   }
   if (empty) return MDG_OK;
-  BincountKArgs<SPLIT> a{};
-  if constexpr (SPLIT) {
-    a.mask.words = mask;
-    a.mask.plane_stride = plane_stride;
-    a.mask.ld = mdg_pair_mask_ld(n_tail);
-    a.mask.nrb = mdg_cdiv(n_head, 32);
-  }
   a.z_head = z_head;
   a.edges = edges;
   a.counts = reinterpret_cast<unsigned long long*>(counts);
@@ -665,9 +566,7 @@ extern "C" int mdg_bilinear_bincount_max_edges(void) { return BINCOUNT_MAX_EDGES
 
 extern "C" size_t mdg_bilinear_bincount_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_edges, int precision) {
   (void)n_head; (void)n_edges;
-  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
-  const size_t z = bincount_align256(static_cast<size_t>(n_tail) * D_ * 2), w = bincount_align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
-  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+  return head_images_workspace_bytes(n_tail, n_labels, D_, precision);
 }
 
 extern "C" int mdg_bilinear_bincount(const float* z_head, const float* z_tail, const float* w_sym, const float* edges, int64_t* counts,

@@ -38,6 +38,19 @@ void mdg_set_error(const char* fmt, ...);
     }                                                                            \
   } while (0)
 
+// Raises a kernel's limit of dynamic LDS to `bytes`, for launches above the default limit.  The attribute belongs to the
+// (kernel, device) pair, so it is set before every such launch, on whichever device is current and from whichever thread: a
+// process-wide "done" flag would leave every device but the first at the default.  Cost per call: DESIGN.md 4ae.
+static inline int mdg_raise_dynamic_lds(const void* kernel, int bytes, const char* what) {
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    mdg_set_error("%s: raising the dynamic LDS limit to %d bytes failed: %s", what, bytes, hipGetErrorString(e));
+    return MDG_ELAUNCH;
+  }
+  return MDG_OK;
+}
+
 static inline bool mdg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t mdg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

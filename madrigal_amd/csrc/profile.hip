@@ -251,60 +251,14 @@ __global__ __launch_bounds__(512, 1) void bilinear_profile_kernel(const ProfileA
   }
 }
 
-// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
-template <int MODE>
-__global__ void profile_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float4 v = reinterpret_cast<const float4*>(x)[i];
-  const float f[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (MODE == MDG_PREC_F16) {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-    f16x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
-    reinterpret_cast<f16x4*>(hi)[i] = o;
-  } else {
-    bf16x4 hv, lw;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      __bf16 a, b;
-      mdg_split_bf16(f[c], a, b);
-      hv[c] = a;
-      lw[c] = b;
-    }
-    reinterpret_cast<bf16x4*>(hi)[i] = hv;
-    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
-  }
-}
-
-inline size_t profile_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
 template <int MODE>
 int launch_profile(ProfileArgs& a, const float* z_tail, const float* w_sym, char* ws, hipStream_t st) {
   const char* const fn = "mdg_bilinear_profile";
-  if constexpr (MODE == MDG_PREC_F32) {
-    a.zt.f32 = z_tail;
-    a.w.f32 = w_sym;
-  } else {
-    const size_t zb = profile_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = profile_align256(static_cast<size_t>(a.n_labels) * D * D * 2);
-    const bool x3 = MODE == MDG_PREC_BF16X3;
-    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
-    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
-    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
-    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
-    const int64_t z4 = a.n_tail * D / 4, w4 = static_cast<int64_t>(a.n_labels) * D * D / 4;
-    hipLaunchKernelGGL(profile_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
-    hipLaunchKernelGGL(profile_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
-    MDG_CHECK_LAUNCH(fn);
-    a.zt.hi = zhi; a.zt.lo = zlo;
-    a.w.hi = whi; a.w.lo = wlo;
-  }
-  static bool attr_done = false;                  // the whole LDS of a CU: above the default limit of dynamic LDS
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_profile_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, PROFILE_LDS);
-    attr_done = true;
-  }
+  make_head_images<MODE>(a.zt, a.w, z_tail, w_sym, a.n_tail, a.n_labels, ws, st);
+  MDG_CHECK_LAUNCH(fn);
+  // the whole LDS of a CU: above the default limit of dynamic LDS
+  const int rc = mdg_raise_dynamic_lds(reinterpret_cast<const void*>(bilinear_profile_kernel<MODE>), PROFILE_LDS, fn);
+  if (rc != MDG_OK) return rc;
   const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_tail, BN)), static_cast<unsigned>(mdg_cdiv(a.n_head, PROFILE_BM)));
   hipLaunchKernelGGL((bilinear_profile_kernel<MODE>), grid, dim3(512), PROFILE_LDS, st, a);
   MDG_CHECK_LAUNCH(fn);
@@ -315,9 +269,7 @@ int launch_profile(ProfileArgs& a, const float* z_tail, const float* w_sym, char
 
 extern "C" size_t mdg_bilinear_profile_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision) {
   (void)n_head;
-  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
-  const size_t z = profile_align256(static_cast<size_t>(n_tail) * D_ * 2), w = profile_align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
-  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+  return head_images_workspace_bytes(n_tail, n_labels, D_, precision);
 }
 
 extern "C" int mdg_bilinear_profile(const float* z_head, const float* z_tail, const float* w_sym, const float* thr, const float* scale,

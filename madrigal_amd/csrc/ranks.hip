@@ -1985,14 +1985,15 @@ static int rank_normalize_impl(const float* scores, int64_t lds, float* out, int
   const uint32_t* only = nullptr;
   const MsdPlan pl = msd_plan(n_outcomes, N);
   if (pl.on) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msd_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msd_partition_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msd_bucket_kernel<MSD_NF>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msd_block_gather_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msd_block_gather_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      attr_done = true;
+    const struct { const void* kernel; int bytes; } big_lds[] = {
+        {reinterpret_cast<const void*>(msd_partition_kernel), 160 * 1024 - 256},
+        {reinterpret_cast<const void*>(msd_partition_pipe_kernel), 160 * 1024 - 256},
+        {reinterpret_cast<const void*>(msd_bucket_kernel<MSD_NF>), 150 * 1024},
+        {reinterpret_cast<const void*>(msd_block_gather_kernel<true>), 150 * 1024},
+        {reinterpret_cast<const void*>(msd_block_gather_kernel<false>), 150 * 1024}};
+    for (const auto& k : big_lds) {
+      const int rc = mdg_raise_dynamic_lds(k.kernel, k.bytes, "mdg_rank_normalize");
+      if (rc != MDG_OK) return rc;
     }
     uint32_t* flags = reinterpret_cast<uint32_t*>(ws);
     ws += a256(static_cast<size_t>(n_outcomes + 1) * 4);

@@ -3,11 +3,11 @@
 //   for every outcome l with its cut thr[l]: all eligible pairs (i, j) with S[l,i,j] >= thr[l], S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j],
 //   as CSR over the n_labels * n_head rows (l, i): row_ptr, then per hit its column j and its score.
 //
-// The set-valued product of the head ("every pair above a cut"): nothing of [L,N,N] is materialised.  The score arithmetic is
-// the sweep's own -- the kernels below are the row-statistics sweeps of bilinear.hip exactly as topk.hip and bincount.hip carry
-// them (same prologue, same staging, same MFMA sequence per accumulator element, same `eligible` handling and LOWER tile skipping),
-// with the epilogue replaced, so every compared and stored score equals the general sweep's bit for bit in f32 / bf16x3
-// (bf16 / f16: the 16x16x32 regrouping, <= 2e-6 of the scale, as for top-k).
+// The set-valued product of the head ("every pair above a cut"): nothing of [L,N,N] is materialised.  The kernels below are
+// the row-statistics sweeps of bilinear.hip as topk.hip and bincount.hip carry them (same prologue, same staging, same MFMA sequence
+// per accumulator element, same LOWER tile skipping) with the epilogue replaced, so every compared and stored score equals the general
+// sweep's bit for bit in f32 / bf16x3 (bf16 / f16: the 16x16x32 regrouping, <= 2e-6 of the scale, as for top-k).  The launch side
+// is shared with those two files (sweep_reduce.h).
 //
 // Two passes over the same sweep (FILL = false / true), because the size of the result is not known beforehand:
 //   count: row_counts[l,i] = #{eligible j : S[l,i,j] >= thr[l]}.  The caller's exclusive prefix sum over the flattened counts is
@@ -40,9 +40,8 @@
 // reason a NaN score is never selected.
 // MASKED instantiations (mdg_bilinear_select_*_masked): a known-pair exclusion bitmap (pairmask.hip) on top of
 // `eligible`; a set bit makes its element NaN like an ineligible one, in both passes alike, so order, bounded writes and
-// determinism are those described above.  The words of a tile reach LDS by one or two more LDS-DMAs in the tile's group
-// (pairmask.h); the MASKED = false kernels are what they were.
-#include "pairmask.h"
+// determinism are those described above.
+#include "sweep_reduce.h"
 
 namespace {
 
@@ -63,11 +62,6 @@ struct SelectArgs {
 template <bool MASKED> struct SelectKArgs : SelectArgs {};
 template <> struct SelectKArgs<true> : SelectArgs { PairMask mask; };
 
-// LDS of a MASKED sweep behind the three stage buffers: per stage buffer and wave, NMW slots of 256 bytes -- the mask words of the
-// wave's row block(s) for the 64 columns of that buffer's tile (pairmask.h; the same arrangement as topk.hip).
-template <int NMW> constexpr int select_mask_stage = 8 * NMW * PAIRMASK_SLOT;
-template <bool MASKED, int NMW> constexpr int select_lds_bytes = 3 * STAGE_BYTES + (MASKED ? 3 * select_mask_stage<NMW> : 0);
-
 // Eligibility of the element in row wrow0 + lr, column tcol0 + lc of a tile (0 <= lr, lc < 64) from the tile's 32-bit distances
 // (wave-uniform, select_clamp-ed): dcr = tcol0 - wrow0, nr = n_head - wrow0, nc = n_tail - tcol0.  The same test as top-k's and
 // bincount's on the 64-bit indices (col - row keeps its sign and its zero through the clamp); a lane's lr and lc differ from
@@ -79,15 +73,6 @@ __device__ __forceinline__ bool select_eligible(int mode, int lr, int lc, int dc
   const int d = dcr + lc - lr;                                                          // column - row
   const bool pair = mode == MDG_TOPK_NOT_SELF ? d != 0 : d < 0;                         // (bitwise: selects, no branches)
   return (lr < nr) & (lc < nc) & ((mode == MDG_TOPK_ALL) | pair);
-}
-
-// column tiles a workgroup with head rows [row0, row0 + BM) has to visit: LOWER needs columns j <= last row - 1 only
-__device__ __forceinline__ int select_tiles(const SelectArgs& p, int64_t row0, int BM) {
-  const int nst = static_cast<int>((p.n_tail + BN - 1) / BN);
-  if (p.eligible != MDG_TOPK_LOWER) return nst;
-  const int64_t last = (row0 + BM < p.n_head ? row0 + BM : p.n_head) - 1;      // columns [0, last) are eligible for some row
-  const int need = static_cast<int>((last + BN - 1) / BN);
-  return need < 1 ? 1 : (need < nst ? need : nst);
 }
 
 // Hit path of one accumulator register.  Must be called in wave-uniform control flow.  G lanes share the row whose row_ptr entry is
@@ -112,6 +97,9 @@ __device__ __forceinline__ void select_take(const SelectArgs& p, unsigned& run, 
   run += __builtin_popcount(mine);
 }
 
+// The two kernels below carry the sweep itself -- prologue, three-buffer LDS-DMA ring with its hand-counted waits, mask-word DMAs --
+// as topk.hip, select.hip and bincount.hip each do: sharing that text between them was tried and measured 0.2 - 2.9 % slower in some
+// instantiations whichever way it was spelled, so a change to the ring is made in all three files.
 // ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the selecting epilogue ---------------------------------------
 // MASKED: an element is eligible when the mode allows it AND its bit of the exclusion mask is clear (it becomes NaN like every
 // ineligible element).  The 64 words [row block of the wave][columns of the tile] ride with the tile: one more LDS-DMA per wave and
@@ -170,7 +158,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectKAr
   }
 
   // ---------------- sweep: three stage buffers, prefetch distance two, ascending column tiles -------------
-  const int nst = select_tiles(p, row0, BM);
+  const int nst = sweep_tiles(p.eligible, row0, BM, p.n_head, p.n_tail);
   const int64_t wrow0 = row0 + wave * 32;        // this wave's rows: wrow0 .. wrow0 + 31
   const int mode = p.eligible;
   unsigned run[16];                              // hits so far of row acc_row(v, h)
@@ -179,10 +167,10 @@ __global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectKAr
   for (int v = 0; v < 16; ++v) run[v] = 0u;
   constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
   static_assert(NDMA == 4, "vmcnt immediate below");
-  // MASKED: the wave's mask slot of stage buffer b is mslot + b * select_mask_stage<1>; every group of DMAs below (tile + words) is
+  // MASKED: the wave's mask slot of stage buffer b is mslot + b * sweep_mask_stage<1>; every group of DMAs below (tile + words) is
   // issued together, so "the last group in flight" is 5 instructions instead of 4 and nothing else about the chain changes.  (The
   // fill pass's stores and row_ptr reads are issued after a group and only make a wait stricter, as before.)
-  constexpr int MSTAGE = select_mask_stage<1>;
+  constexpr int MSTAGE = sweep_mask_stage<1>;
   const char* const mslot = smem + 3 * STAGE_BYTES + wave * PAIRMASK_SLOT;
   const unsigned* mplane = nullptr;
   if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
@@ -257,16 +245,6 @@ __global__ __launch_bounds__(512, 1) void bilinear_select_kernel(const SelectKAr
 }
 
 // ---- bf16 / f16: bilinear_rowstats16_kernel (v_mfma_f32_16x16x32, 64 rows per wave) with the selecting epilogue -----------------
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-template <int MODE>
-__device__ __forceinline__ f32x4v select_mma16x16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  if constexpr (MODE == MDG_PREC_F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // MASKED: as above; the wave's 64 rows are two row blocks of the mask, so two mask DMAs per tile group (2 + 2 = 4 in flight) and
 // two slots: lane (c16, g4) reads word 16 ct + c16 of each for sub-tile ct; row 16 rt + 4 g4 + i is bit 16 (rt & 1) + 4 g4 + i
 // of the word of row block rt >> 1.
@@ -330,14 +308,14 @@ __global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectK
     __syncthreads();
   }
   // ---- sweep ----
-  const int nst = select_tiles(p, row0, BM);
+  const int nst = sweep_tiles(p.eligible, row0, BM, p.n_head, p.n_tail);
   const int64_t wrow0 = row0 + wave * 64;            // this wave's rows: wrow0 .. wrow0 + 63
   const int mode = p.eligible;
   unsigned run[16];                                  // hits so far of row 16 rt + 4 g4 + i: counter 4 rt + i
   const long long* const rp = p.row_ptr + (l * p.n_head + wrow0 + 4 * g4);     // row 16 rt + 4 g4 + i: rp[16 * rt + i]
 #pragma unroll
   for (int q = 0; q < 16; ++q) run[q] = 0u;
-  constexpr int MSTAGE = select_mask_stage<2>;
+  constexpr int MSTAGE = sweep_mask_stage<2>;
   const char* const mslot = smem + 3 * STAGE_BYTES + wave * 2 * PAIRMASK_SLOT;
   const unsigned* mplane = nullptr;
   if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
@@ -382,7 +360,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectK
       for (int ks = 0; ks < 4; ++ks) {
         const bf16x8 b = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(16 * ct + c16, 4 * ks + g4));
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = select_mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
       }
       const int col = static_cast<int>(tcol0) + 16 * ct + c16;
       if (!plain) {
@@ -428,73 +406,12 @@ __global__ __launch_bounds__(512, 1) void bilinear_select16_kernel(const SelectK
   }
 }
 
-// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
-template <int MODE>
-__global__ void select_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float4 v = reinterpret_cast<const float4*>(x)[i];
-  const float f[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (MODE == MDG_PREC_F16) {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-    f16x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
-    reinterpret_cast<f16x4*>(hi)[i] = o;
-  } else {
-    bf16x4 hv, lw;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      __bf16 a, b;
-      mdg_split_bf16(f[c], a, b);
-      hv[c] = a;
-      lw[c] = b;
-    }
-    reinterpret_cast<bf16x4*>(hi)[i] = hv;
-    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
-  }
-}
-
-inline size_t select_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
 template <int MODE, bool FILL, bool MASKED>
 int launch_select(SelectKArgs<MASKED>& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st, const char* fn) {
-  if constexpr (MODE == MDG_PREC_F32) {
-    a.zt.f32 = z_tail;
-    a.w.f32 = w_sym;
-  } else {
-    const size_t zb = select_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = select_align256(static_cast<size_t>(n_labels) * D * D * 2);
-    const bool x3 = MODE == MDG_PREC_BF16X3;
-    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
-    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
-    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
-    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
-    const int64_t z4 = a.n_tail * D / 4, w4 = n_labels * D * D / 4;
-    hipLaunchKernelGGL(select_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
-    hipLaunchKernelGGL(select_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
-    MDG_CHECK_LAUNCH(fn);
-    a.zt.hi = zhi; a.zt.lo = zlo;
-    a.w.hi = whi; a.w.lo = wlo;
-  }
-  if constexpr (MASKED) {                         // more dynamic LDS than the unmasked sweeps use: raise the kernel's limit once
-    static bool attr_done = false;
-    if (!attr_done) {
-      if constexpr (kSingle16<MODE>)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_select16_kernel<MODE, FILL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, select_lds_bytes<true, 2>);
-      else
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_select_kernel<MODE, FILL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, select_lds_bytes<true, 1>);
-      attr_done = true;
-    }
-  }
-  if constexpr (kSingle16<MODE>) {
-    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_select16_kernel<MODE, FILL, MASKED>), grid, dim3(512), (select_lds_bytes<MASKED, 2>), st, a);
-  } else {
-    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_select_kernel<MODE, FILL, MASKED>), grid, dim3(512), (select_lds_bytes<MASKED, 1>), st, a);
-  }
+  make_head_images<MODE>(a.zt, a.w, z_tail, w_sym, a.n_tail, n_labels, ws, st);
   MDG_CHECK_LAUNCH(fn);
-  return MDG_OK;
+  if constexpr (kSingle16<MODE>) return sweep_launch<MASKED, 2>(bilinear_select16_kernel<MODE, FILL, MASKED>, a, n_labels, 0, st, fn);
+  else return sweep_launch<MASKED, 1>(bilinear_select_kernel<MODE, FILL, MASKED>, a, n_labels, 0, st, fn);
 }
 
 // The checks both entry points share; `outputs`: none of the pass's own pointers is null.  Returns MDG_OK with *launch = false
@@ -503,26 +420,16 @@ int select_check(const char* fn, const float* z_head, const float* z_tail, const
                  int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible, void* workspace, size_t workspace_bytes,
                  bool* launch) {
   *launch = false;
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || eligible == MDG_TOPK_NOT_SELF || eligible == MDG_TOPK_LOWER, "%s: unknown eligible mode %d", fn,
-                eligible);
-  MDG_CHECK_ARG(n_head >= 0 && n_tail >= 0 && n_labels >= 0, "%s: negative size", fn);
+  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  if (rc != MDG_OK) return rc;
   MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail,
                 "%s: eligible NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)", fn, (long long)n_head,
                 (long long)n_tail);
-  MDG_CHECK_ARG(D_ == D, "%s: D must be %d (got %lld)", fn, D, (long long)D_);
-  MDG_CHECK_ARG(n_labels <= 65535, "%s: n_labels %lld > 65535 per call", fn, (long long)n_labels);
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 31) - BN, "%s: n_tail %lld does not fit the int32 column indices", fn, (long long)n_tail);
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16 || precision == MDG_PREC_F16,
-                "%s: unknown precision %d", fn, precision);
   if (n_head == 0 || n_labels == 0) return MDG_OK;
   MDG_CHECK_ARG(n_tail >= 1, "%s: n_tail must be at least 1", fn);
-  MDG_CHECK_ARG(z_head && z_tail && w_sym && thr && outputs, "%s: null pointer", fn);
-  MDG_CHECK_ARG(mdg_aligned16(z_head) && mdg_aligned16(z_tail) && mdg_aligned16(w_sym), "%s: z_head, z_tail and w_sym must be 16-byte aligned", fn);
-  const size_t need = mdg_bilinear_select_workspace_bytes(n_head, n_tail, n_labels, D_, precision);
-  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-    mdg_set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", fn, need, workspace_bytes);
-    return MDG_EWORKSPACE;
-  }
+  const int orc = sweep_check_operands(fn, z_head, z_tail, w_sym, thr && outputs, n_tail, n_labels, precision, workspace, workspace_bytes);
+  if (orc != MDG_OK) return orc;
   *launch = true;
   return MDG_OK;
 }
@@ -544,25 +451,10 @@ int select_dispatch(SelectKArgs<MASKED>& a, const float* z_tail, const float* w_
 
 extern "C" size_t mdg_bilinear_select_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision) {
   (void)n_head;
-  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
-  const size_t z = select_align256(static_cast<size_t>(n_tail) * D_ * 2), w = select_align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
-  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+  return head_images_workspace_bytes(n_tail, n_labels, D_, precision);
 }
 
 namespace {
-
-// The mask arguments of the *_masked entry points, checked and put into the kernel argument.
-int select_mask_args(const char* fn, PairMask& m, const uint32_t* mask, int64_t plane_stride, int64_t n_head, int64_t n_tail) {
-  MDG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, "%s: mask must be 4-byte aligned", fn);
-  MDG_CHECK_ARG(plane_stride == 0 || plane_stride >= mdg_pair_mask_plane_words(n_head, n_tail),
-                "%s: plane_stride %lld is neither 0 (shared plane) nor >= the %lld words of a plane", fn, (long long)plane_stride,
-                (long long)mdg_pair_mask_plane_words(n_head, n_tail));
-  m.words = mask;
-  m.plane_stride = plane_stride;
-  m.ld = mdg_pair_mask_ld(n_tail);
-  m.nrb = mdg_cdiv(n_head, 32);
-  return MDG_OK;
-}
 
 template <bool MASKED>
 int select_count_run(const char* fn, const float* z_head, const float* z_tail, const float* w_sym, const float* thr, int32_t* row_counts,
@@ -574,7 +466,7 @@ int select_count_run(const char* fn, const float* z_head, const float* z_tail, c
   if (rc != MDG_OK || !launch) return rc;
   SelectKArgs<MASKED> a{};
   if constexpr (MASKED) {
-    const int mrc = select_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
+    const int mrc = sweep_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
     if (mrc != MDG_OK) return mrc;
   }
   a.z_head = z_head;
@@ -597,7 +489,7 @@ int select_fill_run(const char* fn, const float* z_head, const float* z_tail, co
   if (rc != MDG_OK || !launch) return rc;
   SelectKArgs<MASKED> a{};
   if constexpr (MASKED) {
-    const int mrc = select_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
+    const int mrc = sweep_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
     if (mrc != MDG_OK) return mrc;
   }
   a.z_head = z_head;

@@ -217,35 +217,6 @@ __global__ __launch_bounds__(512, 2) void bilinear_store16_kernel(const Store16A
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
-template <int MODE>
-__global__ void store16_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float4 v = reinterpret_cast<const float4*>(x)[i];
-  const float f[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (MODE == MDG_PREC_F16) {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-    f16x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
-    reinterpret_cast<f16x4*>(hi)[i] = o;
-  } else {
-    bf16x4 hv, lw;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      __bf16 a, b;
-      mdg_split_bf16(f[c], a, b);
-      hv[c] = a;
-      lw[c] = b;
-    }
-    reinterpret_cast<bf16x4*>(hi)[i] = hv;
-    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
-  }
-}
-
-inline size_t store16_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
 template <int MODE, int EPI>
 int launch_store16_ty(const Store16Args& a, int64_t n_labels, int score_type, hipStream_t st) {
   const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
@@ -258,23 +229,8 @@ int launch_store16_ty(const Store16Args& a, int64_t n_labels, int score_type, hi
 template <int MODE>
 int launch_store16(Store16Args& a, const float* z_tail, const float* w_sym, int64_t n_labels, int epilogue, int score_type, char* ws,
                    hipStream_t st) {
-  if constexpr (MODE == MDG_PREC_F32) {
-    a.zt.f32 = z_tail;
-    a.w.f32 = w_sym;
-  } else {
-    const size_t zb = store16_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = store16_align256(static_cast<size_t>(n_labels) * D * D * 2);
-    const bool x3 = MODE == MDG_PREC_BF16X3;
-    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
-    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
-    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
-    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
-    const int64_t z4 = a.n_tail * D / 4, w4 = n_labels * D * D / 4;
-    hipLaunchKernelGGL(store16_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
-    hipLaunchKernelGGL(store16_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
-    MDG_CHECK_LAUNCH("mdg_bilinear_allpairs16_ld(images)");
-    a.zt.hi = zhi; a.zt.lo = zlo;
-    a.w.hi = whi; a.w.lo = wlo;
-  }
+  make_head_images<MODE>(a.zt, a.w, z_tail, w_sym, a.n_tail, n_labels, ws, st);
+  MDG_CHECK_LAUNCH("mdg_bilinear_allpairs16_ld(images)");
   return epilogue == MDG_EPI_STORE ? launch_store16_ty<MODE, MDG_EPI_STORE>(a, n_labels, score_type, st)
                                    : launch_store16_ty<MODE, MDG_EPI_STORE_SIGMOID>(a, n_labels, score_type, st);
 }

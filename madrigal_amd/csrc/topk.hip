@@ -3,10 +3,10 @@
 //   for every outcome l and head row i: the k largest S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j] over the ELIGIBLE tail
 //   columns j, with their column indices, ordered by (score descending, column ascending).
 //
-// The fourth, reducing product of the head: nothing of [L,N,N] is materialised.  The score arithmetic is the sweep's own --
-// the two kernels below are the row-statistics sweeps of bilinear.hip (same prologue, same staging, same MFMA sequence per
-// accumulator element: `bilinear_allpairs_kernel<MODE, ROWSTATS, 8>` for f32 / bf16x3, `bilinear_rowstats16_kernel` for the
-// single-product 16-bit modes) with the sum / max epilogue replaced, so every score equals the general sweep's bit for bit.
+// The fourth, reducing product of the head: nothing of [L,N,N] is materialised.  The score arithmetic is the sweep's own -- the two
+// kernels below are the row-statistics sweeps of bilinear.hip (same prologue, same staging, same MFMA sequence per accumulator
+// element) with the sum / max epilogue replaced, so every score equals the general sweep's bit for bit.  The launch side is shared
+// with select.hip and bincount.hip (sweep_reduce.h).
 //
 // Where the lists live: in registers.  The accumulator layouts give every head row to ONE wave, G lanes per row (G = 32 on
 // the 32x32 MFMA, 16 on 16x16x32), each lane holding one column.  Those same G lanes hold the row's sorted list: entry e sits
@@ -24,13 +24,11 @@
 // full key (score, then column).  No atomics, no memory traffic besides the final k stores per row: bit-reproducible.
 // NaN scores never pass `x > thr` and are never kept (scores are finite by contract).
 //
-// LDS: the three stage buffers of the row-statistics sweeps (96 KB, one workgroup per CU -- as ROWSTATS); registers: the
-// workgroup may use 256 per lane (launch bound 1), see DESIGN.md 4m for the measured budget of every instantiation.
+// Registers: the workgroup may use 256 per lane (launch bound 1), see DESIGN.md 4m for the measured budget of every instantiation.
 //
 // MASKED instantiations (mdg_bilinear_topk_masked): a known-pair exclusion bitmap (pairmask.hip) on top of
-// `eligible`; a set bit makes its element -inf like an ineligible one, so everything above holds for what remains.  The words of a
-// tile reach LDS by one or two more LDS-DMAs in the tile's group (pairmask.h); the MASKED = false kernels are what they were.
-#include "pairmask.h"
+// `eligible`; a set bit makes its element -inf like an ineligible one, so everything above holds for what remains.
+#include "sweep_reduce.h"
 #include "topk_list.h"         // TOPK_MAX_K, topk_insert: shared with knn.hip
 
 namespace {
@@ -50,24 +48,13 @@ struct TopkArgs {
 template <bool MASKED> struct TopkKArgs : TopkArgs {};
 template <> struct TopkKArgs<true> : TopkArgs { PairMask mask; };
 
-// LDS of a MASKED sweep behind the three stage buffers: per stage buffer and wave, NMW slots of 256 bytes -- the mask words of the
-// wave's row block(s) for the 64 columns of that buffer's tile (pairmask.h).
-template <int NMW> constexpr int topk_mask_stage = 8 * NMW * PAIRMASK_SLOT;
-template <bool MASKED, int NMW> constexpr int topk_lds_bytes = 3 * STAGE_BYTES + (MASKED ? 3 * topk_mask_stage<NMW> : 0);
-
 __device__ __forceinline__ bool topk_eligible(int mode, int64_t row, int64_t col, int64_t n_tail) {
   return col < n_tail && (mode == MDG_TOPK_ALL || (mode == MDG_TOPK_NOT_SELF ? col != row : col < row));
 }
 
-// column tiles a workgroup with head rows [row0, row0 + BM) has to visit: LOWER needs columns j <= last row - 1 only
-__device__ __forceinline__ int topk_tiles(const TopkArgs& p, int64_t row0, int BM) {
-  const int nst = static_cast<int>((p.n_tail + BN - 1) / BN);
-  if (p.eligible != MDG_TOPK_LOWER) return nst;
-  const int64_t last = (row0 + BM < p.n_head ? row0 + BM : p.n_head) - 1;      // columns [0, last) are eligible for some row
-  const int need = static_cast<int>((last + BN - 1) / BN);
-  return need < 1 ? 1 : (need < nst ? need : nst);
-}
-
+// The two kernels below carry the sweep itself -- prologue, three-buffer LDS-DMA ring with its hand-counted waits, mask-word DMAs --
+// as topk.hip, select.hip and bincount.hip each do: sharing that text between them was tried and measured 0.2 - 2.9 % slower in some
+// instantiations whichever way it was spelled, so a change to the ring is made in all three files.
 // ---- f32 / bf16x3: bilinear_allpairs_kernel<MODE, ROWSTATS, 8> with the list epilogue ---------------------------------------
 // MASKED: an element is eligible when the mode allows it AND its bit of the exclusion mask is clear.  The 64 words
 // [row block of the wave][columns of the tile] ride with the tile: one more LDS-DMA per wave and tile group, into a slot of the
@@ -125,7 +112,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkKArgs<M
   }
 
   // ---------------- sweep: three stage buffers, prefetch distance two, ascending column tiles -------------
-  const int nst = topk_tiles(p, row0, BM);
+  const int nst = sweep_tiles(p.eligible, row0, BM, p.n_head, p.n_tail);
   const int64_t wrow0 = row0 + wave * 32;        // this wave's rows: wrow0 .. wrow0 + 31
   const int mode = p.eligible, k = p.k;
   float lv[16][1], thr[16];
@@ -134,9 +121,9 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkKArgs<M
   for (int v = 0; v < 16; ++v) { lv[v][0] = -INFINITY; li[v][0] = -1; thr[v] = -INFINITY; }
   constexpr int NDMA = 32 / NW;                  // LDS-DMA instructions per wave and tile
   static_assert(NDMA == 4, "vmcnt immediate below");
-  // MASKED: the wave's mask slot of stage buffer b is mslot + b * topk_mask_stage<1>; every group of DMAs below (tile + words)
+  // MASKED: the wave's mask slot of stage buffer b is mslot + b * sweep_mask_stage<1>; every group of DMAs below (tile + words)
   // is issued together, so "the last group in flight" is 5 instructions instead of 4 and nothing else about the chain changes.
-  constexpr int MSTAGE = topk_mask_stage<1>;
+  constexpr int MSTAGE = sweep_mask_stage<1>;
   const char* const mslot = smem + 3 * STAGE_BYTES + wave * PAIRMASK_SLOT;
   const unsigned* mplane = nullptr;
   if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
@@ -211,16 +198,6 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk_kernel(const TopkKArgs<M
 }
 
 // ---- bf16 / f16: bilinear_rowstats16_kernel (v_mfma_f32_16x16x32, 64 rows per wave) with the list epilogue -----------------
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-template <int MODE>
-__device__ __forceinline__ f32x4v topk_mma16x16(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  if constexpr (MODE == MDG_PREC_F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // MASKED: as above; the wave's 64 rows are two row blocks of the mask, so two mask DMAs per tile group (2 + 2 = 4 in flight) and
 // two slots: lane (c16, g4) reads word 16 ct + c16 of each for sub-tile ct; row 16 rt + 4 g4 + i is bit 16 (rt & 1) + 4 g4 + i
 // of the word of row block rt >> 1.
@@ -283,14 +260,14 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkKArgs
     __syncthreads();
   }
   // ---- sweep ----
-  const int nst = topk_tiles(p, row0, BM);
+  const int nst = sweep_tiles(p.eligible, row0, BM, p.n_head, p.n_tail);
   const int64_t wrow0 = row0 + wave * 64;            // this wave's rows: wrow0 .. wrow0 + 63
   const int mode = p.eligible, k = p.k;
   float lv[16][2], thr[16];                          // row 16 rt + 4 g4 + i is list 4 rt + i
   int li[16][2];
 #pragma unroll
   for (int q = 0; q < 16; ++q) { lv[q][0] = lv[q][1] = -INFINITY; li[q][0] = li[q][1] = -1; thr[q] = -INFINITY; }
-  constexpr int MSTAGE = topk_mask_stage<2>;
+  constexpr int MSTAGE = sweep_mask_stage<2>;
   const char* const mslot = smem + 3 * STAGE_BYTES + wave * 2 * PAIRMASK_SLOT;
   const unsigned* mplane = nullptr;
   if constexpr (MASKED) mplane = p.mask.words + l * p.mask.plane_stride;            // workgroup-uniform
@@ -335,7 +312,7 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkKArgs
       for (int ks = 0; ks < 4; ++ks) {
         const bf16x8 b = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(16 * ct + c16, 4 * ks + g4));
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt] = topk_mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
+        for (int rt = 0; rt < 4; ++rt) acc[rt] = mma16x16<MODE>(A16[rt][ks], b, acc[rt]);
       }
       const int col = static_cast<int>(tcol0) + 16 * ct + c16;
       if (!plain) {
@@ -388,73 +365,12 @@ __global__ __launch_bounds__(512, 1) void bilinear_topk16_kernel(const TopkKArgs
     }
 }
 
-// ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
-template <int MODE>
-__global__ void topk_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float4 v = reinterpret_cast<const float4*>(x)[i];
-  const float f[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (MODE == MDG_PREC_F16) {
-    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-    f16x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = static_cast<_Float16>(f[c]);
-    reinterpret_cast<f16x4*>(hi)[i] = o;
-  } else {
-    bf16x4 hv, lw;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      __bf16 a, b;
-      mdg_split_bf16(f[c], a, b);
-      hv[c] = a;
-      lw[c] = b;
-    }
-    reinterpret_cast<bf16x4*>(hi)[i] = hv;
-    if constexpr (MODE == MDG_PREC_BF16X3) reinterpret_cast<bf16x4*>(lo)[i] = lw;
-  }
-}
-
-inline size_t topk_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
 template <int MODE, bool MASKED>
 int launch_topk(TopkKArgs<MASKED>& a, const float* z_tail, const float* w_sym, int64_t n_labels, char* ws, hipStream_t st) {
-  if constexpr (MODE == MDG_PREC_F32) {
-    a.zt.f32 = z_tail;
-    a.w.f32 = w_sym;
-  } else {
-    const size_t zb = topk_align256(static_cast<size_t>(a.n_tail) * D * 2), wb = topk_align256(static_cast<size_t>(n_labels) * D * D * 2);
-    const bool x3 = MODE == MDG_PREC_BF16X3;
-    __bf16* zhi = reinterpret_cast<__bf16*>(ws);
-    __bf16* whi = reinterpret_cast<__bf16*>(ws + zb);
-    __bf16* zlo = x3 ? reinterpret_cast<__bf16*>(ws + zb + wb) : nullptr;
-    __bf16* wlo = x3 ? reinterpret_cast<__bf16*>(ws + 2 * zb + wb) : nullptr;
-    const int64_t z4 = a.n_tail * D / 4, w4 = n_labels * D * D / 4;
-    hipLaunchKernelGGL(topk_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(z4, 256))), dim3(256), 0, st, z_tail, zhi, zlo, z4);
-    hipLaunchKernelGGL(topk_images_kernel<MODE>, dim3(static_cast<unsigned>(mdg_cdiv(w4, 256))), dim3(256), 0, st, w_sym, whi, wlo, w4);
-    MDG_CHECK_LAUNCH("mdg_bilinear_topk(operand images)");
-    a.zt.hi = zhi; a.zt.lo = zlo;
-    a.w.hi = whi; a.w.lo = wlo;
-  }
-  if constexpr (MASKED) {                         // more dynamic LDS than the unmasked sweeps use: raise the kernel's limit once
-    static bool attr_done = false;
-    if (!attr_done) {
-      if constexpr (kSingle16<MODE>)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_topk16_kernel<MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, topk_lds_bytes<true, 2>);
-      else
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bilinear_topk_kernel<MODE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, topk_lds_bytes<true, 1>);
-      attr_done = true;
-    }
-  }
-  if constexpr (kSingle16<MODE>) {
-    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 512)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_topk16_kernel<MODE, MASKED>), grid, dim3(512), (topk_lds_bytes<MASKED, 2>), st, a);
-  } else {
-    const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 256)), static_cast<unsigned>(n_labels));
-    hipLaunchKernelGGL((bilinear_topk_kernel<MODE, MASKED>), grid, dim3(512), (topk_lds_bytes<MASKED, 1>), st, a);
-  }
-  MDG_CHECK_LAUNCH("mdg_bilinear_topk");
-  return MDG_OK;
+  make_head_images<MODE>(a.zt, a.w, z_tail, w_sym, a.n_tail, n_labels, ws, st);
+  MDG_CHECK_LAUNCH("mdg_bilinear_topk(operand images)");
+  if constexpr (kSingle16<MODE>) return sweep_launch<MASKED, 2>(bilinear_topk16_kernel<MODE, MASKED>, a, n_labels, 0, st, "mdg_bilinear_topk");
+  else return sweep_launch<MASKED, 1>(bilinear_topk_kernel<MODE, MASKED>, a, n_labels, 0, st, "mdg_bilinear_topk");
 }
 
 }  // namespace
@@ -463,9 +379,7 @@ extern "C" int mdg_bilinear_topk_max_k(void) { return TOPK_MAX_K; }
 
 extern "C" size_t mdg_bilinear_topk_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int k) {
   (void)n_head; (void)k;
-  if (precision == MDG_PREC_F32 || n_tail <= 0 || n_labels <= 0 || D_ <= 0) return 0;
-  const size_t z = topk_align256(static_cast<size_t>(n_tail) * D_ * 2), w = topk_align256(static_cast<size_t>(n_labels) * D_ * D_ * 2);
-  return precision == MDG_PREC_BF16X3 ? 2 * (z + w) : (z + w);
+  return head_images_workspace_bytes(n_tail, n_labels, D_, precision);
 }
 
 namespace {
@@ -475,35 +389,23 @@ template <bool MASKED>
 int topk_run(const float* z_head, const float* z_tail, const float* w_sym, float* vals, int32_t* idx, int64_t n_head, int64_t n_tail,
              int64_t n_labels, int64_t D_, int precision, int k, int eligible, void* workspace, size_t workspace_bytes, void* stream,
              const uint32_t* mask, int64_t plane_stride) {
-  MDG_CHECK_ARG(D_ == D, "mdg_bilinear_topk: D must be %d (got %lld)", D, (long long)D_);
+  const char* const fn = "mdg_bilinear_topk";
+  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  if (rc != MDG_OK) return rc;
   MDG_CHECK_ARG(k >= 1 && k <= TOPK_MAX_K, "mdg_bilinear_topk: k must be in 1..%d (got %d)", TOPK_MAX_K, k);
-  MDG_CHECK_ARG(n_head >= 0 && n_tail >= 0 && n_labels >= 0, "mdg_bilinear_topk: negative size");
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 31) - BN, "mdg_bilinear_topk: n_tail %lld does not fit the int32 column indices", (long long)n_tail);
-  MDG_CHECK_ARG(n_labels <= 65535, "mdg_bilinear_topk: n_labels %lld > 65535 per call", (long long)n_labels);
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || eligible == MDG_TOPK_NOT_SELF || eligible == MDG_TOPK_LOWER,
-                "mdg_bilinear_topk: unknown eligible mode %d", eligible);
   MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail,
                 "mdg_bilinear_topk: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)", (long long)n_head, (long long)n_tail);
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16 || precision == MDG_PREC_F16,
-                "mdg_bilinear_topk: unknown precision %d", precision);
   if (n_head == 0 || n_labels == 0) return MDG_OK;
   MDG_CHECK_ARG(n_tail >= 1, "mdg_bilinear_topk: n_tail must be at least 1");
-  MDG_CHECK_ARG(z_head && z_tail && w_sym && vals && idx, "mdg_bilinear_topk: null pointer");
-  MDG_CHECK_ARG(mdg_aligned16(z_head) && mdg_aligned16(z_tail) && mdg_aligned16(w_sym),
-                "mdg_bilinear_topk: z_head, z_tail and w_sym must be 16-byte aligned");
-  if constexpr (MASKED) {
-    MDG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, "mdg_bilinear_topk_masked: mask must be 4-byte aligned");
-    MDG_CHECK_ARG(plane_stride == 0 || plane_stride >= mdg_pair_mask_plane_words(n_head, n_tail),
-                  "mdg_bilinear_topk_masked: plane_stride %lld is neither 0 (shared plane) nor >= the %lld words of a plane", (long long)plane_stride,
-                  (long long)mdg_pair_mask_plane_words(n_head, n_tail));
-  }
-  const size_t need = mdg_bilinear_topk_workspace_bytes(n_head, n_tail, n_labels, D_, precision, k);
-  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-    mdg_set_error("mdg_bilinear_topk: workspace of %zu bytes (16-byte aligned) required, got %zu", need, workspace_bytes);
-    return MDG_EWORKSPACE;
-  }
+  const int orc = sweep_check_operands(fn, z_head, z_tail, w_sym, vals && idx, n_tail, n_labels, precision, workspace, workspace_bytes);
+  if (orc != MDG_OK) return orc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TopkKArgs<MASKED> a{};
+  if constexpr (MASKED) {
+    const int mrc = sweep_mask_args("mdg_bilinear_topk_masked", a.mask, mask, plane_stride, n_head, n_tail);
+    if (mrc != MDG_OK) return mrc;
+  }
   a.z_head = z_head;
   a.vals = vals;
   a.idx = idx;
@@ -512,12 +414,6 @@ int topk_run(const float* z_head, const float* z_tail, const float* w_sym, float
   a.eligible = eligible;
   a.zt.nrows = n_tail;
   a.w.nrows = D;
-  if constexpr (MASKED) {
-    a.mask.words = mask;
-    a.mask.plane_stride = plane_stride;
-    a.mask.ld = mdg_pair_mask_ld(n_tail);
-    a.mask.nrb = mdg_cdiv(n_head, 32);
-  }
   char* ws = static_cast<char*>(workspace);
   switch (precision) {
     case MDG_PREC_F32: return launch_topk<MDG_PREC_F32, MASKED>(a, z_tail, w_sym, n_labels, ws, st);
