@@ -148,6 +148,31 @@ int mdg_bilinear_ensemble_sigmoid(const float* const* z_head_host, const float* 
                                   int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Per-row top-k of the checkpoint ensemble (ABI 25): for every outcome l and head row i the k largest
+ *   P[l,i,j] = mean_m sigmoid(z_head_m[i]^T W_sym_m[l] z_tail_m[j])
+ * over the ELIGIBLE tail columns j, and those columns, without materialising [L,N,N].  The probability is the one
+ * get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) average over the
+ * checkpoints; the lists are what the reference reads off that stored tensor (notebooks/quick_predictions.ipynb cell 8) and, in
+ * LOWER mode, the candidates of the pairs notebooks/normalize_scores.py:39-46 ranks.  The mean of sigmoids is not monotone in any
+ * one model's logit, so the single-model lists of mdg_bilinear_topk cannot be combined into these.
+ *   Operands as mdg_bilinear_ensemble_sigmoid (HOST arrays of n_models = 1..8 device pointers, 16-byte aligned, D == 128);
+ *   precision MDG_PREC_F32 or MDG_PREC_BF16X3.  P is bit for bit what mdg_bilinear_ensemble_sigmoid's general sweep (z_head !=
+ *   z_tail) writes: the same products, sigmoid 1 / (1 + expf(-s)), fp32 sum in model order, one division by K.
+ *   vals [n_labels,n_head,k] fp32, idx [n_labels,n_head,k] int32, order (P descending, column ascending), which is also the tie
+ *   rule for what is kept (exact ties are common: many probabilities round to 1); padding -inf / -1.  eligible, k, n_tail and
+ *   n_labels as mdg_bilinear_topk.  mask / plane_stride as the *_masked entry points below (mask == NULL: the unmasked kernel,
+ *   no mask memory is read).  mdg_bilinear_ensemble_topk_chunk_tiles: the 64-column tail tiles a workgroup sweeps between two
+ *   rebuilds of the models' z_head . W_sym products (for tests that want sizes at that boundary).
+ *   Workspace: split-bf16 images of every model's z_tail and W_sym (0 for F32), the size mdg_bilinear_ensemble_sigmoid needs.
+ * Deterministic: no atomics, the lists live in registers, nothing is stored before the final k stores per row. */
+int mdg_bilinear_ensemble_topk_chunk_tiles(void);
+size_t mdg_bilinear_ensemble_topk_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_models,
+                                                  int precision);
+int mdg_bilinear_ensemble_topk(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                               float* vals, int32_t* idx, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision,
+                               int k, int eligible, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask,
+                               int64_t plane_stride);
+
 /* Per-row top-k of the all-pairs sweep: for every outcome l and head row i the k largest scores S[l,i,j] (the arithmetic of
  * mdg_bilinear_allpairs' general sweep in `precision`, bit for bit in F32 / BF16X3; the 16-bit modes run the row-statistics
  * sweep, whose fp32 sums are grouped differently: <= 2e-6 of the scale) over the ELIGIBLE tail columns j, and those columns.

@@ -789,6 +789,78 @@ def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", o
     return out
 
 
+def bilinear_ensemble_topk_chunk_tiles() -> int:
+    """The 64-column tail tiles ``bilinear_ensemble_topk`` sweeps between two rebuilds of the models' z_head . W_sym products."""
+    return lib().mdg_bilinear_ensemble_topk_chunk_tiles()
+
+
+def bilinear_ensemble_topk(z_heads, z_tails, w_syms, k: int, *, eligible: str = "all", precision="bf16x3", out=None,
+                           exclude: Optional[torch.Tensor] = None):
+    """Per-row top-k of the checkpoint ensemble: ``(vals [L,Nh,k] fp32, idx [L,Nh,k] int32)``, for every outcome and head row the
+    ``k`` largest P[l,i,j] = mean_m sigmoid(z_heads[m][i]^T w_syms[m][l] z_tails[m][j]) over the eligible tail columns and those
+    columns, ordered by (P descending, column ascending); rows with fewer than ``k`` eligible columns are padded with ``-inf`` /
+    ``-1``.  Nothing of [L,Nh,Nt] is materialised (madrigal/evaluate/predict.py:466-499, 582-614 average the sigmoids; the mean is
+    not monotone in any one model's logit, so ``bilinear_topk`` per model cannot give this ranking).
+
+    K = len(z_heads) in 1..8.  P is bit for bit what ``bilinear_ensemble_sigmoid``'s general sweep writes in the same
+    ``precision`` ("f32" or "bf16x3") -- the sweep it runs when the head is not the tail object, e.g. a row subset.  ``eligible``,
+    ``k``, ``out`` and ``exclude`` as ``bilinear_topk``."""
+    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
+    K = len(zh)
+    if not 1 <= K <= 8:
+        raise ValueError(f"bilinear_ensemble_topk: 1..8 models, got {K}")
+    if len(zt) != K or len(ws) != K:
+        raise ValueError(f"bilinear_ensemble_topk: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
+    if precision not in ENSEMBLE_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    max_k = bilinear_topk_max_k()
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
+        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
+    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
+    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
+    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
+    L, D = ws[0].shape[0], ws[0].shape[1]
+    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
+    dev = zh[0].device
+    for m in range(K):
+        if zh[m].shape != (Nh, D) or zt[m].shape != (Nt, D) or ws[m].shape != (L, D, D):
+            raise ValueError(f"bilinear_ensemble_topk: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
+                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+        if zh[m].device != dev or zt[m].device != dev or ws[m].device != dev:
+            raise ValueError("bilinear_ensemble_topk: every tensor must be on the same device")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
+    shape = (L, Nh, k)
+    if out is None:
+        vals = torch.empty(shape, dtype=torch.float32, device=dev)
+        idx = torch.empty(shape, dtype=torch.int32, device=dev)
+    else:
+        vals, idx = out
+        for t, dt, name in ((vals, torch.float32, "out[0]"), (idx, torch.int32, "out[1]")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous {dt} GPU tensor of shape {shape}")
+    if vals.numel() == 0:
+        return vals, idx
+    if Nt == 0:                                  # no column at all: every row is padding
+        vals.fill_(float("-inf"))
+        idx.fill_(-1)
+        return vals, idx
+    prec = ENSEMBLE_PRECISIONS[precision]
+    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
+    a_h, a_t = arr(zh), arr(zt)
+    for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
+        hi = min(L, lo + 65535)
+        wsp, nbytes = _scratch("mdg_bilinear_ensemble_topk_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
+        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
+        call("mdg_bilinear_ensemble_topk", a_h, a_t, a_w, K, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt,
+             hi - lo, D, prec, int(k), TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]),
+             None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride)
+    return vals, idx
+
+
 def empty_scores(L: int, Nh: int, Nt: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """An uninitialised [L,Nh,Nt] fp32 score (or rank) tensor in the layout the head writes fastest: rows padded to a multiple of
     32 floats, so that every row starts on a 128-byte line whatever Nt is (the real drug counts -- 11 607 in

@@ -1083,3 +1083,119 @@ def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_ind
             ps, pe = pending[b]
             out[ps:pe] = pin_buf[b][: pe - ps].numpy()
     return out
+
+
+def _ensemble_operands(models, zs, label_range, what: str):
+    """Checked operands of the ensemble screens -> (zs, W_sym slices [hi - lo,D,D] per checkpoint, lo, hi, L_all, precision)."""
+    from .models import get_precision
+    models, zs = list(models), list(zs)
+    K = len(models)
+    if not 1 <= K <= 8 or len(zs) != K:
+        raise ValueError(f"{what}: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
+    z0 = zs[0]
+    if not (isinstance(z0, torch.Tensor) and z0.is_cuda):
+        raise ValueError("zs: embeddings must be GPU tensors")
+    ws = [_ensemble_weight(m) for m in models]
+    L_all = ws[0].shape[0]
+    for k in range(K):
+        if zs[k].shape != z0.shape or ws[k].shape[0] != L_all:
+            raise ValueError(f"{what}: checkpoint {k} has z {tuple(zs[k].shape)} and {ws[k].shape[0]} outcomes; "
+                             f"checkpoint 0 has {tuple(z0.shape)} and {L_all}")
+    lo, hi = (0, L_all) if label_range is None else label_range
+    if not (0 <= lo <= hi <= L_all):
+        raise ValueError(f"label_range {label_range} outside [0, {L_all}]")
+    return zs, [w[lo:hi] for w in ws], lo, hi, L_all, get_precision()
+
+
+def _ensemble_exclusion(exclude, L_all: int) -> Optional[torch.Tensor]:
+    if exclude is None:
+        return None
+    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 3:
+        raise ValueError("exclude: expected a mask from known_pairs_mask / ops.pair_mask")
+    if exclude.shape[0] not in (1, L_all):
+        raise ValueError(f"exclude: {exclude.shape[0]} planes; expected 1 or one per outcome of the head ({L_all})")
+    return exclude
+
+
+def _planes(excl, s: int, e: int):
+    """The planes of outcomes [s, e) of an exclusion mask (a shared plane serves every range)."""
+    return None if excl is None else (excl if excl.shape[0] == 1 else excl[s:e])
+
+
+@torch.no_grad()
+def ensemble_top_partners(models, zs, k: int, label_range: Optional[Tuple[int, int]] = None, drug_rows=None,
+                          max_temp_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
+    """``top_partners`` over a checkpoint ensemble -> ``(vals, idx)`` [L', n, k] (fp32, int32): row i of outcome l holds the k
+    largest P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) over j != i and those j, ordered by (P descending, j ascending), padded with
+    -inf / -1 -- the partners the five-seed ensemble of get_twosides_scores_wrapper / get_drugbank_scores_wrapper
+    (madrigal/evaluate/predict.py:466-499, 582-614) rates highest, without its [L,N,N] tensor (``ops.bilinear_ensemble_topk``).
+    The single-model lists cannot be combined into these: the mean of sigmoids is not monotone in any one model's score.
+
+    ``models[m]``: checkpoint m's NovelDDIMultilabel, its BilinearDDIScorer or its original [L,128,128] head weight; ``zs[m]``: its
+    [N,128] embeddings of the same drugs.  ``label_range`` slices every checkpoint's W_sym; ``drug_rows``, ``max_temp_bytes`` and
+    ``exclude`` as ``top_partners``.  Precision follows ``models.precision(...)``; P is bit for bit the general sweep's of
+    ``ops.bilinear_ensemble_sigmoid``."""
+    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_top_partners")
+    N, dev = zs[0].shape[0], zs[0].device
+    rows = _index(drug_rows, N, "drug_rows", dev)
+    excl = _ensemble_exclusion(exclude, L_all)
+    if rows is None:
+        return ops.bilinear_ensemble_topk(zs, zs, ws, k, eligible="not_self", precision=prec, exclude=_planes(excl, lo, hi))
+    n = int(rows.numel())
+    vals = torch.empty((hi - lo, n, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((hi - lo, n, k), dtype=torch.int32, device=dev)
+    chunk = max(1, int(max_temp_bytes) // max(N * k * 8, 1))
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        v, i = ops.bilinear_ensemble_topk(zs, zs, [w[s - lo:e - lo] for w in ws], k, eligible="not_self", precision=prec,
+                                          exclude=_planes(excl, s, e))
+        vals[s - lo:e - lo] = v[:, rows]
+        idx[s - lo:e - lo] = i[:, rows]
+    return vals, idx
+
+
+@torch.no_grad()
+def ensemble_top_pairs(models, zs, K: int, label_range: Optional[Tuple[int, int]] = None, k_row: Optional[int] = None,
+                       max_temp_bytes: int = 1 << 30, info: Optional[dict] = None, exclude: Optional[torch.Tensor] = None):
+    """``top_pairs`` over a checkpoint ensemble -> ``(vals [L', K] fp32, head [L', K], tail [L', K] int64)``: the ``K`` unordered
+    drug pairs with the highest mean probability P[l, i, j] = mean_m sigmoid(S_m[l, i, j]), i > j, ordered by (P descending, i
+    ascending, j ascending), padded with -inf / -1.  Exact for every K and without the [L', N, N] tensor: the lower-triangle lists of
+    ``ops.bilinear_ensemble_topk`` (``k_row`` per row, default min(K, 16)), the K best candidates, and the open rows re-scored with
+    ``ops.bilinear_ensemble_sigmoid`` over those rows -- a row subset is not the tail object, so the general sweep runs and the
+    re-scored probabilities are bit for bit what the lists saw -- merged by ``merge_row_candidates``.  Probabilities tie often (many
+    round to exactly 1), so open rows are common with a small ``k_row``; the result stays exact.
+    ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``max_temp_bytes``, ``info`` and ``exclude`` as ``top_pairs``."""
+    max_k = ops.bilinear_topk_max_k()
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"K: expected a positive int, got {K!r}")
+    k_row = min(K, 16) if k_row is None else k_row
+    if isinstance(k_row, bool) or not isinstance(k_row, int) or not 1 <= k_row <= max_k:
+        raise ValueError(f"k_row: expected an int in 1..{max_k}, got {k_row!r}")
+    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_top_pairs")
+    N, dev = zs[0].shape[0], zs[0].device
+    excl = _ensemble_exclusion(exclude, L_all)
+    out_v = torch.empty((hi - lo, K), dtype=torch.float32, device=dev)
+    out_h = torch.empty((hi - lo, K), dtype=torch.int64, device=dev)
+    out_t = torch.empty((hi - lo, K), dtype=torch.int64, device=dev)
+    opened = []
+    chunk = max(1, int(max_temp_bytes) // max(N * k_row * 48, 1))
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        vals, idx = ops.bilinear_ensemble_topk(zs, zs, [w[s - lo:e - lo] for w in ws], k_row, eligible="lower", precision=prec,
+                                               exclude=_planes(excl, s, e))
+        part = {}
+
+        def rescore(l, rows, s=s):
+            ws_l = [w[s - lo + l:s - lo + l + 1] for w in ws]
+            dense = ops.bilinear_ensemble_sigmoid([z[rows] for z in zs], zs, ws_l, precision=prec)[0]
+            if excl is not None:
+                dense.masked_fill_(ops.pair_mask_rows(excl, 0 if excl.shape[0] == 1 else s + l, rows, N), float("-inf"))
+            return dense
+
+        v, h, t = merge_row_candidates(vals, idx, K, rescore, part)
+        out_v[s - lo:e - lo], out_h[s - lo:e - lo], out_t[s - lo:e - lo] = v, h, t
+        opened += part["open_rows"]
+        del vals, idx, v, h, t
+    if info is not None:
+        info["open_rows"] = opened
+    return out_v, out_h, out_t
