@@ -173,6 +173,40 @@ int mdg_bilinear_ensemble_topk(const float* const* z_head, const float* const* z
                                int k, int eligible, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask,
                                int64_t plane_stride);
 
+/* Threshold selection over the checkpoint ensemble (ABI 26): for every outcome l with its cut thr[l], ALL eligible pairs (i,j) with
+ *   P[l,i,j] = mean_m sigmoid(z_head_m[i]^T W_sym_m[l] z_tail_m[j])  >=  thr[l]
+ * as CSR over the n_labels * n_head rows (l,i), without materialising [L,N,N]: mdg_bilinear_select_*'s contract on the probability
+ * get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) average over the
+ * checkpoints -- "every pair the ensemble calls an interaction with P >= 0.9", the set the reference's users read off that stored
+ * tensor (notebooks/quick_predictions.ipynb cell 8); in LOWER mode the pairs are those of the strict lower triangle
+ * notebooks/normalize_scores.py:39-46 ranks.  The mean of sigmoids is not monotone in any one model's logit, so no union or
+ * intersection of mdg_bilinear_select_* results gives this set.
+ *   Operands as mdg_bilinear_ensemble_topk (HOST arrays of n_models = 1..8 device pointers, 16-byte aligned, D == 128); precision
+ *   MDG_PREC_F32 or MDG_PREC_BF16X3.  P is bit for bit what mdg_bilinear_ensemble_sigmoid's general sweep writes; the compare is
+ *   on the quotient, P >= thr[l] (thr [n_labels] fp32, device): -inf selects every eligible pair, +inf or a NaN cut none.
+ *   mdg_bilinear_ensemble_select_count: row_counts [n_labels,n_head] int32, every entry written, zeros included; the caller's
+ *     exclusive prefix sum over the flattened counts is row_ptr.
+ *   mdg_bilinear_ensemble_select_fill: row_ptr [n_labels*n_head + 1] int64; cols [T] int32 and vals [T] fp32, T = row_ptr[last]:
+ *     the selected columns of row (l,i) in ASCENDING order and their probabilities -- canonical CSR, the order torch.nonzero gives
+ *     on the dense mask.  Bounded writes as mdg_bilinear_select_fill: slot s of row r is stored only if 0 <= row_ptr[r] <= s <
+ *     row_ptr[r+1]; all slot arithmetic is 64-bit.
+ *   eligible, n_tail (>= 1, < 2^31 - 64) and n_labels (<= 65535 per call) as mdg_bilinear_select_*; mask / plane_stride as the
+ *   *_masked entry points below (mask == NULL: the unmasked kernel, no mask memory is read).  The tail tiles between two rebuilds of
+ *   the models' z_head . W_sym products are mdg_bilinear_ensemble_topk_chunk_tiles().
+ *   Workspace: the size mdg_bilinear_ensemble_sigmoid_workspace_bytes gives (0 for F32).
+ * Deterministic: every row belongs to one wave that walks the column tiles in ascending order; no atomics; bit-identical from
+ * launch to launch. */
+size_t mdg_bilinear_ensemble_select_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_models,
+                                                    int precision);
+int mdg_bilinear_ensemble_select_count(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                                       const float* thr, int32_t* row_counts, int64_t n_head, int64_t n_tail, int64_t n_labels,
+                                       int64_t D, int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream,
+                                       const uint32_t* mask, int64_t plane_stride);
+int mdg_bilinear_ensemble_select_fill(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                                      const float* thr, const int64_t* row_ptr, int32_t* cols, float* vals, int64_t n_head,
+                                      int64_t n_tail, int64_t n_labels, int64_t D, int precision, int eligible, void* workspace,
+                                      size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
+
 /* Per-row top-k of the all-pairs sweep: for every outcome l and head row i the k largest scores S[l,i,j] (the arithmetic of
  * mdg_bilinear_allpairs' general sweep in `precision`, bit for bit in F32 / BF16X3; the 16-bit modes run the row-statistics
  * sweep, whose fp32 sums are grouped differently: <= 2e-6 of the scale) over the ELIGIBLE tail columns j, and those columns.

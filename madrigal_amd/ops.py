@@ -861,6 +861,137 @@ def bilinear_ensemble_topk(z_heads, z_tails, w_syms, k: int, *, eligible: str = 
     return vals, idx
 
 
+def _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=True):
+    """Validation shared by ``bilinear_ensemble_select_count`` and ``bilinear_ensemble_select``: the lists, the names and the
+    thresholds first (on whatever device the tensors live), then the device -> (zh, zt, ws, thr, precision code).
+    ``nan_check_on_device=False``: the caller reads the NaN flag of GPU thresholds itself, together with another value."""
+    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
+    K = len(zh)
+    if not 1 <= K <= 8:
+        raise ValueError(f"{what}: 1..8 models, got {K}")
+    if len(zt) != K or len(ws) != K:
+        raise ValueError(f"{what}: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
+    if precision not in ENSEMBLE_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    for t, name, nd in ((zh[0], "z_heads[0]", 2), (zt[0], "z_tails[0]", 2), (ws[0], "w_syms[0]", 3), (thresholds, "thresholds", 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    forward_only(*zh, *zt, *ws, thresholds)
+    L, D = ws[0].shape[0], ws[0].shape[1]
+    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
+    for m in range(K):
+        if tuple(zh[m].shape) != (Nh, D) or tuple(zt[m].shape) != (Nt, D) or tuple(ws[m].shape) != (L, D, D):
+            raise ValueError(f"{what}: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
+                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+    if thresholds.shape[0] != L:
+        raise ValueError(f"thresholds: expected [{L}] (one cut per outcome), got {tuple(thresholds.shape)}")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    if Nt >= (1 << 31) - 64:
+        raise ValueError(f"z_tails: {Nt} rows do not fit the int32 column indices")
+    if L and (nan_check_on_device or not thresholds.is_cuda) and bool(torch.isnan(thresholds).any()):
+        raise ValueError(_SELECT_NAN)
+    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
+    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
+    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
+    thr = _f32_cuda(thresholds, "thresholds", 1)
+    dev = zh[0].device
+    if any(t.device != dev for t in (*zh, *zt, *ws, thr)):
+        raise ValueError(f"{what}: every tensor must be on the same device")
+    return zh, zt, ws, thr, ENSEMBLE_PRECISIONS[precision]
+
+
+def _ensemble_select_sweep(entry, zh, zt, ws, thr, prec, eligible, mask, mstride, outputs) -> None:
+    """One pass (``entry``: mdg_bilinear_ensemble_select_count / _fill) over all outcomes, 65 535 per call (the grid's y extent).
+    ``outputs(lo)``: the pass's own pointer arguments for the outcomes from ``lo`` on."""
+    K, L, D, Nh, Nt = len(zh), ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
+    dev = zh[0].device
+    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
+    a_h, a_t = arr(zh), arr(zt)
+    for lo in range(0, L, 65535):
+        hi = min(L, lo + 65535)
+        wsp, nbytes = _scratch("mdg_bilinear_ensemble_select_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
+        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
+        call(entry, a_h, a_t, a_w, K, thr.data_ptr() + lo * 4, *outputs(lo), Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(wsp),
+             nbytes, _stream(zh[0]), None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride)
+
+
+def _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride, out=None) -> torch.Tensor:
+    L, Nh, Nt = ws[0].shape[0], zh[0].shape[0], zt[0].shape[0]
+    if out is None:
+        counts = torch.empty((L, Nh), dtype=torch.int32, device=zh[0].device)
+    else:
+        counts = out
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == zh[0].device and out.dtype == torch.int32
+                and tuple(out.shape) == (L, Nh) and out.is_contiguous()):
+            raise ValueError(f"out: expected a contiguous int32 GPU tensor of shape {(L, Nh)}")
+    if counts.numel() == 0:
+        return counts
+    if Nt == 0:                                  # no column at all
+        return counts.zero_()
+    _ensemble_select_sweep("mdg_bilinear_ensemble_select_count", zh, zt, ws, thr, prec, eligible, mask, mstride,
+                           lambda lo: (counts.data_ptr() + lo * Nh * 4,))
+    return counts
+
+
+def bilinear_ensemble_select_count(z_heads, z_tails, w_syms, thresholds: torch.Tensor, *, eligible: str = "all", precision="bf16x3",
+                                   exclude: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-row sizes of ``bilinear_ensemble_select`` -> int32 [L, Nh]: ``counts[l, i]`` is the number of eligible tail columns j with
+    P[l,i,j] = mean_m sigmoid(z_heads[m][i]^T w_syms[m][l] z_tails[m][j]) ``>= thresholds[l]``, counted inside the ensemble's
+    all-pairs sweep (nothing of [L,Nh,Nt] is materialised; madrigal/evaluate/predict.py:466-499, 582-614 average the sigmoids).
+    With one drug set and ``eligible="not_self"`` this is the degree of drug i in the network the ensemble predicts for the outcome.
+
+    K = len(z_heads) in 1..8; P is bit for bit ``bilinear_ensemble_sigmoid``'s general sweep in ``precision`` ("f32" or "bf16x3").
+    ``thresholds``: fp32 [L] probabilities, no NaN; ``-inf`` (or 0.0) counts every eligible column, ``+inf`` none.  ``eligible`` and
+    ``exclude`` as ``bilinear_select_count``.  ``out``: optional contiguous int32 [L, Nh] GPU tensor; every entry is written, zeros
+    included.  Deterministic: no atomics."""
+    zh, zt, ws, thr, prec = _ensemble_select_args("bilinear_ensemble_select_count", z_heads, z_tails, w_syms, thresholds, eligible, precision)
+    mask, mstride = _exclude_args(exclude, zh[0], zh[0].shape[0], zt[0].shape[0], ws[0].shape[0])
+    return _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride, out)
+
+
+def bilinear_ensemble_select(z_heads, z_tails, w_syms, thresholds: torch.Tensor, *, eligible: str = "all", precision="bf16x3",
+                             max_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
+    """Every eligible pair the checkpoint ensemble rates at or above a per-outcome probability cut, as CSR -> ``(row_ptr int64
+    [L*Nh + 1], cols int32 [T], vals fp32 [T])``: row ``l * Nh + i`` holds, at ``[row_ptr[r], row_ptr[r + 1])``, the tail columns j
+    with P[l,i,j] = mean_m sigmoid(z_heads[m][i]^T w_syms[m][l] z_tails[m][j]) ``>= thresholds[l]`` in ascending order and those
+    probabilities.  This is ``torch.nonzero((P >= thresholds[:, None, None]) & eligible_mask)`` of ``bilinear_ensemble_sigmoid``'s
+    dense result, in that order, with nothing of [L,Nh,Nt] materialised: ``bilinear_select``'s flow -- a counting sweep,
+    ``torch.cumsum``, one host read of the total ``T`` (the thresholds' NaN flag travels with it), a filling sweep.  The mean of K
+    sigmoids is not monotone in any one model's logit, so no combination of ``bilinear_select`` results per model gives this set.
+
+    K = len(z_heads) in 1..8; P is bit for bit the general sweep's of ``bilinear_ensemble_sigmoid`` in ``precision`` ("f32" or
+    "bf16x3").  ``thresholds``: fp32 [L], no NaN; the rule is ``>=``, so a cut at the K-th best probability includes every tie with
+    it (at saturated inputs many probabilities are exactly 1.0).  ``eligible``, ``max_bytes`` and ``exclude`` as ``bilinear_select``.
+    Deterministic: no atomics; bit-identical from call to call."""
+    what = "bilinear_ensemble_select"
+    zh, zt, ws, thr, prec = _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=False)
+    L, Nh, Nt = ws[0].shape[0], zh[0].shape[0], zt[0].shape[0]
+    dev = zh[0].device
+    mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
+    counts = _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride)      # (a NaN cut selects nothing: harmless until it is refused below)
+    row_ptr = torch.zeros(L * Nh + 1, dtype=torch.int64, device=dev)
+    T = 0
+    if L:
+        row_ptr[1:] = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+        T, bad = torch.stack([row_ptr[-1], torch.isnan(thr).any().to(torch.int64)]).tolist()          # the one host read
+        if bad:
+            raise ValueError(_SELECT_NAN)
+    if 8 * T > int(max_bytes):
+        raise ValueError(f"{what}: T = {T} selected pairs need {8 * T} bytes, more than max_bytes = {int(max_bytes)}; "
+                         "raise the thresholds, pass fewer outcomes per call, or raise max_bytes")
+    cols = torch.empty(T, dtype=torch.int32, device=dev)
+    vals = torch.empty(T, dtype=torch.float32, device=dev)
+    if T == 0:
+        return row_ptr, cols, vals
+    _ensemble_select_sweep("mdg_bilinear_ensemble_select_fill", zh, zt, ws, thr, prec, eligible, mask, mstride,
+                           lambda lo: (row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols), _ptr(vals)))
+    return row_ptr, cols, vals
+
+
 def empty_scores(L: int, Nh: int, Nt: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """An uninitialised [L,Nh,Nt] fp32 score (or rank) tensor in the layout the head writes fastest: rows padded to a multiple of
     32 floats, so that every row starts on a 128-byte line whatever Nt is (the real drug counts -- 11 607 in

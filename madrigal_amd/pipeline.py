@@ -1199,3 +1199,71 @@ def ensemble_top_pairs(models, zs, K: int, label_range: Optional[Tuple[int, int]
     if info is not None:
         info["open_rows"] = opened
     return out_v, out_h, out_t
+
+
+def _ensemble_select_operands(models, zs, thresholds, label_range, exclude, what: str):
+    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, what)
+    return zs, ws, _cuts(thresholds, hi - lo, zs[0].device), prec, _planes(_ensemble_exclusion(exclude, L_all), lo, hi), hi - lo
+
+
+@torch.no_grad()
+def ensemble_partner_counts(models, zs, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30,
+                            exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``partner_counts`` over a checkpoint ensemble -> int32 [L', N]: ``counts[l, i]`` = #{j != i : P[l, i, j] >= thresholds[l]},
+    P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) -- the degree of drug i in the network the ensemble of get_twosides_scores_wrapper /
+    get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) predicts for outcome l, counted inside the sweep
+    (``ops.bilinear_ensemble_select_count``, ``not_self`` mode): no [L', N, N] tensor at any N.
+
+    ``thresholds``: a PROBABILITY cut, a number such as 0.9 or [L'] (no NaN), e.g. ``ensemble_top_pairs(models, zs, K)[0][:, -1]``;
+    the rule is ``>=``, so ties with the K-th pair are counted, and at saturated inputs many probabilities are exactly 1.0.  A cut on
+    the ensemble's probability needs no calibration per outcome, unlike a cut on one model's logit.  Normalised ranks under the
+    ensemble are not part of this.  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as
+    ``partner_counts``; ``max_bytes`` is accepted for symmetry with ``ensemble_partners_above`` (the result is 4 L' N bytes)."""
+    zs, ws, thr, prec, excl, _ = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_partner_counts")
+    return ops.bilinear_ensemble_select_count(zs, zs, ws, thr, eligible="not_self", precision=prec, exclude=excl)
+
+
+@torch.no_grad()
+def ensemble_partners_above(models, zs, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30,
+                            exclude: Optional[torch.Tensor] = None):
+    """``partners_above`` over a checkpoint ensemble, as CSR -> ``(row_ptr int64 [L' * N + 1], cols int32 [T], vals fp32 [T])``: row
+    ``l * N + i`` lists ALL j != i with P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) >= thresholds[l] in ascending order and those
+    probabilities (``ops.bilinear_ensemble_select``, ``not_self`` mode; ``csr_rows(row_ptr, N)`` gives every entry's outcome and
+    drug).  Where ``ensemble_top_partners`` returns at most 32 partners of a drug, this returns its whole neighbourhood -- a hub has
+    hundreds; every unordered pair appears from both sides, with P[l, i, j] and P[l, j, i] (equal up to the last bits).  More than
+    ``max_bytes`` (8 bytes per entry) raises a ValueError naming the size before anything is allocated.
+
+    ``thresholds``: a PROBABILITY cut, a number such as 0.9 or [L'] (no NaN), e.g. ``ensemble_top_pairs(models, zs, K)[0][:, -1]``;
+    the rule is ``>=``, so ties with the K-th pair are included, and at saturated inputs many probabilities are exactly 1.0.
+    Normalised ranks under the ensemble are not part of this.  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``;
+    ``exclude`` as ``partners_above``."""
+    zs, ws, thr, prec, excl, _ = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_partners_above")
+    return ops.bilinear_ensemble_select(zs, zs, ws, thr, eligible="not_self", precision=prec, max_bytes=max_bytes, exclude=excl)
+
+
+@torch.no_grad()
+def ensemble_pairs_above(models, zs, thresholds, label_range: Optional[Tuple[int, int]] = None, max_bytes: int = 1 << 30,
+                         exclude: Optional[torch.Tensor] = None):
+    """``pairs_above`` over a checkpoint ensemble -- "every pair the five-seed ensemble calls an interaction with P >= 0.9", the
+    outcome's predicted network -- -> ``(offsets int64 [L' + 1], head int64 [T], tail int64 [T], vals fp32 [T])``: outcome l owns the
+    entries ``offsets[l]:offsets[l + 1]``.  The pair {i, j} is rated P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) with i > j, the
+    strict-lower-triangle entry ``ensemble_top_pairs`` uses, and is selected when that probability is ``>= thresholds[l]``; the
+    entries are ordered by (outcome, head, tail) ascending.  Nothing of [L', N, N] is materialised (``ops.bilinear_ensemble_select``,
+    ``lower`` mode: a counting and a filling sweep); ``head`` is expanded from the sweep's row pointers (``csr_rows``).  The mean of
+    sigmoids is not monotone in any one model's score, so no union or intersection of ``pairs_above`` per checkpoint gives this set.
+    More than ``max_bytes`` (8 bytes per pair in the sweep's result) raises a ValueError naming the size.
+
+    Where a cut comes from (``thresholds``: a PROBABILITY, a number or [L'], no NaN):
+      * a number such as 0.9: the same cut means the same thing for every outcome, no calibration per outcome;
+      * the K-th value of ``ensemble_top_pairs``: ``ensemble_pairs_above(models, zs, ensemble_top_pairs(models, zs, K)[0][:, -1])``
+        holds those K pairs and every pair tied with the last of them (the rule is ``>=``).  At saturated inputs many probabilities
+        are exactly 1.0, so such a tie set can be large: ``max_bytes`` bounds it.
+    Normalised ranks under the ensemble are not part of this (``normalized_ranks_of`` ranks one model's scores).
+    ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as ``pairs_above``."""
+    zs, ws, thr, prec, excl, n_out = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_pairs_above")
+    row_ptr, cols, vals = ops.bilinear_ensemble_select(zs, zs, ws, thr, eligible="lower", precision=prec, max_bytes=max_bytes, exclude=excl)
+    N = zs[0].shape[0]
+    _, head, offsets = csr_rows(row_ptr, N, total=int(cols.numel()))
+    if N == 0:
+        offsets = torch.zeros(n_out + 1, dtype=torch.int64, device=zs[0].device)
+    return offsets, head, cols.long(), vals
