@@ -512,6 +512,24 @@ int mdg_fusion_attention_qkv(const float* q, int64_t ldq, int hq, const float* k
                              float qscale, void* stream);
 int mdg_token_scaled_rows(const float* tokens, int64_t ldt, const float* rf, int nr, int64_t D, int64_t d, float eps, float* X,
                           int64_t ldx, float* tail, int64_t ldtail, float* rstd, int64_t rows, void* stream);
+/* The last layer of the fusion transformer in inference, where only the rows that are pooled continue past the attention (ABI 27;
+ * models.py:401-455 with the pooling of :422-443 reading the bottleneck tokens alone; TransformerFusion._layer with keep_rows).
+ * Keys and values are needed for all R live rows, queries and outputs for the n_keep kept rows only.  q_slot [R]: the compact index
+ * of a kept row, negative for a row that is not kept (a slot >= n_keep counts as not kept).
+ *   mdg_layernorm_packed_kept   mdg_layernorm_packed without the fp32 rows, plus a second image y_kept of n_keep rows
+ *                               (mdg_pack_operand_bytes(n_keep, d, precision) bytes): row q_slot[r] of it is row r of y_packed, so
+ *                               y_kept equals mdg_pack_operand of the kept fp32 rows gathered in slot order, bit for bit.
+ *                               16-bit modes, d a multiple of 64.
+ *   mdg_fusion_attention_kept   compact mode of mdg_fusion_attention (row_start [n+1] the tile table, row_bits [R]) with q
+ *                               [n_keep, ldq] and out [n_keep, ldo] holding the kept rows in slot order, k and v [R, ld] with their
+ *                               own base pointers.  Row q_slot[r] of out equals row r of mdg_fusion_attention's output bit for bit;
+ *                               query rows that are not kept are never read.  No weights out, no dropout. */
+int mdg_layernorm_packed_kept(const float* x, int64_t ldx, const float* gamma, const float* beta, int64_t rows, int64_t d, float eps,
+                              int precision, void* y_packed, size_t y_packed_bytes, const int* q_slot, int64_t n_keep, void* y_kept,
+                              size_t y_kept_bytes, void* stream);
+int mdg_fusion_attention_kept(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld, float* out, int64_t ldo,
+                              const int64_t* row_start, const uint32_t* row_bits, const int* q_slot, int64_t n_keep, int64_t n, int H,
+                              int dh, void* stream);
 
 /* Cross-attention pooling with one learned query shared by all drugs: out[i,h,:] = softmax_j(q_h . K_ijh / sqrt(dh)) V_ijh.
  * q_proj [H*dh] (already projected), kv_proj [n*Tk, 2*H*dh] = K|V of the Tk allowed key tokens of each drug.

@@ -95,6 +95,14 @@ __device__ __forceinline__ void load_rows(const float* mat, int64_t ld, int T, i
   }
 }
 
+// load_rows of a compact operand: tile row (lane >> 4) + 4 i is row slot[i] of mat, a negative slot a row of zeros that is never read
+__device__ __forceinline__ void load_rows_slots(const float* mat, int64_t ld, const int* slot, int k0, int dh, int lane, f32x4 (&r)[8]) {
+  const int k = k0 + 4 * (lane & 15);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    r[i] = (slot[i] >= 0 && k < dh) ? *reinterpret_cast<const f32x4*>(mat + static_cast<int64_t>(slot[i]) * ld + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 __device__ __forceinline__ void write_rows(const f32x4 (&r)[8], float* tile, int lane) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(tile + tile_off((lane >> 4) + 4 * i, lane & 15)) = r[i];
@@ -106,9 +114,10 @@ __device__ __forceinline__ void write_rows(const f32x4 (&r)[8], float* tile, int
 // LDS; with the weights as the A operand the result comes out with the lane on the column, so every store is a 128-byte
 // row piece.
 // kTrim: dh need not be a multiple of 64; the 32-column halves of the last piece that lie wholly past dh are skipped.
-template <bool kTrim = false>
+// kSlots: out is compact.  Lane x holds in `oslot` the output row of tile row x, negative for a row that is not stored.
+template <bool kTrim = false, bool kSlots = false>
 __device__ __forceinline__ void weights_rows_product(const f32x16& w, const float* m, int64_t ldm, float* out, int64_t ldo, int T, int dh,
-                                                     float* ta, float* tb, int x, int half, int lane) {
+                                                     float* ta, float* tb, int x, int half, int lane, int oslot = 0) {
   f32x4 pre[8];
   load_rows(m, ldm, T, 0, dh, lane, pre);
   write_rows(pre, ta, lane);
@@ -132,8 +141,15 @@ __device__ __forceinline__ void weights_rows_product(const f32x16& w, const floa
       if (c0 + col < dh) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int i = (v & 3) + 8 * (v >> 2) + 4 * half;
-          if (i < T) out[static_cast<int64_t>(i) * ldo + c0 + col] = o[v];
+          if constexpr (kSlots) {                          // row i's slot sits on lane i: one scalar read per lane half
+            const int i0 = (v & 3) + 8 * (v >> 2);
+            const int s0 = __builtin_amdgcn_readlane(oslot, i0), s1 = __builtin_amdgcn_readlane(oslot, i0 + 4);
+            const int s = half ? s1 : s0;
+            if (s >= 0) out[static_cast<int64_t>(s) * ldo + c0 + col] = o[v];
+          } else {
+            const int i = (v & 3) + 8 * (v >> 2) + 4 * half;
+            if (i < T) out[static_cast<int64_t>(i) * ldo + c0 + col] = o[v];
+          }
         }
       }
     }
@@ -144,18 +160,21 @@ __device__ __forceinline__ void weights_rows_product(const f32x16& w, const floa
 // acc += B^T-style product of the swapped layout: acc[v] (lane x) += sum_k a[j_v][k] * b[x][k] over the dh columns of two
 // row-major operands a (rows -> accumulator registers) and b (rows -> lanes), b scaled by `bscale`.
 // kTrim: the 8-column steps of the last piece that lie wholly past dh (zero on both sides) are skipped.
-template <bool kTrim = false>
+// kSlots: b is compact, its tile rows found through `bslot` (load_rows_slots).
+template <bool kTrim = false, bool kSlots = false>
 __device__ __forceinline__ void rows_product(const float* a, int64_t lda, const float* b, int64_t ldb, int T, int dh, float bscale, float* ta,
-                                             float* tb, int x, int half, int lane, f32x16& acc) {
+                                             float* tb, int x, int half, int lane, f32x16& acc, const int* bslot = nullptr) {
   f32x4 ra[8], rb[8];
   load_rows(a, lda, T, 0, dh, lane, ra);
-  load_rows(b, ldb, T, 0, dh, lane, rb);
+  if constexpr (kSlots) load_rows_slots(b, ldb, bslot, 0, dh, lane, rb);
+  else load_rows(b, ldb, T, 0, dh, lane, rb);
   for (int k0 = 0; k0 < dh; k0 += 64) {
     write_rows(ra, ta, lane);
     write_rows(rb, tb, lane);
     if (k0 + 64 < dh) {                                        // the next 64 columns travel while these feed the MFMAs
       load_rows(a, lda, T, k0 + 64, dh, lane, ra);
-      load_rows(b, ldb, T, k0 + 64, dh, lane, rb);
+      if constexpr (kSlots) load_rows_slots(b, ldb, bslot, k0 + 64, dh, lane, rb);
+      else load_rows(b, ldb, T, k0 + 64, dh, lane, rb);
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -289,6 +308,53 @@ __global__ __launch_bounds__(256) void fusion_attention_qkv_kernel(const AttnQkv
   masked_softmax(acc, attn_blocked(p.row_start, p.row_bits, p.kpm_bits, p.src_bits, drug, base, xr), T, half);
   weights_rows_product<true>(acc, p.v + base * p.ldv + head * p.hv, p.ldv, p.out + base * p.ldo + head * p.ho, p.ldo, T, p.dv, ta, tb, x,
                              half, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The compact-mode forward pass for the last layer, where only some query rows continue (TransformerFusion._layer with keep_rows):
+// k and v hold all R live rows, q and out only the kept ones, row q_slot[r] for live row r (negative: r is not kept).  A lane's scores
+// and its output row depend on its own query row and the tile's key / value rows alone, and the products run in fusion_attention_kernel's
+// order, so a kept row comes out with that kernel's bits.  A row that is not kept is staged as zeros (zero logits, a finite softmax)
+// and stored nowhere; a tile without a kept row does nothing.  No attention weights out, no dropout.
+// ---------------------------------------------------------------------------------------------
+struct AttnKeptArgs {
+  const float* q; int64_t ldq;       // [n_keep, H*dh]
+  const float* k; const float* v; int64_t ld;      // [R, .]: one row stride for both
+  float* out; int64_t ldo;           // [n_keep, H*dh]
+  const int64_t* row_start;          // [n+1] first row of each tile
+  const uint32_t* row_bits;          // [R] as AttnArgs, or null
+  const int* q_slot;                 // [R]
+  int64_t n, n_keep;
+  int H, dh;
+  float qscale;
+};
+
+__global__ __launch_bounds__(256) void fusion_attention_kept_kernel(const AttnKeptArgs p) {
+  __shared__ __attribute__((aligned(16))) float stage[4][2][kTileFloats];
+  const int lane = threadIdx.x & 63, x = lane & 31, half = lane >> 5, wave = threadIdx.x >> 6;
+  const int64_t gw = static_cast<int64_t>(blockIdx.x) * 4 + wave;
+  if (gw >= p.n * p.H) return;
+  const int64_t tile = gw / p.H;
+  const int head = static_cast<int>(gw % p.H);
+  const int64_t base = p.row_start[tile];
+  const int T = static_cast<int>(p.row_start[tile + 1] - base);
+  if (T <= 0) return;
+  const int xr = x < T ? x : T - 1;
+  int slot = x < T ? p.q_slot[base + x] : -1;
+  if (slot >= p.n_keep) slot = -1;                             // (a slot outside q and out is a row that is not kept)
+  if (__ballot(slot >= 0) == 0) return;
+  int qs[8];                                                   // the slots of the eight tile rows this lane stages
+#pragma unroll
+  for (int i = 0; i < 8; ++i) qs[i] = __shfl(slot, (lane >> 4) + 4 * i, 64);
+  float* const ta = stage[wave][0];
+  float* const tb = stage[wave][1];
+
+  f32x16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  rows_product<false, true>(p.k + base * p.ld + head * p.dh, p.ld, p.q + head * p.dh, p.ldq, T, p.dh, p.qscale, ta, tb, x, half, lane, acc, qs);
+  masked_softmax(acc, p.row_bits ? p.row_bits[base + xr] : 0u, T, half);
+  weights_rows_product<false, true>(acc, p.v + base * p.ld + head * p.dh, p.ld, p.out + head * p.dh, p.ldo, T, p.dh, ta, tb, x, half, lane, slot);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -807,6 +873,24 @@ extern "C" int mdg_fusion_attention_qkv(const float* q, int64_t ldq, int hq, con
                 "%s: bad strides / alignment", who);
   AttnQkvArgs a{q, k, v, ldq, ldk, ldv, hq, hk, hv, out, ldo, ho, kpm_bits, src_bits, row_start, row_bits, n, S, H, ds, dv, qscale};
   hipLaunchKernelGGL(fusion_attention_qkv_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n * H, 4))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a);
+  MDG_CHECK_LAUNCH(who);
+  return MDG_OK;
+}
+
+extern "C" int mdg_fusion_attention_kept(const float* q, int64_t ldq, const float* k, const float* v, int64_t ld, float* out, int64_t ldo,
+                                         const int64_t* row_start, const uint32_t* row_bits, const int* q_slot, int64_t n_keep, int64_t n,
+                                         int H, int dh, void* stream) {
+  const char* who = "mdg_fusion_attention_kept";
+  MDG_CHECK_ARG(n >= 0 && n_keep >= 0 && n_keep < (1ll << 31), "%s: bad sizes", who);
+  MDG_CHECK_ARG(H >= 1 && dh >= 8 && dh % 32 == 0 && dh <= 1024, "%s: head_dim must be a multiple of 32 (got %d)", who, dh);
+  if (n == 0 || n_keep == 0) return MDG_OK;
+  MDG_CHECK_ARG(q && k && v && out && row_start && q_slot, "%s: null pointer", who);
+  const int64_t d = static_cast<int64_t>(H) * dh;
+  MDG_CHECK_ARG(ldq % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && ldq >= d && ld >= d && ldo >= d && mdg_aligned16(q) && mdg_aligned16(k) &&
+                    mdg_aligned16(v) && mdg_aligned16(out), "%s: bad strides / alignment", who);
+  AttnKeptArgs a{q, ldq, k, v, ld, out, ldo, row_start, row_bits, q_slot, n, n_keep, H, dh, 1.0f / sqrtf(static_cast<float>(dh))};
+  hipLaunchKernelGGL(fusion_attention_kept_kernel, dim3(static_cast<unsigned>(mdg_cdiv(n * H, 4))), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
   MDG_CHECK_LAUNCH(who);
   return MDG_OK;

@@ -1309,11 +1309,13 @@ __device__ __forceinline__ void ln_row_stats(const float* __restrict__ xr, int l
 }
 
 // the normalised row from its statistics, written as fp32 (y non-null) and / or as operand image (img_hi non-null); v is left
-// holding the normalised row (what layernorm_logits_kernel dots with G)
+// holding the normalised row (what layernorm_logits_kernel dots with G).  img_kept non-null: the image row is written a second time,
+// from the same registers, as row row_kept of that image (layernorm_kept_kernel)
 template <int VEC>
 __device__ __forceinline__ void ln_apply_store(f32x4 (&v)[VEC], int lane, int d, float mean, float rstd, const float* __restrict__ g,
                                                const float* __restrict__ b, float* __restrict__ y, int64_t ldy, int64_t row,
-                                               char* __restrict__ img_hi, int img_x3) {
+                                               char* __restrict__ img_hi, int img_x3, char* __restrict__ img_kept = nullptr,
+                                               int64_t row_kept = 0) {
   float* yr = y + row * ldy;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -1338,8 +1340,14 @@ __device__ __forceinline__ void ln_apply_store(f32x4 (&v)[VEC], int lane, int d,
           char* o_ = img_hi + img_off_x3(row, c, d);
           *reinterpret_cast<bf16x4*>(o_) = hi;
           *reinterpret_cast<bf16x4*>(o_ + 64) = lo;
+          if (img_kept) {
+            char* k_ = img_kept + img_off_x3(row_kept, c, d);
+            *reinterpret_cast<bf16x4*>(k_) = hi;
+            *reinterpret_cast<bf16x4*>(k_ + 64) = lo;
+          }
         } else {
           *reinterpret_cast<bf16x4*>(img_hi + (row * d + c) * 2) = hi;
+          if (img_kept) *reinterpret_cast<bf16x4*>(img_kept + (row_kept * d + c) * 2) = hi;
         }
       }
     }
@@ -1359,40 +1367,82 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   ln_apply_store<VEC>(v, lane, d, mean, rstd, g, b, y, ldy, row, img_hi, img_x3);
 }
 
-// layernorm_kernel plus H dot products of each normalised fp32 row, taken while the row is in registers:
-// logits[row, h] = sum_c LN(x)[row, c] * G[h, c] (the folded cross-attention pooling's key logits; H <= 64).
-// The row's fp32 output and image are those of layernorm_kernel bit for bit; the dot order is fixed (lane-major, then the
-// wave's butterfly), so the logits are bit-identical from one launch to the next.
+// layernorm_kernel's image alone (no fp32 rows), with the rows that continue written a second time into a compact image of their
+// own: row q_slot[row] of img_kept when that slot lies in [0, n_keep).  Both copies come from the same registers, so the compact
+// image holds what prep_operands_kernel writes from the gathered fp32 rows.
 template <int VEC>
-__global__ __launch_bounds__(256) void layernorm_logits_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
-                                                               const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
-                                                               int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3,
-                                                               const float* __restrict__ G, int H, float* __restrict__ logits) {
+__global__ __launch_bounds__(256) void layernorm_kept_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
+                                                             const float* __restrict__ b, int64_t rows, int d, float eps,
+                                                             char* __restrict__ img_hi, int img_x3, const int* __restrict__ q_slot,
+                                                             int64_t n_keep, char* __restrict__ img_kept) {
   const int lane = threadIdx.x & 63;
   const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   f32x4 v[VEC];
   float mean, rstd;
   ln_row_stats<VEC>(x + row * ldx, lane, d, eps, v, mean, rstd);
-  ln_apply_store<VEC>(v, lane, d, mean, rstd, g, b, y, ldy, row, img_hi, img_x3);
-  float mine = 0.f;                                      // lane h keeps logit h: one coalesced store per row
+  const int slot = q_slot[row];
+  ln_apply_store<VEC>(v, lane, d, mean, rstd, g, b, nullptr, 0, row, img_hi, img_x3, (slot >= 0 && slot < n_keep) ? img_kept : nullptr, slot);
+}
+
+// layernorm_kernel plus H dot products of each normalised fp32 row, taken while the row is in registers:
+// logits[row, h] = sum_c LN(x)[row, c] * G[h, c] (the folded cross-attention pooling's key logits; H <= 64).
+// The row's fp32 output and image are those of layernorm_kernel bit for bit; the dot order is fixed (lane-major, then the
+// wave's butterfly), so the logits are bit-identical from one launch to the next.
+// A wave holds kLogitRows consecutive rows, so that a row of G read once meets all of them (one row per wave read the whole of G,
+// 64 KB at d = 2048 and H = 8, for every row); each row's sums run in the order they had alone.
+constexpr int kLogitRows = 4;
+
+template <int VEC>
+__global__ __launch_bounds__(256) void layernorm_logits_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
+                                                               const float* __restrict__ b, float* __restrict__ y, int64_t ldy,
+                                                               int64_t rows, int d, float eps, char* __restrict__ img_hi, int img_x3,
+                                                               const float* __restrict__ G, int H, float* __restrict__ logits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row0 = (static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6)) * kLogitRows;
+  if (row0 >= rows) return;
+  f32x4 v[kLogitRows][VEC];
+#pragma unroll
+  for (int j = 0; j < kLogitRows; ++j) {
+    if (row0 + j < rows) {
+      float mean, rstd;
+      ln_row_stats<VEC>(x + (row0 + j) * ldx, lane, d, eps, v[j], mean, rstd);
+      ln_apply_store<VEC>(v[j], lane, d, mean, rstd, g, b, y, ldy, row0 + j, img_hi, img_x3);
+    } else {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) v[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  float mine[kLogitRows];                                // lane h keeps logit h: one coalesced store per row
+#pragma unroll
+  for (int j = 0; j < kLogitRows; ++j) mine[j] = 0.f;
 #pragma unroll 1
   for (int h = 0; h < H; ++h) {
     const float* gh = G + static_cast<int64_t>(h) * d;
-    float s = 0.f;
+    float s[kLogitRows];
+#pragma unroll
+    for (int j = 0; j < kLogitRows; ++j) s[j] = 0.f;
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       const int c = (lane + 64 * i) * 4;
       if (c < d) {
         const f32x4 gg = *reinterpret_cast<const f32x4*>(gh + c);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s += v[i][e] * gg[e];
+        for (int j = 0; j < kLogitRows; ++j) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[j] += v[j][i][e] * gg[e];
+        }
       }
     }
-    s = mdg_wave_sum(s);
-    if (lane == h) mine = s;
+#pragma unroll
+    for (int j = 0; j < kLogitRows; ++j) {
+      const float t = mdg_wave_sum(s[j]);
+      if (lane == h) mine[j] = t;
+    }
   }
-  if (lane < H) logits[row * H + lane] = mine;
+#pragma unroll
+  for (int j = 0; j < kLogitRows; ++j)
+    if (row0 + j < rows && lane < H) logits[(row0 + j) * H + lane] = mine[j];
 }
 
 // LayerNorm's row statistics only: rstd[row] = 1 / sqrt(var + eps), the same reduction as layernorm_kernel (mdg_row_rstd)
@@ -2000,6 +2050,7 @@ static int layernorm_impl(const float* x, int64_t ldx, const float* gamma, const
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int di = static_cast<int>(d);
   if (G) {
+    const dim3 grid(static_cast<unsigned>(mdg_cdiv(rows, 4 * kLogitRows)));
     if (d <= 256) hipLaunchKernelGGL(layernorm_logits_kernel<1>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
     else if (d <= 512) hipLaunchKernelGGL(layernorm_logits_kernel<2>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
     else if (d <= 1024) hipLaunchKernelGGL(layernorm_logits_kernel<4>, grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, rows, di, eps, hi, x3, G, H, logits);
@@ -2026,6 +2077,39 @@ extern "C" int mdg_layernorm_packed(const float* x, int64_t ldx, const float* ga
                                     int64_t d, float eps, int precision, void* y_packed, size_t y_packed_bytes, void* stream) {
   MDG_CHECK_ARG(y_packed, "mdg_layernorm_packed: null image");
   return layernorm_impl(x, ldx, gamma, beta, y, ldy, rows, d, eps, precision, y_packed, y_packed_bytes, stream);
+}
+
+// mdg_layernorm_packed without the fp32 rows and with a second, compact image of the rows that continue: row q_slot[r] of y_kept
+// (an image of n_keep rows) for every r whose slot lies in [0, n_keep).  y_packed is mdg_layernorm_packed's image bit for bit, and
+// y_kept is mdg_pack_operand of those rows of y, gathered in slot order.
+extern "C" int mdg_layernorm_packed_kept(const float* x, int64_t ldx, const float* gamma, const float* beta, int64_t rows, int64_t d, float eps,
+                                         int precision, void* y_packed, size_t y_packed_bytes, const int* q_slot, int64_t n_keep,
+                                         void* y_kept, size_t y_kept_bytes, void* stream) {
+  const char* who = "mdg_layernorm_packed_kept";
+  MDG_CHECK_ARG(rows >= 0 && d > 0 && n_keep >= 0 && n_keep < (1ll << 31), "%s: bad shape", who);
+  if (rows == 0) return MDG_OK;
+  MDG_CHECK_ARG(x && gamma && beta && y_packed && q_slot && (y_kept || n_keep == 0), "%s: null pointer", who);
+  MDG_CHECK_ARG(precision == MDG_PREC_BF16X3 || precision == MDG_PREC_BF16, "%s: a 16-bit operand mode", who);
+  MDG_CHECK_ARG(d % 64 == 0 && d <= 2048 && ldx % 4 == 0 && ldx >= d, "%s: d must be a multiple of 64 and <= 2048 (got %lld), ldx >= d", who,
+                (long long)d);
+  MDG_CHECK_ARG(mdg_aligned16(x) && mdg_aligned16(gamma) && mdg_aligned16(beta) && mdg_aligned16(y_packed) && mdg_aligned16(y_kept),
+                "%s: 16-byte alignment", who);
+  const size_t need = image_bytes(rows, d, precision), need_kept = image_bytes(n_keep, d, precision);
+  if (y_packed_bytes < need || y_kept_bytes < need_kept) {
+    mdg_set_error("%s: images of %zu and %zu bytes required, got %zu and %zu", who, need, need_kept, y_packed_bytes, y_kept_bytes);
+    return MDG_EWORKSPACE;
+  }
+  const dim3 grid(static_cast<unsigned>(mdg_cdiv(rows, 4)));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int di = static_cast<int>(d), x3 = precision == MDG_PREC_BF16X3 ? 1 : 0;
+  char* hi = static_cast<char*>(y_packed);
+  char* kept = static_cast<char*>(y_kept);
+  if (d <= 256) hipLaunchKernelGGL(layernorm_kept_kernel<1>, grid, dim3(256), 0, st, x, ldx, gamma, beta, rows, di, eps, hi, x3, q_slot, n_keep, kept);
+  else if (d <= 512) hipLaunchKernelGGL(layernorm_kept_kernel<2>, grid, dim3(256), 0, st, x, ldx, gamma, beta, rows, di, eps, hi, x3, q_slot, n_keep, kept);
+  else if (d <= 1024) hipLaunchKernelGGL(layernorm_kept_kernel<4>, grid, dim3(256), 0, st, x, ldx, gamma, beta, rows, di, eps, hi, x3, q_slot, n_keep, kept);
+  else hipLaunchKernelGGL(layernorm_kept_kernel<8>, grid, dim3(256), 0, st, x, ldx, gamma, beta, rows, di, eps, hi, x3, q_slot, n_keep, kept);
+  MDG_CHECK_LAUNCH(who);
+  return MDG_OK;
 }
 
 // mdg_layernorm / mdg_layernorm_packed that also writes logits[r, h] = LN(x)[r, :] . G[h, :] (G [H, d] fp32, H <= 64, logits [rows, H])

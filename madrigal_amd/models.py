@@ -1325,6 +1325,9 @@ class TransformerFusion(nn.Module):
         self.compose_layer0_attn = True
         # eval path: the x-attn pooling folded through V, out_proj and latent2embed (_x_attn_pool_folded); False: K|V block -> pool
         self.compose_pool = True
+        # eval path, pre-norm, a last layer behind another one: queries and attention rows for the kept rows only (_layer's ``kept``);
+        # False: queries scattered into a [R, 3d] block, attention over all R rows, the kept rows gathered from its output
+        self.compact_last_queries = True
 
     # ---- layer 0's QKV block with embed2latent and norm1 folded into its weights ---------------------
     def _qkv0(self, L, tokens, h):
@@ -1382,11 +1385,13 @@ class TransformerFusion(nn.Module):
         return ops.linear(ot, C, co, precision=prec, weight_image=C_img)
 
     # ---- one transformer layer on a set of token rows (dense or compact) --------------------
-    def _layer(self, L, h, attend, keep_rows=None, tokens=None):
+    def _layer(self, L, h, attend, keep_rows=None, tokens=None, kept=None):
         """``attend(qkv) -> attention output rows``; ``keep_rows`` (int64 index) prunes the rows that
         continue after the attention (last layer: only the pooled key tokens are ever read again).  ``tokens``: layer 0's input
         rows ahead of embed2latent, whose QKV block then comes from ``_qkv0`` (``attend`` sees no normalised rows); with ``h`` None the
-        whole attention block comes from them (``_layer0_tokenspace``)."""
+        whole attention block comes from them (``_layer0_tokenspace``).  ``kept`` = (q_slot, attend_kept(q, k, v) -> kept rows), with
+        ``keep_rows`` on a pre-norm layer: queries and attention outputs exist for the kept rows only, where the norm
+        writes an operand image and the rows are few enough for the split in_proj block."""
         sa = L.self_attn
 
         def norm(x, ln, want_fp32=True):
@@ -1415,13 +1420,25 @@ class TransformerFusion(nn.Module):
             if tokens is not None and h is None:
                 h = self._layer0_tokenspace(L, tokens, attend)
             else:
-                if tokens is not None:
-                    att = attend(self._qkv0(L, tokens, h), None)
+                imgs = None
+                if tokens is None and kept is not None and h.shape[0] >= 4 * keep_rows.numel() // 3:
+                    imgs = ops.layernorm_packed_kept(h, L.norm1.weight, L.norm1.bias, L.norm1.eps, _state["precision"], kept[0], keep_rows.numel())
+                if imgs is not None:
+                    # keys and values for all rows from the full image, queries from the kept rows' image, and an attention that
+                    # reads and writes the kept rows only: no query slot is left unwritten, no row is gathered or scattered
+                    w, b, d, prec = sa.in_proj_weight.detach(), sa.in_proj_bias.detach(), self.latent_dim, _state["precision"]
+                    kv = ops.linear_packed(imgs[0], h.shape[0], w[d:], b[d:], precision=prec)
+                    q = ops.linear_packed(imgs[1], keep_rows.numel(), w[:d], b[:d], precision=prec)
+                    att = kept[1](q, kv[:, :d], kv[:, d:])
+                    h = h.index_select(0, keep_rows)
                 else:
-                    a, a_img = norm(h, L.norm1)
-                    att = attend(in_proj(a, a_img), a)
-                if keep_rows is not None:
-                    att, h = att.index_select(0, keep_rows), h.index_select(0, keep_rows)
+                    if tokens is not None:
+                        att = attend(self._qkv0(L, tokens, h), None)
+                    else:
+                        a, a_img = norm(h, L.norm1)
+                        att = attend(in_proj(a, a_img), a)
+                    if keep_rows is not None:
+                        att, h = att.index_select(0, keep_rows), h.index_select(0, keep_rows)
                 h = _lin(att, sa.out_proj.weight, sa.out_proj.bias, residual=h)
             f, f_img = norm(h, L.norm2, want_fp32=False)
             u = lin_of(f, f_img, L.linear1.weight, L.linear1.bias, rows=h.shape[0], act=self.actn)
@@ -1678,7 +1695,16 @@ class TransformerFusion(nn.Module):
             plan["Tk"] = int(keys.numel())
         elif self.transformer_agg == 'cls':
             plan["key_rows"] = row_start[:-1].contiguous()
+        if "key_rows" in plan:
+            plan["q_slot"] = self._q_slot(plan["key_rows"], R)
         return plan
+
+    @staticmethod
+    def _q_slot(key_rows: torch.Tensor, R: int) -> torch.Tensor:
+        """The inverse of ``key_rows`` over the R live rows, int32: the position of a kept row in ``key_rows``, -1 for any other row."""
+        q_slot = torch.full((R,), -1, dtype=torch.int32, device=key_rows.device)
+        q_slot[key_rows] = torch.arange(key_rows.numel(), dtype=torch.int32, device=key_rows.device)
+        return q_slot
 
     def merged_live_plan(self, a: dict, b: dict) -> dict:
         """The live-token plan of two batches laid one after the other (``a``'s drugs and token rows first): one transformer pass
@@ -1696,6 +1722,7 @@ class TransformerFusion(nn.Module):
              "row_bits": torch.cat([a["row_bits"], b["row_bits"]]).contiguous()}
         if "key_rows" in a:
             m["key_rows"] = torch.cat([a["key_rows"], b["key_rows"] + Ra]).contiguous()
+            m["q_slot"] = self._q_slot(m["key_rows"], m["R"])
         if "Tk" in a:
             m["Tk"] = a["Tk"]
         self.__dict__["_merged_plan"] = (key, m, a, b)          # (holds a and b: their ids cannot be recycled meanwhile)
@@ -1720,11 +1747,16 @@ class TransformerFusion(nn.Module):
                 return ops.fusion_attention_qkv(q, k, v, plan["n_tiles"], S, H, w, w, hq=w, hk=0, hv=0, out=out, ho=w,
                                                 row_start=plan["tile_start"], row_bits=plan["row_bits"])
             return ops.fusion_attention(qkv, plan["n_tiles"], S, H, dh, row_start=plan["tile_start"], row_bits=plan["row_bits"])[0]
+
+        def attend_kept(q, k, v):
+            return ops.fusion_attention_kept(q, k, v, plan["n_tiles"], H, dh, plan["tile_start"], plan["row_bits"], plan["q_slot"])
         for li, L in enumerate(layers):
             last = li == len(layers) - 1
             keep = plan.get("key_rows") if (last and agg in ('x-attn', 'cls')) else None
             compose = li == 0 and self.compose_layer0 and keep is None            # (a last layer 0 with kept rows: queries of those only)
-            h = self._layer(L, h, attend, keep_rows=keep, tokens=tokens if compose else None)
+            # a last layer behind another one: its queries and attention rows are formed for the kept rows only
+            kept = (plan["q_slot"], attend_kept) if (keep is not None and li > 0 and self.compact_last_queries and "q_slot" in plan) else None
+            h = self._layer(L, h, attend, keep_rows=keep, tokens=tokens if compose else None, kept=kept)
         self.last_attention_weights = None
         if agg == 'x-attn':
             return self._x_attn_pool(h, n, plan["Tk"])

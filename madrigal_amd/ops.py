@@ -1289,6 +1289,29 @@ def layernorm_packed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     return y, img
 
 
+def layernorm_packed_kept(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, precision, q_slot: torch.Tensor, n_keep: int):
+    """``layernorm_packed(.., want_fp32=False)`` of a 2-D ``x`` [R, d] whose kernel writes the rows that continue a second time, as a compact
+    image of ``n_keep`` rows -> (image, kept_image).  ``q_slot`` [R] int32: the compact index of a kept row, negative elsewhere;
+    ``kept_image`` is ``pack_operand`` of the kept fp32 rows in slot order, bit for bit.  None where the arithmetic mode or the width takes
+    no image (the caller keeps its other path)."""
+    forward_only(x, weight, bias)
+    x2 = x if (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.is_cuda and x.dtype == torch.float32) else _rows2d(x, "x")[0]
+    R, d = x2.shape
+    prec = _prec(precision)
+    if prec == PREC_F32 or d % 64 or R == 0:
+        return None
+    if not (q_slot.is_cuda and q_slot.dtype == torch.int32 and q_slot.dim() == 1 and q_slot.numel() == R and q_slot.is_contiguous()
+            and q_slot.device == x2.device):
+        raise ValueError(f"q_slot: expected a contiguous int32 cuda [{R}] on {x2.device}")
+    n_keep = int(n_keep)
+    nbytes, kbytes = lib().mdg_pack_operand_bytes(R, d, prec), lib().mdg_pack_operand_bytes(n_keep, d, prec)
+    img = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
+    kept = torch.empty(kbytes, dtype=torch.uint8, device=x2.device)
+    call("mdg_layernorm_packed_kept", _ptr(x2), x2.stride(0), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()), R, d, eps,
+         prec, _ptr(img), nbytes, _ptr(q_slot), n_keep, _ptr(kept), kbytes, _stream(x2))
+    return img, kept
+
+
 def layernorm_logits(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, G: torch.Tensor, precision):
     """``layernorm_packed`` of a 2-D ``x`` [R, d] plus logits [R, H] = LN(x) G^T, formed from the normalised fp32 rows inside the
     norm kernel (G [H, d] fp32, H <= 64) -> (y, image, logits).  As in ``layernorm_packed(.., want_fp32=False)``: y is None when the
@@ -1488,6 +1511,32 @@ def fusion_attention_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: i
         raise ValueError("out: give its head step ho, and columns for H heads of it")
     call("mdg_fusion_attention_qkv", _ptr(q), q.stride(0), hq, _ptr(k), k.stride(0), hk, _ptr(v), v.stride(0), hv, _ptr(out), out.stride(0), ho,
          _ptr(kpm_bits), _ptr(src_bits), _ptr(row_start), _ptr(row_bits), n, S, H, ds, dv, qscale, _stream(q))
+    return out
+
+
+def fusion_attention_kept(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n_tiles: int, H: int, dh: int, row_start: torch.Tensor,
+                          row_bits: Optional[torch.Tensor], q_slot: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Compact-mode ``fusion_attention`` where only the kept rows have a query and an output: ``q`` [n_keep, H*dh] and the result
+    [n_keep, H*dh] hold the kept rows in slot order, ``k`` / ``v`` are [R, H*dh] views of one row stride (e.g. the halves of a K|V
+    block), ``q_slot`` [R] int32 gives a kept row's slot and is negative elsewhere.  Row ``q_slot[r]`` of the result equals row r of
+    ``fusion_attention``'s, bit for bit; the queries of the other rows are never read."""
+    forward_only(q, k, v)
+    d, R, n_keep = H * dh, k.shape[0], q.shape[0]
+    for nm, t, rows in (("q", q, n_keep), ("k", k, R), ("v", v, R)) + ((("out", out, n_keep),) if out is not None else ()):
+        if t.dim() != 2 or t.shape != (rows, d) or t.stride(1) != 1 or t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f"{nm}: expected an fp32 cuda [{rows},{d}] tensor with unit inner stride")
+    if R and k.stride(0) != v.stride(0):
+        raise ValueError("k and v: one row stride for both")
+    if row_start.dtype != torch.int64 or row_start.numel() != n_tiles + 1 or not row_start.is_contiguous():
+        raise ValueError("row_start: contiguous int64 [n_tiles+1]")
+    if q_slot.dtype != torch.int32 or q_slot.dim() != 1 or q_slot.numel() != R or not q_slot.is_contiguous() or not q_slot.is_cuda:
+        raise ValueError(f"q_slot: expected a contiguous int32 cuda [{R}]")
+    if row_bits is not None and (row_bits.numel() != R or not row_bits.is_contiguous()):
+        raise ValueError(f"row_bits: expected a contiguous [{R}]")
+    if out is None:
+        out = torch.empty((n_keep, d), dtype=torch.float32, device=q.device)
+    call("mdg_fusion_attention_kept", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(out), out.stride(0), _ptr(row_start),
+         _ptr(row_bits), _ptr(q_slot), n_keep, n_tiles, H, dh, _stream(k))
     return out
 
 

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Steady-state launch census per step of the three timed loops (run on the GPU box):  bash scripts/profile_steady.sh <outdir> <round tag>
+# Steady-state launch census per step of the three timed loops (run on the GPU box):  bash scripts/profile_steady.sh <outdir> <round tag> [loops]
+# (loops: the loops to trace, e.g. "inference" or "inference finetune"; default all three)
 # For each loop two rocprofv3 traces (kernels + memory copies) with 8 and 24 steps and no warm-up; their difference / 16 is one
 # steady-state step (scripts/steady_state_stats.py): own kernels, torch / rocBLAS / rocprim kernels, copies and fills per step.
 #   inference step   bench.py headline (encode+fuse 4096 drugs, score 4096^2 x 896)
@@ -7,11 +8,13 @@
 #   contrastive step scripts/pretrain_bench.py (batch 2048)
 export TMPDIR=/tmp
 out=gpurun_out/$1; tag=$2
+loops=${3:-inference finetune contrastive}
 mkdir -p $out profiles
 run() {   # name, command...
   name=$1; shift
   for n in 8 24; do
-    rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $out/$name$n -- "$@" --steps $n --warmup 0 > $out/$name$n.log 2>&1
+    timeout -k 10 ${STEP_TIMEOUT:-600} rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $out/$name$n -- "$@" --steps $n --warmup 0 > $out/$name$n.log 2>&1 \
+      || { echo "$name, $n steps: the trace ended with status $?; nothing more is started"; tail -n 20 $out/$name$n.log; exit 1; }
     cp "$(find $out/$name$n -name '*kernel_stats.csv' | head -n 1)" $out/${name}_stats$n.csv
     cp "$(find $out/$name$n -name '*memory_copy_stats.csv' | head -n 1)" $out/${name}_copies$n.csv 2>/dev/null
   done
@@ -41,7 +44,8 @@ with open(f"profiles/{tag}_{name}_launch_census.txt", "w") as f:
 print(open(f"profiles/{tag}_{name}_launch_census.txt").read()[:1500])
 PY
 }
-run inference python3 bench.py --no-cpu-baseline --finetune-steps 0 --pretrain-steps 0 --stress-drugs 0 --rank-outcomes 0 --no-f32-exact
-run finetune python3 scripts/train_bench.py --precision bf16
-run contrastive python3 scripts/pretrain_bench.py
+want() { case " $loops " in *" $1 "*) return 0;; esac; return 1; }
+want inference && run inference python3 bench.py --no-cpu-baseline --finetune-steps 0 --pretrain-steps 0 --stress-drugs 0 --rank-outcomes 0 --no-f32-exact
+want finetune && run finetune python3 scripts/train_bench.py --precision bf16
+want contrastive && run contrastive python3 scripts/pretrain_bench.py
 cp profiles/${tag}_* $out/ 2>/dev/null
