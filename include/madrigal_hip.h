@@ -207,6 +207,43 @@ int mdg_bilinear_ensemble_select_fill(const float* const* z_head, const float* c
                                       int64_t n_tail, int64_t n_labels, int64_t D, int precision, int eligible, void* workspace,
                                       size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
 
+/* Per-outcome probability counts of the checkpoint ensemble (ABI 28): for every outcome l, given n_edges ascending finite fp32 edges
+ * e[l,0..B-1],
+ *   counts[l,b] = #{eligible (i,j) : e[l,b-1] <= P[l,i,j] < e[l,b]},   e[l,-1] = -inf, e[l,B] = +inf        (b = 0..B)
+ *   P[l,i,j]    = mean_m sigmoid(z_head_m[i]^T W_sym_m[l] z_tail_m[j])
+ * -- torch.bucketize(P, e[l], right=True) followed by a bincount, without materialising [L,N,N]: mdg_bilinear_bincount's contract on
+ * the probability get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) average
+ * over the checkpoints.  With the edges at the probabilities of screened hits (mdg_bilinear_ensemble_topk / _select_fill return
+ * exactly these values) the cumulative counts are the hits' exact normalised ranks among all pairs, the quantity
+ * notebooks/normalize_scores.py:36-74 computes by ranking the stored lower triangle; with evenly spaced edges they are histograms
+ * of the ensemble's probabilities.  The mean of sigmoids is not monotone in any one model's logit, so no combination of
+ * mdg_bilinear_bincount results gives these counts.
+ *   Operands as mdg_bilinear_ensemble_select_count (HOST arrays of n_models = 1..8 device pointers, 16-byte aligned, D == 128);
+ *   precision MDG_PREC_F32 or MDG_PREC_BF16X3.  P is bit for bit what mdg_bilinear_ensemble_sigmoid's general sweep writes; the
+ *   compares are on the quotient, e <= P.
+ *   edges [n_labels,n_edges] fp32, device; counts [n_labels,n_edges+1] int64, zeroed by the call on `stream`; every row of counts
+ *   sums to the number of eligible pairs.  Equal neighbouring edges give an empty bin; unsorted edges give unspecified counts (no
+ *   out-of-bounds access).  A NaN probability is counted nowhere.
+ *   1 <= n_edges <= mdg_bilinear_bincount_max_edges(); n_labels <= 65535 per call; eligible as mdg_bilinear_topk (NOT_SELF / LOWER
+ *   need n_head == n_tail); n_tail < 2^23, as mdg_bilinear_bincount: a workgroup counts its 128 x n_tail probabilities in 32-bit
+ *   counters.  n_head == 0 or n_labels == 0: MDG_OK, nothing launched, the counts zeroed where the pointer is not null.
+ *   mdg_bilinear_ensemble_bincount_split: the arguments above plus `mask` / `plane_stride` (the rules of the *_masked entry points
+ *   below) and counts int64 [2][n_labels][n_edges+1]: table 0 the eligible pairs whose bit is CLEAR, table 1 those whose bit is
+ *   SET; a pair `eligible` or the bounds rule out is in neither, whatever its bit.  Nothing is excluded: the two tables sum to the
+ *   unsplit counts exactly.  mask == NULL: table 0 is the unsplit result, table 1 zero, and no mask memory is read.
+ *   Workspace: the size mdg_bilinear_ensemble_sigmoid_workspace_bytes gives (0 for F32).
+ * Deterministic: the workgroups add their counts into `counts` with integer atomics, so the sums are bit-identical from launch to
+ * launch. */
+size_t mdg_bilinear_ensemble_bincount_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_models,
+                                                      int precision);
+int mdg_bilinear_ensemble_bincount(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                                   const float* edges, int64_t* counts, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D,
+                                   int n_edges, int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream);
+int mdg_bilinear_ensemble_bincount_split(const float* const* z_head, const float* const* z_tail, const float* const* w_sym,
+                                         int n_models, const float* edges, int64_t* counts, int64_t n_head, int64_t n_tail,
+                                         int64_t n_labels, int64_t D, int n_edges, int precision, int eligible, void* workspace,
+                                         size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
+
 /* Per-row top-k of the all-pairs sweep: for every outcome l and head row i the k largest scores S[l,i,j] (the arithmetic of
  * mdg_bilinear_allpairs' general sweep in `precision`, bit for bit in F32 / BF16X3; the 16-bit modes run the row-statistics
  * sweep, whose fp32 sums are grouped differently: <= 2e-6 of the scale) over the ELIGIBLE tail columns j, and those columns.

@@ -992,6 +992,94 @@ def bilinear_ensemble_select(z_heads, z_tails, w_syms, thresholds: torch.Tensor,
     return row_ptr, cols, vals
 
 
+def bilinear_ensemble_bincount(z_heads, z_tails, w_syms, edges: torch.Tensor, *, eligible: str = "all", precision="bf16x3",
+                               split: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-outcome counts of the checkpoint ensemble's probabilities between edges -> int64 [L, B+1]: with ``edges`` [L, B] fp32,
+    finite and ascending per outcome, ``counts[l, b]`` is the number of eligible pairs (i, j) with ``edges[l, b-1] <= P[l,i,j] <
+    edges[l, b]`` (``edges[l, -1] = -inf``, ``edges[l, B] = +inf``), P[l,i,j] = mean_m sigmoid(z_heads[m][i]^T w_syms[m][l]
+    z_tails[m][j]): ``torch.bucketize(P[l], edges[l], right=True)`` followed by a bincount, counted inside the ensemble's all-pairs
+    sweep with nothing of [L,Nh,Nt] materialised (madrigal/evaluate/predict.py:466-499, 582-614 average the sigmoids;
+    notebooks/normalize_scores.py:36-74 ranks that tensor).  Equal neighbouring edges give an empty bin; every row sums to the number
+    of eligible pairs.  The mean of K sigmoids is not monotone in any one model's logit, so no combination of ``bilinear_bincount``
+    results per model gives these counts.
+
+    K = len(z_heads) in 1..8; P is bit for bit ``bilinear_ensemble_sigmoid``'s general sweep in ``precision`` ("f32" or "bf16x3"),
+    the value ``bilinear_ensemble_topk`` and ``bilinear_ensemble_select`` return, so their values can serve as edges.  ``eligible``
+    as ``bilinear_topk``; ``1 <= B <= bilinear_bincount_max_edges()``; Nt < 2^23.  Integer sums: bit-identical from launch to launch.
+
+    ``split``: a mask from ``pair_mask`` (``[1, ...]`` shared by all outcomes or ``[L, ...]``, one plane per outcome) -> int64
+    [2, L, B+1]: the same sweep with the two classes counted separately -- ``[0]`` the eligible pairs whose bit is clear, ``[1]``
+    those whose bit is set (the known pairs); a bit of an ineligible pair changes nothing.  Nothing is excluded: ``result.sum(0)`` is
+    the call without ``split``, exactly."""
+    what = "bilinear_ensemble_bincount"
+    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
+    K = len(zh)
+    if not 1 <= K <= 8:
+        raise ValueError(f"{what}: 1..8 models, got {K}")
+    if len(zt) != K or len(ws) != K:
+        raise ValueError(f"{what}: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
+    if precision not in ENSEMBLE_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    # shapes and edge values first (on whatever device the tensors live), then the device: a bad call says what is wrong with it
+    for t, name, nd in ((zh[0], "z_heads[0]", 2), (zt[0], "z_tails[0]", 2), (ws[0], "w_syms[0]", 3), (edges, "edges", 2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    forward_only(*zh, *zt, *ws, edges)
+    L, D = ws[0].shape[0], ws[0].shape[1]
+    Nh, Nt, B = zh[0].shape[0], zt[0].shape[0], edges.shape[1]
+    for m in range(K):
+        if tuple(zh[m].shape) != (Nh, D) or tuple(zt[m].shape) != (Nt, D) or tuple(ws[m].shape) != (L, D, D):
+            raise ValueError(f"{what}: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
+                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+    max_edges = bilinear_bincount_max_edges()
+    if edges.shape[0] != L:
+        raise ValueError(f"edges: expected [{L}, B] (one row per outcome), got {tuple(edges.shape)}")
+    if not 1 <= B <= max_edges:
+        raise ValueError(f"edges: expected 1..{max_edges} edges per outcome, got {B}")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    if Nt >= 1 << 23:
+        raise ValueError(f"z_tails: {Nt} rows; the 32-bit workgroup counters hold fewer than 2^23")
+    if L and not bool(torch.isfinite(edges).all()):
+        raise ValueError("edges: must be finite")
+    if L and not bool((edges[:, 1:] >= edges[:, :-1]).all()):
+        raise ValueError("edges: must be ascending within every outcome (unsorted edges give unspecified counts)")
+    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
+    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
+    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
+    e = _f32_cuda(edges, "edges", 2)
+    dev = zh[0].device
+    if any(t.device != dev for t in (*zh, *zt, *ws, e)):
+        raise ValueError(f"{what}: every tensor must be on the same device")
+    prec = ENSEMBLE_PRECISIONS[precision]
+    mask, mstride = _exclude_args(split, zh[0], Nh, Nt, L)
+    tables = () if split is None else (2,)
+    counts = torch.empty((*tables, L, B + 1), dtype=torch.int64, device=dev)
+    if counts.numel() == 0:
+        return counts
+    if Nh == 0 or Nt == 0:                       # no pair at all
+        return counts.zero_()
+    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
+    a_h, a_t = arr(zh), arr(zt)
+    for lo in range(0, L, 65535):                # the grid's y extent caps one call at 65535 outcomes
+        hi = min(L, lo + 65535)
+        wsp, nbytes = _scratch("mdg_bilinear_ensemble_bincount_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
+        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
+        if split is None:
+            call("mdg_bilinear_ensemble_bincount", a_h, a_t, a_w, K, e.data_ptr() + lo * B * 4, counts.data_ptr() + lo * (B + 1) * 8, Nh, Nt,
+                 hi - lo, D, B, prec, TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]))
+            continue
+        part = counts if hi - lo == L else torch.empty((2, hi - lo, B + 1), dtype=torch.int64, device=dev)   # [2][this call's outcomes]
+        call("mdg_bilinear_ensemble_bincount_split", a_h, a_t, a_w, K, e.data_ptr() + lo * B * 4, _ptr(part), Nh, Nt, hi - lo, D, B, prec,
+             TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]), mask.data_ptr() + lo * mstride * 4, mstride)
+        if part is not counts:
+            counts[:, lo:hi] = part
+    return counts
+
+
 def empty_scores(L: int, Nh: int, Nt: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """An uninitialised [L,Nh,Nt] fp32 score (or rank) tensor in the layout the head writes fastest: rows padded to a multiple of
     32 floats, so that every row starts on a 128-byte line whatever Nt is (the real drug counts -- 11 607 in

@@ -519,9 +519,22 @@ def _count_below(model, z, scores, label_range, known):
     s = torch.as_tensor(scores, dtype=torch.float32, device=z.device)
     if s.dim() != 2 or s.shape[0] != hi - lo:
         raise ValueError(f"scores: expected [{hi - lo}, Q], got {tuple(s.shape)}")
-    L, Q = s.shape
     split = _exclusion(known, model)
-    less = torch.zeros((L, Q) if split is None else (2, L, Q), dtype=torch.int64, device=z.device)
+
+    def counting(edges):
+        if split is None:
+            return model.decoder.bincount(z, z, edges, (lo, hi), eligible="lower")
+        return model.decoder.bincount(z, z, edges, (lo, hi), eligible="lower", split=split)
+
+    return _count_below_sweeps(counting, s, split is not None)
+
+
+def _count_below_sweeps(counting, s: torch.Tensor, split: bool):
+    """The sort / dedup / chunk / scatter of ``count_below`` and ``ensemble_count_below`` around a counting sweep: ``counting(edges)``
+    -> the lower-triangle counts int64 [L', B+1] (``split``: [2, L', B+1]) of contiguous fp32 ``edges`` [L', B], B <=
+    ``ops.bilinear_bincount_max_edges()``.  ``s``: the queries, fp32 [L', Q] on the sweep's device -> (less, totals) as ``_count_below``."""
+    L, Q = s.shape
+    less = torch.zeros((2, L, Q) if split else (L, Q), dtype=torch.int64, device=s.device)
     if L == 0 or Q == 0:
         return less, None
     if not bool(torch.isfinite(s).all()):
@@ -533,18 +546,15 @@ def _count_below(model, z, scores, label_range, known):
     U = int(pos.max()) + 1
     uniq = sv[:, -1:].expand(L, U).clone()                      # outcomes with fewer distinct values: the largest one repeated (empty bins)
     uniq.scatter_(1, pos, sv)
-    below = torch.empty(less.shape[:-1] + (U,), dtype=torch.int64, device=z.device)
+    below = torch.empty(less.shape[:-1] + (U,), dtype=torch.int64, device=s.device)
     step = ops.bilinear_bincount_max_edges()
     totals = None
     for c0 in range(0, U, step):
         c1 = min(U, c0 + step)
-        if split is None:
-            counts = model.decoder.bincount(z, z, uniq[:, c0:c1].contiguous(), (lo, hi), eligible="lower")
-        else:
-            counts = model.decoder.bincount(z, z, uniq[:, c0:c1].contiguous(), (lo, hi), eligible="lower", split=split)
+        counts = counting(uniq[:, c0:c1].contiguous())
         below[..., c0:c1] = torch.cumsum(counts, -1)[..., : c1 - c0]
         totals = counts.sum(-1) if totals is None else totals
-    if split is None:
+    if not split:
         less.scatter_(1, order, torch.gather(below, 1, pos))
     else:
         less.scatter_(2, order.expand(2, -1, -1), torch.gather(below, 2, pos.expand(2, -1, -1)))
@@ -1217,7 +1227,7 @@ def ensemble_partner_counts(models, zs, thresholds, label_range: Optional[Tuple[
     ``thresholds``: a PROBABILITY cut, a number such as 0.9 or [L'] (no NaN), e.g. ``ensemble_top_pairs(models, zs, K)[0][:, -1]``;
     the rule is ``>=``, so ties with the K-th pair are counted, and at saturated inputs many probabilities are exactly 1.0.  A cut on
     the ensemble's probability needs no calibration per outcome, unlike a cut on one model's logit.  Normalised ranks under the
-    ensemble are not part of this.  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as
+    ensemble: ``ensemble_normalized_ranks_of``.  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as
     ``partner_counts``; ``max_bytes`` is accepted for symmetry with ``ensemble_partners_above`` (the result is 4 L' N bytes)."""
     zs, ws, thr, prec, excl, _ = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_partner_counts")
     return ops.bilinear_ensemble_select_count(zs, zs, ws, thr, eligible="not_self", precision=prec, exclude=excl)
@@ -1235,8 +1245,8 @@ def ensemble_partners_above(models, zs, thresholds, label_range: Optional[Tuple[
 
     ``thresholds``: a PROBABILITY cut, a number such as 0.9 or [L'] (no NaN), e.g. ``ensemble_top_pairs(models, zs, K)[0][:, -1]``;
     the rule is ``>=``, so ties with the K-th pair are included, and at saturated inputs many probabilities are exactly 1.0.
-    Normalised ranks under the ensemble are not part of this.  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``;
-    ``exclude`` as ``partners_above``."""
+    Normalised ranks under the ensemble: ``ensemble_normalized_ranks_of``.  ``models`` / ``zs`` / ``label_range`` as
+    ``ensemble_top_partners``; ``exclude`` as ``partners_above``."""
     zs, ws, thr, prec, excl, _ = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_partners_above")
     return ops.bilinear_ensemble_select(zs, zs, ws, thr, eligible="not_self", precision=prec, max_bytes=max_bytes, exclude=excl)
 
@@ -1258,7 +1268,7 @@ def ensemble_pairs_above(models, zs, thresholds, label_range: Optional[Tuple[int
       * the K-th value of ``ensemble_top_pairs``: ``ensemble_pairs_above(models, zs, ensemble_top_pairs(models, zs, K)[0][:, -1])``
         holds those K pairs and every pair tied with the last of them (the rule is ``>=``).  At saturated inputs many probabilities
         are exactly 1.0, so such a tie set can be large: ``max_bytes`` bounds it.
-    Normalised ranks under the ensemble are not part of this (``normalized_ranks_of`` ranks one model's scores).
+    The returned probabilities can go straight into ``ensemble_normalized_ranks_of`` (``normalized_ranks_of`` ranks one model's scores).
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as ``pairs_above``."""
     zs, ws, thr, prec, excl, n_out = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_pairs_above")
     row_ptr, cols, vals = ops.bilinear_ensemble_select(zs, zs, ws, thr, eligible="lower", precision=prec, max_bytes=max_bytes, exclude=excl)
@@ -1267,3 +1277,121 @@ def ensemble_pairs_above(models, zs, thresholds, label_range: Optional[Tuple[int
     if N == 0:
         offsets = torch.zeros(n_out + 1, dtype=torch.int64, device=zs[0].device)
     return offsets, head, cols.long(), vals
+
+
+def _known_mask(known, required: bool) -> None:
+    """The cheap part of the check of ``known=``, ahead of the operands; ``_ensemble_exclusion`` checks the planes against the head."""
+    if known is None and not required:
+        return
+    if not isinstance(known, torch.Tensor) or known.dim() != 3:
+        raise ValueError("known: expected a mask from known_pairs_mask")
+
+
+def _ensemble_counting(models, zs, label_range, known, eligible: str, what: str):
+    """Checked operands of the ensemble's counting products -> (counting, n_out, device): ``counting(edges)`` is
+    ``ops.bilinear_ensemble_bincount`` of contiguous fp32 ``edges`` [L', B] over the outcomes of ``label_range``, int64 [L', B+1], or
+    [2, L', B+1] split by ``known``."""
+    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, what)
+    split = _planes(_ensemble_exclusion(known, L_all), lo, hi)
+
+    def counting(edges):
+        return ops.bilinear_ensemble_bincount(zs, zs, ws, edges, eligible=eligible, precision=prec, split=split)
+
+    return counting, hi - lo, zs[0].device
+
+
+@torch.no_grad()
+def ensemble_score_histogram(models, zs, edges: torch.Tensor, label_range: Optional[Tuple[int, int]] = None, eligible: str = "lower",
+                             known: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``score_histogram`` over a checkpoint ensemble -> int64 [L', B+1]: ``counts[l, b]`` is the number of eligible pairs whose
+    mean probability P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) -- the value get_twosides_scores_wrapper / get_drugbank_scores_wrapper
+    (madrigal/evaluate/predict.py:466-499, 582-614) predict from -- lies in ``[edges[l, b-1], edges[l, b])`` (-inf below the first
+    edge, +inf above the last), counted inside the ensemble's sweep (``ops.bilinear_ensemble_bincount``): no [L', N, N] tensor at any
+    N.  ``edges``: ``[B]`` shared by all outcomes or ``[L', B]``, fp32 PROBABILITIES, finite and ascending, 1 <= B <=
+    ``ops.bilinear_bincount_max_edges()``; ``eligible`` as ``score_histogram``.  Cumulative sums of a row are the distribution
+    function of the outcome's probabilities at the edges, from which quantiles follow.  Saturated probabilities tie exactly (many
+    are exactly 1.0): an edge at 1.0 puts that whole tie group into the last bin.
+    ``known``: a ``known_pairs_mask`` -> int64 [2, L', B+1]: the novel pairs (``[0]``) and the known pairs (``[1]``) counted
+    separately in the same sweep; ``result.sum(0)`` is the histogram without ``known``.
+    Edges taken from ``ensemble_top_pairs`` / ``ensemble_pairs_above`` can be fed straight in (the same arithmetic, bit for bit): the
+    cumulative counts below such an edge are that pair's rank, the lowest of its tie group (``ensemble_normalized_ranks_of``; not
+    ``ensemble_pair_ranks``, which is the geometric mean of per-model ranks).
+    ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``.  Multi-GPU: pass the rank's outcome shard as ``label_range``."""
+    _known_mask(known, False)
+    counting, n_out, dev = _ensemble_counting(models, zs, label_range, known, eligible, "ensemble_score_histogram")
+    e = torch.as_tensor(edges, dtype=torch.float32, device=dev)
+    if e.dim() == 1:
+        e = e[None, :].expand(n_out, -1)
+    if e.dim() != 2 or e.shape[0] != n_out:
+        raise ValueError(f"edges: expected [B] or [{n_out}, B], got {tuple(e.shape)}")
+    return counting(e.contiguous())
+
+
+def _ensemble_count_below(models, zs, probs, label_range, known, what: str):
+    counting, n_out, dev = _ensemble_counting(models, zs, label_range, known, "lower", what)
+    s = torch.as_tensor(probs, dtype=torch.float32, device=dev)
+    if s.dim() != 2 or s.shape[0] != n_out:
+        raise ValueError(f"probs: expected [{n_out}, Q], got {tuple(s.shape)}")
+    return _count_below_sweeps(counting, s, known is not None)
+
+
+@torch.no_grad()
+def ensemble_count_below(models, zs, probs: torch.Tensor, label_range: Optional[Tuple[int, int]] = None,
+                         known: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``count_below`` over a checkpoint ensemble -> int64 [L', Q]: for every query ``probs[l, q]`` the number of
+    strict-lower-triangle pairs (i > j) of outcome l whose mean probability P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) is strictly
+    less.  Any Q; the queries may be unsorted and repeated: per outcome they are sorted and deduplicated and the counting sweep
+    (``ops.bilinear_ensemble_bincount``, lower-triangle mode) runs once per chunk of at most ``ops.bilinear_bincount_max_edges()``
+    distinct values, exactly as ``count_below`` does around the single-model sweep.  Strictly less: a query that ties with many
+    pairs -- saturated probabilities are exactly 1.0 -- counts none of its tie group.
+    The probabilities ``ensemble_top_pairs`` / ``ensemble_pairs_above`` return can be fed straight in: they come from the same
+    arithmetic, bit for bit, so a pair is never counted below itself.  The counts are over the MEAN probability; ``ensemble_pair_ranks``
+    is a different quantity, the geometric mean of every checkpoint's own rank of the pair.
+    ``known``: a ``known_pairs_mask`` -> int64 [2, L', Q]: the novel (``[0]``) and the known pairs (``[1]``) below every query.
+    ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``."""
+    _known_mask(known, False)
+    return _ensemble_count_below(models, zs, probs, label_range, known, "ensemble_count_below")[0]
+
+
+@torch.no_grad()
+def ensemble_normalized_ranks_of(models, zs, probs: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """The normalised rank of the ensemble probabilities ``probs[l, q]`` within their outcomes -> float32 [L', Q]: where a pair with
+    mean probability ``probs[l, q]`` sits among all N (N - 1) / 2 pairs ranked by P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) -- the
+    value notebooks/normalize_scores.py:36-74 computes from the stored ensemble tensor -- without that tensor or its sort:
+    ``ranks_from_counts(ensemble_count_below(...), N)``.
+
+    Tie rule: for a probability shared by several pairs this is the LOWEST rank of the tie group, and exact ties are the rule for
+    saturated probabilities (at N(0,1) inputs about 7 % of one model's probabilities are exactly 1.0): all of them get the rank of
+    the first of them.
+    This is NOT ``ensemble_pair_ranks``: that is the geometric mean of every checkpoint's own rank of the pair; this is the rank of
+    the mean probability.  The two orderings differ, because the mean of sigmoids is not monotone in any one model's score.
+    The values ``ensemble_top_pairs`` / ``ensemble_pairs_above`` return can be fed straight in (the same arithmetic, bit for bit)."""
+    zs = list(zs)
+    less = ensemble_count_below(models, zs, probs, label_range)
+    return ranks_from_counts(less, zs[0].shape[0])
+
+
+@torch.no_grad()
+def ensemble_recovery_at_cuts(models, zs, known: torch.Tensor, cuts: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> dict:
+    """``recovery_at_cuts`` over a checkpoint ensemble -> the dict of ``recovery_from_counts``, every entry [L', B]: for each
+    PROBABILITY cut ``cuts[l, b]`` (any order, repeats allowed) the strict-lower-triangle pairs the ensemble rates at or above it
+    (``selected``, P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) >= cut), the known ones among them (``hits``) and the exact precision,
+    recall and enrichment over all N (N - 1) / 2 pairs, with no [L', N, N] tensor.  ``known``: a ``known_pairs_mask``; the class
+    sizes are read from the same sweeps.  The rule is ``>=`` and ties are exact: a cut at 1.0 selects the whole saturated tie group.
+    Cuts taken from ``ensemble_top_pairs`` / ``ensemble_pairs_above`` can be fed straight in (the same arithmetic, bit for bit)."""
+    _known_mask(known, True)
+    less, totals = _ensemble_count_below(models, zs, cuts, label_range, known, "ensemble_recovery_at_cuts")
+    if totals is None:                                          # no outcome or no cut: nothing was swept
+        totals = torch.zeros((2, less.shape[1]), dtype=torch.int64, device=less.device)
+    return recovery_from_counts(less[0] + less[1], less[1], (totals[0] + totals[1])[:, None], totals[1][:, None])
+
+
+@torch.no_grad()
+def ensemble_auroc_bounds(models, zs, known: torch.Tensor, edges: torch.Tensor, label_range: Optional[Tuple[int, int]] = None):
+    """``auroc_bounds`` over a checkpoint ensemble -> ``(lower, upper)`` float64 [L']: bounds on the AUROC of ranking ALL
+    strict-lower-triangle pairs by the mean probability P[l, i, j] = mean_m sigmoid(S_m[l, i, j]) against the known network:
+    ``ensemble_score_histogram(known=)`` followed by ``auroc_bounds_from_counts`` -- one sweep, no sampled negatives.  Pairs that
+    share a bin count towards the gap between the bounds; exactly tied probabilities (the saturated group at 1.0) share a bin
+    whatever the edges, and the exact AUROC counts them 1/2, inside the interval."""
+    _known_mask(known, True)
+    return auroc_bounds_from_counts(ensemble_score_histogram(models, zs, edges, label_range, eligible="lower", known=known))
