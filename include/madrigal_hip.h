@@ -244,6 +244,39 @@ int mdg_bilinear_ensemble_bincount_split(const float* const* z_head, const float
                                          int64_t n_labels, int64_t D, int n_edges, int precision, int eligible, void* workspace,
                                          size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
 
+/* Per-pair outcome profiles of the checkpoint ensemble (ABI 29): for every eligible pair (i,j), over the n_labels outcomes of the call,
+ *   P[l,i,j]    = mean_m sigmoid(z_head_m[i]^T W_sym_m[l] z_tail_m[j])
+ *   count[i,j]  = #{l : P[l,i,j] >= thr[l]}                      (the compare is on the quotient, as mdg_bilinear_ensemble_select_*)
+ *   margin[i,j] = max_l u_l,  u_l = (P[l,i,j] - thr[l]) * scale[l]  (a subtract, then a multiply, each rounded to fp32; scale == NULL: ones)
+ *   best[i,j]   = the lowest l attaining that maximum
+ * -- mdg_bilinear_profile's contract on the probability get_twosides_scores_wrapper / get_drugbank_scores_wrapper
+ * (madrigal/evaluate/predict.py:466-499, 582-614) average over the checkpoints: "for how many interaction types does the five-seed
+ * ensemble flag the pair at P >= 0.9, and which is its strongest", the per-pair reading of the stored tensor
+ * (notebooks/quick_predictions.ipynb cell 8), without materialising [L,N,N].  The mean of sigmoids is not monotone in any one
+ * model's logit, so neither the counts nor the best outcome can be merged from n_models mdg_bilinear_profile results.
+ *   Operands as mdg_bilinear_ensemble_select_count (HOST arrays of n_models = 1..8 device pointers, 16-byte aligned, D == 128);
+ *   precision MDG_PREC_F32 or MDG_PREC_BF16X3.  P is bit for bit what mdg_bilinear_ensemble_sigmoid's general sweep (z_head !=
+ *   z_tail) writes: the same products, sigmoid 1 / (1 + expf(-s)), fp32 sum in model order, one division by K.
+ *   thr [n_labels] fp32 (device), no NaN; scale [n_labels] fp32 (device), finite and > 0, or NULL.  Both are read back and checked
+ *   before anything is launched, which synchronises `stream` once (as mdg_bilinear_profile).
+ *   count, best (int32) and margin (fp32): [n_head, ldo], ldo >= n_tail.  The running state starts at 0 / -1 / -inf and moves only
+ *   on u > margin: exact ties of u -- the rule here, many probabilities round to exactly 1 -- keep the lowest l.  A NaN probability
+ *   is never counted and never best.  Ineligible pairs (eligible: mdg_topk_eligible; NOT_SELF / LOWER need n_head == n_tail) get
+ *   0 / -1 / -inf.  Every entry [i < n_head, j < n_tail] is written, nothing at columns [n_tail, ldo).  n_labels == 0 writes
+ *   0 / -1 / -inf everywhere.  n_labels <= 65535 per call (count and best share a register; merge chunks as for
+ *   mdg_bilinear_profile), n_tail < 2^31 - 64, n_head <= 65535 * 128.
+ *   mdg_bilinear_ensemble_profile_tiles: the 64-column tail tiles a workgroup owns (for tests that want sizes at that boundary).
+ *   Workspace: the size mdg_bilinear_ensemble_sigmoid_workspace_bytes gives (0 for F32).
+ * Deterministic: the state lives in registers, one store per entry after the last outcome; no atomics; bit-identical from launch
+ * to launch. */
+int mdg_bilinear_ensemble_profile_tiles(void);
+size_t mdg_bilinear_ensemble_profile_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_models,
+                                                     int precision);
+int mdg_bilinear_ensemble_profile(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                                  const float* thr, const float* scale, int32_t* count, int32_t* best, float* margin, int64_t ldo,
+                                  int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision, int eligible,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-row top-k of the all-pairs sweep: for every outcome l and head row i the k largest scores S[l,i,j] (the arithmetic of
  * mdg_bilinear_allpairs' general sweep in `precision`, bit for bit in F32 / BF16X3; the 16-bit modes run the row-statistics
  * sweep, whose fp32 sums are grouped differently: <= 2e-6 of the scale) over the ELIGIBLE tail columns j, and those columns.

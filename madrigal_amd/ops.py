@@ -1080,6 +1080,59 @@ def bilinear_ensemble_bincount(z_heads, z_tails, w_syms, edges: torch.Tensor, *,
     return counts
 
 
+def bilinear_ensemble_profile_tiles() -> int:
+    """The 64-column tail tiles a workgroup of ``bilinear_ensemble_profile`` owns (its column groups are this many tiles wide)."""
+    return lib().mdg_bilinear_ensemble_profile_tiles()
+
+
+def bilinear_ensemble_profile(z_heads, z_tails, w_syms, thresholds: torch.Tensor, *, scale: Optional[torch.Tensor] = None,
+                              eligible: str = "all", precision="bf16x3", out=None):
+    """Per-pair outcome profile of the checkpoint ensemble -> ``(count int32, best int32, margin fp32)``, each [Nh, Nt]: over the L
+    outcomes, with P[l,i,j] = mean_m sigmoid(z_heads[m][i]^T w_syms[m][l] z_tails[m][j]), ``count[i, j]`` = #{l : P[l,i,j] >=
+    thresholds[l]}, ``margin[i, j]`` = max_l (P[l,i,j] - thresholds[l]) * scale[l] (a subtract, then a multiply, in fp32) and
+    ``best[i, j]`` the lowest l attaining it -- ``bilinear_profile``'s contract on the probability madrigal/evaluate/predict.py:
+    466-499, 582-614 average over the checkpoints, reduced over the OUTCOMES inside the ensemble's sweep with nothing of [L,Nh,Nt]
+    materialised (``mdg_bilinear_ensemble_profile``).  The mean of K sigmoids is not monotone in any one model's logit, so K
+    ``bilinear_profile`` results cannot be merged into this.
+
+    K = len(z_heads) in 1..8; P is bit for bit ``bilinear_ensemble_sigmoid``'s general sweep in ``precision`` ("f32" or "bf16x3").
+    ``thresholds``: fp32 [L] probabilities, no NaN (``-inf`` flags every eligible pair with margin +inf, ``+inf`` none); ``scale``:
+    fp32 [L], finite and > 0 (None: ones).  Exact ties of the margin are common -- many probabilities round to exactly 1 -- and keep
+    the lowest outcome; a pair no outcome moves off ``-inf`` keeps ``best = -1``.  Ineligible pairs (``eligible`` as in
+    ``bilinear_topk``) get 0 / -1 / -inf; every entry is written.  L <= 65535 per call: merge chunks with ``profile_merge``.
+    ``out``: an optional (count, best, margin) triple to reuse, contiguous or with one common row pitch.  The values of
+    ``thresholds`` and ``scale`` are checked by the library, which synchronises the stream once.  Deterministic: no atomics."""
+    what = "bilinear_ensemble_profile"
+    if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 3):
+        raise ValueError("out: expected a (count, best, margin) triple")
+    w0 = next(iter(w_syms), None) if isinstance(w_syms, (list, tuple)) else None
+    if isinstance(w0, torch.Tensor) and w0.dim() == 3:                                       # shapes first, then the device
+        if scale is not None and (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or tuple(scale.shape) != (w0.shape[0],)):
+            raise ValueError(f"scale: expected a float32 tensor [{w0.shape[0]}] (one per outcome)")
+        if w0.shape[0] > 65535:
+            raise ValueError(f"w_syms: {w0.shape[0]} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
+    zh, zt, ws, thr, prec = _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=False)
+    K, L, D, Nh, Nt = len(zh), ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
+    dev = zh[0].device
+    if L > 65535:
+        raise ValueError(f"w_syms: {L} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
+    sc = None
+    if scale is not None:
+        if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or tuple(scale.shape) != (L,):
+            raise ValueError(f"scale: expected a float32 tensor [{L}] (one per outcome)")
+        sc = _f32_cuda(scale, "scale", 1)
+        if sc.device != dev:
+            raise ValueError("scale must be on the device of z_heads")
+    res = _profile_out(out, Nh, Nt, dev)
+    if Nh == 0 or Nt == 0:
+        return res
+    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
+    wsp, nbytes = _scratch("mdg_bilinear_ensemble_profile_workspace_bytes", dev, Nh, Nt, L, D, K, prec)
+    call("mdg_bilinear_ensemble_profile", arr(zh), arr(zt), arr(ws), K, _ptr(thr), _ptr(sc), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
+         res[0].stride(0), Nh, Nt, L, D, prec, TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]))
+    return res
+
+
 def empty_scores(L: int, Nh: int, Nt: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """An uninitialised [L,Nh,Nt] fp32 score (or rank) tensor in the layout the head writes fastest: rows padded to a multiple of
     32 floats, so that every row starts on a 128-byte line whatever Nt is (the real drug counts -- 11 607 in

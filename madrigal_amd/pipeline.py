@@ -704,32 +704,37 @@ def _profile_keys(count: torch.Tensor, margin: torch.Tensor) -> torch.Tensor:
     return (count.long() << 32) | mkey
 
 
-@torch.no_grad()
-def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, label_range: Optional[Tuple[int, int]] = None,
-                       max_bytes: int = 1 << 30):
-    """The ``K`` unordered drug pairs flagged for the most outcomes -> ``(count int32 [K], head int64 [K], tail int64 [K], best
-    int64 [K], margin fp32 [K])``: the pair {i, j} is profiled as (i, j) with i > j (the strict lower triangle ``top_pairs`` uses),
-    ordered by (count descending, margin descending, i ascending, j ascending); ``count``, ``best`` and ``margin`` are those of
-    ``outcome_profile``.  Padded with 0 / -1 / -1 / -1 / -inf when K > N (N - 1) / 2.  Streams over row blocks -- rows [r0, r1)
-    against the drugs [0, r1), the rest of the block being the upper triangle -- sized so that a block's profile and its selection
-    temporaries (about 48 bytes per pair) stay under ``max_bytes``, and keeps a running best K: no [N, N] tensor either, so it
-    runs at any N.  Exact: a tie at the K-th place is broken by (i, j) like every other."""
-    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
-        raise ValueError(f"K: expected a positive int, got {K!r}")
-    lo, hi = _outcomes(model, label_range)
-    thr = _cuts(thresholds, hi - lo, z.device)
-    sc = None if scale is None else _cuts(scale, hi - lo, z.device)
-    N, dev = z.shape[0], z.device
+def _shared_plane(exclude) -> Optional[torch.Tensor]:
+    """``exclude`` of the per-pair products: ONE plane from ``known_pairs_mask``, applied to the finished profile (exact, since a
+    pair is excluded under every outcome or under none).  A plane per outcome would change the counts outcome by outcome, inside
+    the sweep: out of scope."""
+    if exclude is None:
+        return None
+    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 3:
+        raise ValueError("exclude: expected a mask from known_pairs_mask / ops.pair_mask")
+    if exclude.shape[0] != 1:
+        raise ValueError(f"exclude: {exclude.shape[0]} planes; the per-pair profiles take one shared plane (known_pairs_mask without "
+                         f"labels) -- a plane per outcome changes the counts inside the sweep and is out of scope")
+    return exclude
+
+
+def _most_flagged(profile_block, N: int, K: int, lo: int, max_bytes: int, dev, exclude: Optional[torch.Tensor] = None):
+    """The row-block walk, key construction and running best K that ``most_flagged_pairs`` and ``ensemble_most_flagged_pairs`` share.
+    ``profile_block(r0, r1)`` -> the ALL-mode profile (count int32, best, margin fp32), each [r1 - r0, r1], of rows [r0, r1) against
+    the drugs [0, r1), ``best`` relative to ``lo``.  ``exclude``: one shared plane; its pairs never enter the ranking."""
     rows = max(1, int(max_bytes) // max(48 * N, 1))
     if rows >= 256:
         rows -= rows % 256                      # whole workgroups of the sweep
     run = None                                  # (key, count, head, tail, best, margin) of the best K so far, in result order
     for r0 in range(1, N, rows):                # row 0 has no column below it
         r1 = min(N, r0 + rows)
-        count, best, margin = _profile_chunks(model, z[r0:r1], z[:r1], thr, sc, lo, hi, "all", PROFILE_CHUNK)
+        count, best, margin = profile_block(r0, r1)
         i = torch.arange(r0, r1, device=dev)[:, None]
         j = torch.arange(r1, device=dev)[None, :]
-        key = _profile_keys(count, margin).masked_fill_(j >= i, -1).reshape(-1)
+        key = _profile_keys(count, margin).masked_fill_(j >= i, -1)
+        if exclude is not None:
+            key.masked_fill_(ops.pair_mask_rows(exclude, 0, torch.arange(r0, r1, device=dev), r1), -1)
+        key = key.reshape(-1)
         k = min(K, key.numel())
         kth = torch.topk(key, k, sorted=True).values[-1].clamp_(min=0)          # (>= 0: ineligible entries never enter)
         flat = torch.nonzero(key >= kth).reshape(-1)                           # ascending (i, j)
@@ -750,6 +755,28 @@ def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, l
         out_c[:n], out_h[:n], out_t[:n], out_m[:n] = run[1], run[2], run[3], run[5]
         out_b[:n] = torch.where(run[4] >= 0, run[4] + lo, run[4])
     return out_c, out_h, out_t, out_b, out_m
+
+
+@torch.no_grad()
+def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, label_range: Optional[Tuple[int, int]] = None,
+                       max_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
+    """The ``K`` unordered drug pairs flagged for the most outcomes -> ``(count int32 [K], head int64 [K], tail int64 [K], best
+    int64 [K], margin fp32 [K])``: the pair {i, j} is profiled as (i, j) with i > j (the strict lower triangle ``top_pairs`` uses),
+    ordered by (count descending, margin descending, i ascending, j ascending); ``count``, ``best`` and ``margin`` are those of
+    ``outcome_profile``.  Padded with 0 / -1 / -1 / -1 / -inf when K > N (N - 1) / 2.  Streams over row blocks -- rows [r0, r1)
+    against the drugs [0, r1), the rest of the block being the upper triangle -- sized so that a block's profile and its selection
+    temporaries (about 48 bytes per pair) stay under ``max_bytes``, and keeps a running best K: no [N, N] tensor either, so it
+    runs at any N.  Exact: a tie at the K-th place is broken by (i, j) like every other.  ``exclude``: ONE shared plane from
+    ``known_pairs_mask`` (no ``labels``); its pairs are left out of the ranking, so the result lists novel pairs only (a plane per
+    outcome is refused: it would change the counts inside the sweep)."""
+    excl = _shared_plane(exclude)
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"K: expected a positive int, got {K!r}")
+    lo, hi = _outcomes(model, label_range)
+    thr = _cuts(thresholds, hi - lo, z.device)
+    sc = None if scale is None else _cuts(scale, hi - lo, z.device)
+    return _most_flagged(lambda r0, r1: _profile_chunks(model, z[r0:r1], z[:r1], thr, sc, lo, hi, "all", PROFILE_CHUNK), z.shape[0], K, lo,
+                         max_bytes, z.device, excl)
 
 
 # ---- per-pair highest outcomes of a rank or score tensor, streamed (ops.outcome_topk) ----
@@ -1395,3 +1422,93 @@ def ensemble_auroc_bounds(models, zs, known: torch.Tensor, edges: torch.Tensor, 
     whatever the edges, and the exact AUROC counts them 1/2, inside the interval."""
     _known_mask(known, True)
     return auroc_bounds_from_counts(ensemble_score_histogram(models, zs, edges, label_range, eligible="lower", known=known))
+
+
+# ---- per-pair outcome profiles of the checkpoint ensemble (ops.bilinear_ensemble_profile) ----
+def _ensemble_profile_chunks(zh, zt, ws, thr, scale, eligible, chunk, prec):
+    """``ops.bilinear_ensemble_profile`` over the outcomes of ``ws`` in chunks, merged -> (count, best, margin), ``best`` relative to
+    the first outcome of ``ws``."""
+    L = ws[0].shape[0]
+    res = None
+    for s in range(0, max(L, 1), chunk):
+        e = min(L, s + chunk)
+        part = ops.bilinear_ensemble_profile(zh, zt, [w[s:e] for w in ws], thr[s:e], scale=None if scale is None else scale[s:e],
+                                             eligible=eligible, precision=prec)
+        res = part if res is None else ops.profile_merge(res, part, s)
+    return res
+
+
+@torch.no_grad()
+def ensemble_outcome_profile(models, zs, thresholds, scale=None, label_range: Optional[Tuple[int, int]] = None,
+                             eligible: str = "not_self", head_rows: Optional[Tuple[int, int]] = None, chunk: int = PROFILE_CHUNK,
+                             exclude: Optional[torch.Tensor] = None):
+    """``outcome_profile`` over a checkpoint ensemble -> ``(count int32, best int64, margin fp32)``, each [N, N] (or [r1 - r0, N]
+    with ``head_rows``): for the pair (i, j), over the outcomes ``label_range`` (default: all), with P[l, i, j] = mean_m
+    sigmoid(S_m[l, i, j]), ``count`` is the number of outcomes with P[l, i, j] >= thresholds[l] -- for how many interaction types
+    the ensemble of get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) flags
+    the pair --, ``margin`` the largest ``(P[l, i, j] - thresholds[l]) * scale[l]`` and ``best`` the MODELS' index of the lowest
+    outcome attaining it (-1 where no outcome moved the pair off -inf; ties are common, many probabilities round to exactly 1).
+    Nothing of [L', N, N] is materialised (``ops.bilinear_ensemble_profile``: one sweep per ``chunk`` <= 65535 outcomes, merged with
+    ``ops.profile_merge``).  The single-model profiles cannot be combined into this: the mean of sigmoids is not monotone in any one
+    model's score.
+
+    ``thresholds``: a PROBABILITY cut, a number such as 0.9 or [L'] (no NaN) -- it needs no calibration per outcome; ``scale``:
+    None, a positive number or [L'].  ``eligible`` and ``head_rows`` as ``outcome_profile``.  ``exclude``: ONE shared plane from
+    ``known_pairs_mask`` (no ``labels``); its pairs are blanked to 0 / -1 / -inf like ineligible ones (a plane per outcome is
+    refused: it would change the counts inside the sweep).  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``."""
+    if eligible not in ops.TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(ops.TOPK_ELIGIBLE)}")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= PROFILE_CHUNK:
+        raise ValueError(f"chunk: expected an int in 1..{PROFILE_CHUNK}, got {chunk!r}")
+    excl = _shared_plane(exclude)
+    zs, ws, lo, hi, _, prec = _ensemble_operands(models, zs, label_range, "ensemble_outcome_profile")
+    N, dev = zs[0].shape[0], zs[0].device
+    thr = _cuts(thresholds, hi - lo, dev)
+    sc = None if scale is None else _cuts(scale, hi - lo, dev)
+    out = None                                  # the entries to blank afterwards
+    if head_rows is None:
+        r0, r1 = 0, N
+        count, best, margin = _ensemble_profile_chunks(zs, zs, ws, thr, sc, eligible, chunk, prec)
+    else:
+        r0, r1 = head_rows
+        if not (0 <= r0 <= r1 <= N):
+            raise ValueError(f"head_rows {head_rows} outside [0, {N}]")
+        # a rectangle: the sweep runs in "all" mode and the block's self / upper entries are blanked here
+        count, best, margin = _ensemble_profile_chunks([z[r0:r1] for z in zs], zs, ws, thr, sc, "all", chunk, prec)
+        if eligible != "all":
+            i = torch.arange(r0, r1, device=dev)[:, None]
+            j = torch.arange(N, device=dev)[None, :]
+            out = (j == i) if eligible == "not_self" else (j >= i)
+    if excl is not None:
+        known = ops.pair_mask_rows(excl, 0, torch.arange(r0, r1, device=dev), N)
+        out = known if out is None else (out | known)
+    if out is not None:
+        count = count.masked_fill(out, 0)
+        best = best.masked_fill(out, -1)
+        margin = margin.masked_fill(out, float("-inf"))
+    best = best.long()
+    return count, torch.where(best >= 0, best + lo, best), margin
+
+
+@torch.no_grad()
+def ensemble_most_flagged_pairs(models, zs, thresholds, K: int, scale=None, label_range: Optional[Tuple[int, int]] = None,
+                                max_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
+    """``most_flagged_pairs`` over a checkpoint ensemble -> ``(count int32 [K], head int64 [K], tail int64 [K], best int64 [K],
+    margin fp32 [K])``: the ``K`` unordered drug pairs {i, j}, i > j, the ensemble flags for the most outcomes at the probability
+    cut ``thresholds`` (e.g. 0.9), ordered by (count descending, margin descending, i ascending, j ascending); ``count``, ``best``
+    and ``margin`` are those of ``ensemble_outcome_profile``.  Padding, the row-block streaming under ``max_bytes`` and the exact
+    tie rule at the K-th place are ``most_flagged_pairs``'s (one shared walk); no [N, N] and no [L', N, N] tensor, so it runs at
+    any N.  ``exclude``: ONE shared plane from ``known_pairs_mask``; its pairs are left out of the ranking (novel pairs only).
+    ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``."""
+    excl = _shared_plane(exclude)
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"K: expected a positive int, got {K!r}")
+    zs, ws, lo, hi, _, prec = _ensemble_operands(models, zs, label_range, "ensemble_most_flagged_pairs")
+    N, dev = zs[0].shape[0], zs[0].device
+    thr = _cuts(thresholds, hi - lo, dev)
+    sc = None if scale is None else _cuts(scale, hi - lo, dev)
+
+    def block(r0, r1):
+        return _ensemble_profile_chunks([z[r0:r1] for z in zs], [z[:r1] for z in zs], ws, thr, sc, "all", PROFILE_CHUNK, prec)
+
+    return _most_flagged(block, N, K, lo, max_bytes, dev, excl)
