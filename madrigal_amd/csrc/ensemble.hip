@@ -26,111 +26,24 @@
 // vector-memory stream is [LDS-DMA of the next tile][32 row stores (+ 32 mirrored)], so `s_waitcnt vmcnt(32)` retires the DMA and
 // leaves the youngest stores in flight (in-order retirement, see bilinear.hip's main loop); a stage that follows a T rebuild or
 // issued no stores waits vmcnt(0).
-#include "bilinear_tiles.h"
+//
+// build_t, pick, sigmoid_head and the constants of the layout live in ensemble_sweep.h, which the four reducing products of this
+// sweep (ensemble_topk / _select / _bincount / _profile.hip) include as well.
+#include "ensemble_sweep.h"
 
 namespace {
 
-constexpr int MAXK = 8;
 // waves per workgroup: K >= 2 one per SIMD (512 VGPRs: T, the chunk's running sums), K = 1 two per SIMD like the head
-template <bool ONE> constexpr int kWaves = ONE ? 8 : 4;
+template <bool ONE> constexpr int kWaves = ONE ? 8 : ENS_NW;
 constexpr int BM_MAX = 32 * 8;         // the most head rows per workgroup
-constexpr int SLAB_BYTES = 8192;       // per wave: [32 rows][64 columns] fp32 (T half while rebuilding, finished tile when mirroring)
 template <int NW> constexpr int kLds = 2 * STAGE_BYTES + NW * SLAB_BYTES;   // stage buffers + one slab per wave
 
-struct EnsembleArgs {
-  const float* z_head[MAXK];   // fp32 rows (T prologue)
-  TileSrc zt[MAXK];            // tail operand images (fp32, or hi/lo bf16)
-  TileSrc w[MAXK];             // W_sym images, all outcomes; nrows = D
+struct EnsembleArgs : EnsOperands {
   float* out;
   int64_t n_head, n_tail, ldo;
   int n_models;
   int stagger;
 };
-
-// a[k] for a wave-uniform k without dynamic indexing of the kernel arguments (scalar selects)
-template <typename T>
-__device__ __forceinline__ T pick(const T (&a)[MAXK], int k) {
-  T v = a[0];
-#pragma unroll
-  for (int i = 1; i < MAXK; ++i)
-    if (k == i) v = a[i];
-  return v;
-}
-
-__device__ __forceinline__ float sigmoid_head(float s) { return 1.0f / (1.0f + expf(-s)); }   // MDG_EPI_STORE_SIGMOID's formula
-
-// T = z_head[32 rows of this wave] . W_sym[l] -> At, the same fp32 values as the head's prologue: per 32-column tile the MFMA
-// chain runs over k in the same order with the same products (compute_tile), only the loop nest is k-outer so that the z operand
-// is held one k step at a time (8 VGPRs instead of a 64-VGPR fragment: the running sums of the chunk stay resident).  W_sym[l]
-// (symmetric: its rows are its columns) is staged whole, rows 0..63 in stage buffer 0 and 64..127 in buffer 1.
-template <int MODE, int NW>
-__device__ __forceinline__ void build_t(AFrag<MODE>& At, const float* zrow, const TileSrc& wl, char* smem, char* slab, int tid,
-                                        int r, int h) {
-  {
-    u32x4 r0[32 / NW], r1[32 / NW];
-    stage_load<MODE, NW>(wl, 0, tid, r0);
-    stage_load<MODE, NW>(wl, 64, tid, r1);
-    __syncthreads();                                // every wave is done with the stage buffers
-    stage_write<MODE, NW>(smem, tid, r0);
-    stage_write<MODE, NW>(smem + STAGE_BYTES, tid, r1);
-    __syncthreads();
-  }
-  f32x16 acc[4];                                    // output columns 32 c .. 32 c + 31
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[c][v] = 0.f;
-  if constexpr (MODE == MDG_PREC_F32) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float4 a = *reinterpret_cast<const float4*>(zrow + 8 * q + 4 * h);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 b = *reinterpret_cast<const float4*>(smem + (c >> 1) * STAGE_BYTES + tile_off<512>(32 * (c & 1) + r, 2 * q + h));
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);          // one k step of operands live at a time
-    }
-  } else {
-    static_assert(MODE == MDG_PREC_BF16X3, "fp32 and split-bf16 operands");
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float4 v0 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h);
-      const float4 v1 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h + 4);
-      bf16x8 ahi, alo;
-      split8<MODE>(v0, v1, ahi, alo);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const char* lds = smem + (c >> 1) * STAGE_BYTES;
-        const int j = 32 * (c & 1) + r;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(j, 2 * s + h));
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lds + LO_OFF + tile_off<256>(j, 2 * s + h));
-        acc[c] = mma16<MODE>(alo, bh, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bl, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bh, acc[c]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // T (fp32) -> this wave's slab, one 64-column half at a time, and back as the A fragment (the head's afrag_from_slab)
-#pragma unroll
-  for (int st = 0; st < 2; ++st) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = acc_row(v, h), n = 32 * t + r;
-        *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[2 * st + t][v];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    afrag_from_slab<MODE>(At, slab, st, r, h);
-  }
-  __syncthreads();                                  // every wave is done reading W from the stage buffers
-}
 
 // ONE: K == 1 (T built once per row block and held for the whole sweep, no running sums)
 template <int MODE, bool SYM, bool ONE, int CH>
@@ -316,8 +229,6 @@ __global__ void ensemble_split_kernel(const SplitJobs j) {
 }
 
 inline size_t ens_align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
-constexpr int ENS_CH = 6;   // tail tiles per chunk (running sums: 6 x 32 VGPRs; T rebuilt for a third of the chunk's MFMA work)
 
 template <int MODE>
 int launch_ensemble(const EnsembleArgs& a, bool sym, int64_t n_labels, hipStream_t st) {

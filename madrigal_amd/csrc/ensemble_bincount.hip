@@ -16,9 +16,9 @@
 //     waves, 128 head rows of one outcome, one wave per SIMD) walks its tail tiles in chunks of CH; for every chunk it rebuilds
 //     T_m = z_head_m[rows] . W_sym_m[l] (build_t) for m = 0..K-1 and sweeps the chunk with it, sigmoid 1 / (1 + expf(-s)), the
 //     running sums of the chunk (psum, CH x 32 VGPRs) staying in registers across the models, divided once by K; every compare is on
-//     that quotient.  With K = 1 the one T is built for the first chunk only.  build_t, pick, sigmoid_head and the two-buffer ring
-//     are copies: ensemble.hip, ensemble_topk.hip and ensemble_select.hip stay as they are (sharing sweep text has moved hipcc's
-//     schedule before).
+//     that quotient.  With K = 1 the one T is built for the first chunk only.  build_t, pick, sigmoid_head, the eligibility test
+//     and the layout's constants are ensemble_sweep.h's, shared by the family; the two-buffer ring is this file's own text
+//     (sharing sweep text has moved hipcc's schedule before).
 //   epilogue: bincount.hip's, run on the chunk's finished tiles after its last model.  The tile index of that loop is a run-time
 //     value and the tile's sums are picked by wave-uniform selects: ONE copy of the counting code (copies inside the
 //     unrolled stage loop sent psum to scratch).  One workgroup = one outcome, so the edge table is workgroup-uniform: the B edges
@@ -44,25 +44,17 @@
 // table whatever its bit, which is what forcing its bit clear amounts to.  The unsplit instantiations read no mask memory.
 // Waits.  Every stage barrier waits vmcnt(0); the only vector-memory operations a wave has in flight there are the LDS-DMAs of the
 // tile about to be read (the LDS adds of the epilogue are counted by lgkmcnt, the global adds come after the last tile).
-#include "sweep_reduce.h"
+#include "ensemble_sweep.h"
 
 namespace {
 
-constexpr int MAXK = 8;
-constexpr int ENS_BIN_NW = 4;               // waves per workgroup, one per SIMD (512 VGPRs: T, the chunk's running sums, the searches)
-constexpr int ENS_BIN_CH = 6;               // tail tiles per chunk, as ensemble.hip, ensemble_topk.hip and ensemble_select.hip
-constexpr int SLAB_BYTES = 8192;            // per wave: [32 rows][64 columns] fp32, T half while rebuilding
-constexpr int ENS_BIN_RING = 2 * STAGE_BYTES + ENS_BIN_NW * SLAB_BYTES;
 constexpr int ENS_BIN_MAX_EDGES = 1024;     // mdg_bilinear_bincount_max_edges()
 constexpr int ENS_BIN_TABLE = ENS_BIN_MAX_EDGES + 4;        // SPLIT: words from table 0 to table 1
-// LDS behind the ring and the slabs: the edges, then one or two counter tables.
-template <bool SPLIT> constexpr int ens_bin_lds = ENS_BIN_RING + ENS_BIN_MAX_EDGES * 4 + (SPLIT ? 2 : 1) * ENS_BIN_TABLE * 4;
+// LDS behind the ring and the slabs (ENS_LDS): the edges, then one or two counter tables.
+template <bool SPLIT> constexpr int ens_bin_lds = ENS_LDS + ENS_BIN_MAX_EDGES * 4 + (SPLIT ? 2 : 1) * ENS_BIN_TABLE * 4;
 
-struct EnsBinArgs {
-  const float* z_head[MAXK];   // fp32 rows (T prologue)
-  TileSrc zt[MAXK];            // tail operand images (fp32, or hi/lo bf16)
-  TileSrc w[MAXK];             // W_sym images, all outcomes; nrows = D
-  const float* edges;          // [n_labels, n_edges] ascending per outcome
+struct EnsBinArgs : EnsOperands {
+  const float* edges;         // [n_labels, n_edges] ascending per outcome
   unsigned long long* counts;  // [n_labels, n_edges + 1] (SPLIT: two such tables), zeroed on the stream before the launch
   int64_t n_head, n_tail;
   int n_models;
@@ -72,29 +64,6 @@ struct EnsBinArgs {
 
 template <bool SPLIT> struct EnsBinKArgs : EnsBinArgs {};
 template <> struct EnsBinKArgs<true> : EnsBinArgs { PairMask mask; };
-
-// a[k] for a wave-uniform k without dynamic indexing of the kernel arguments (scalar selects)
-template <typename T>
-__device__ __forceinline__ T pick(const T (&a)[MAXK], int k) {
-  T v = a[0];
-#pragma unroll
-  for (int i = 1; i < MAXK; ++i)
-    if (k == i) v = a[i];
-  return v;
-}
-
-__device__ __forceinline__ float sigmoid_head(float s) { return 1.0f / (1.0f + expf(-s)); }   // MDG_EPI_STORE_SIGMOID's formula
-
-// Eligibility of the element in row wrow0 + lr, column tcol0 + lc of a tile from the tile's 32-bit distances (wave-uniform, clamped):
-// dcr = tcol0 - wrow0, nr = n_head - wrow0, nc = n_tail - tcol0.  ensemble_select.hip's test.
-__device__ __forceinline__ int ens_bin_clamp(int64_t x) {
-  return static_cast<int>(x < -(int64_t(1) << 30) ? -(int64_t(1) << 30) : (x > (int64_t(1) << 30) ? (int64_t(1) << 30) : x));
-}
-__device__ __forceinline__ bool ens_bin_eligible(int mode, int lr, int lc, int dcr, int nr, int nc) {
-  const int d = dcr + lc - lr;                                                          // column - row
-  const bool pair = mode == MDG_TOPK_NOT_SELF ? d != 0 : d < 0;                         // (bitwise: selects, no branches)
-  return (lr < nr) & (lc < nc) & ((mode == MDG_TOPK_ALL) | pair);
-}
 
 // The wave's fast-path counts and the edge / counter tables in LDS.
 struct EnsBinState {
@@ -162,81 +131,10 @@ __device__ __forceinline__ void ens_bin_search(const EnsBinState& b, const float
   }
 }
 
-// T = z_head[32 rows of this wave] . W_sym[l] -> At: ensemble.hip's build_t (k-outer loop nest, the head's products in the head's
-// order per accumulator element).  W_sym[l] is staged whole, rows 0..63 in stage buffer 0 and 64..127 in buffer 1.
-template <int MODE, int NW>
-__device__ __forceinline__ void build_t(AFrag<MODE>& At, const float* zrow, const TileSrc& wl, char* smem, char* slab, int tid,
-                                        int r, int h) {
-  {
-    u32x4 r0[32 / NW], r1[32 / NW];
-    stage_load<MODE, NW>(wl, 0, tid, r0);
-    stage_load<MODE, NW>(wl, 64, tid, r1);
-    __syncthreads();                                // every wave is done with the stage buffers
-    stage_write<MODE, NW>(smem, tid, r0);
-    stage_write<MODE, NW>(smem + STAGE_BYTES, tid, r1);
-    __syncthreads();
-  }
-  f32x16 acc[4];                                    // output columns 32 c .. 32 c + 31
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[c][v] = 0.f;
-  if constexpr (MODE == MDG_PREC_F32) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float4 a = *reinterpret_cast<const float4*>(zrow + 8 * q + 4 * h);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 b = *reinterpret_cast<const float4*>(smem + (c >> 1) * STAGE_BYTES + tile_off<512>(32 * (c & 1) + r, 2 * q + h));
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);          // one k step of operands live at a time
-    }
-  } else {
-    static_assert(MODE == MDG_PREC_BF16X3, "fp32 and split-bf16 operands");
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float4 v0 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h);
-      const float4 v1 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h + 4);
-      bf16x8 ahi, alo;
-      split8<MODE>(v0, v1, ahi, alo);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const char* lds = smem + (c >> 1) * STAGE_BYTES;
-        const int j = 32 * (c & 1) + r;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(j, 2 * s + h));
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lds + LO_OFF + tile_off<256>(j, 2 * s + h));
-        acc[c] = mma16<MODE>(alo, bh, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bl, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bh, acc[c]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // T (fp32) -> this wave's slab, one 64-column half at a time, and back as the A fragment (the head's afrag_from_slab)
-#pragma unroll
-  for (int st = 0; st < 2; ++st) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = acc_row(v, h), n = 32 * t + r;
-        *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[2 * st + t][v];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    afrag_from_slab<MODE>(At, slab, st, r, h);
-  }
-  __syncthreads();                                  // every wave is done reading W from the stage buffers
-}
-
 template <int MODE, bool SPLIT, int CH>
-__global__ __launch_bounds__(64 * ENS_BIN_NW, 1) void ensemble_bincount_kernel(const EnsBinKArgs<SPLIT> p) {
+__global__ __launch_bounds__(64 * ENS_NW, 1) void ensemble_bincount_kernel(const EnsBinKArgs<SPLIT> p) {
   static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "the ensemble's precisions");
-  constexpr int NW = ENS_BIN_NW, BM = 32 * NW;
+  constexpr int NW = ENS_NW, BM = 32 * NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t l = blockIdx.y;
@@ -254,8 +152,8 @@ __global__ __launch_bounds__(64 * ENS_BIN_NW, 1) void ensemble_bincount_kernel(c
   // Kernel start: the outcome's edges into LDS, the counters to zero.  The barriers of the first build_t order this before the sweep.
   EnsBinState bs;
   {
-    float* eds = reinterpret_cast<float*>(smem + ENS_BIN_RING);
-    unsigned* cnt = reinterpret_cast<unsigned*>(smem + ENS_BIN_RING + ENS_BIN_MAX_EDGES * 4);
+    float* eds = reinterpret_cast<float*>(smem + ENS_LDS);
+    unsigned* cnt = reinterpret_cast<unsigned*>(smem + ENS_LDS + ENS_BIN_MAX_EDGES * 4);
     const float* ge = p.edges + l * p.n_edges;
     for (int i = tid; i < p.n_edges; i += 64 * NW) eds[i] = ge[i];
     for (int i = tid; i <= p.n_edges; i += 64 * NW) cnt[i] = 0u;
@@ -384,12 +282,12 @@ __global__ __launch_bounds__(64 * ENS_BIN_NW, 1) void ensemble_bincount_kernel(c
         const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 32 <= p.n_head &&
                            (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 31));
         if (!plain) {
-          const int dcr = ens_bin_clamp(tcol0 - wrow0), nr = ens_bin_clamp(p.n_head - wrow0), ncl = ens_bin_clamp(p.n_tail - tcol0);
+          const int dcr = ens_clamp(tcol0 - wrow0), nr = ens_clamp(p.n_head - wrow0), ncl = ens_clamp(p.n_tail - tcol0);
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v)
-              pr[t][v] = ens_bin_eligible(mode, acc_row(v, h), 32 * t + r, dcr, nr, ncl) ? pr[t][v] : __builtin_nanf("");
+              pr[t][v] = ens_eligible(mode,acc_row(v, h), 32 * t + r, dcr, nr, ncl) ? pr[t][v] : __builtin_nanf("");
         }
         // SPLIT: a tile without a known pair for the wave (wave-uniform) costs this ballot and goes the unsplit way
         bool mixed = false;
@@ -446,22 +344,18 @@ __global__ __launch_bounds__(64 * ENS_BIN_NW, 1) void ensemble_bincount_kernel(c
 template <int MODE, bool SPLIT>
 int launch_ens_bincount(EnsBinKArgs<SPLIT>& a, const float* const* z_tail, const float* const* w_sym, int64_t n_labels, char* ws,
                         hipStream_t st, const char* fn) {
-  // per model the operand images of the single-model head (zhi | whi | zlo | wlo), one after the other
-  const size_t per = head_images_workspace_bytes(a.n_tail, n_labels, D, MODE);
-  for (int m = 0; m < a.n_models; ++m)
-    make_head_images<MODE>(a.zt[m], a.w[m], z_tail[m], w_sym[m], a.n_tail, n_labels, ws ? ws + m * per : nullptr, st);
-  MDG_CHECK_LAUNCH(fn);
-  for (int m = a.n_models; m < MAXK; ++m) { a.zt[m] = a.zt[0]; a.w[m] = a.w[0]; }      // unused slots repeat model 0 (never read)
-  constexpr int lds = ens_bin_lds<SPLIT>;
-  const int rc = mdg_raise_dynamic_lds(reinterpret_cast<const void*>(ensemble_bincount_kernel<MODE, SPLIT, ENS_BIN_CH>), lds, fn);
+  int rc = ens_make_images<MODE>(a, z_tail, w_sym, a.n_models, a.n_tail, n_labels, ws, st, fn);
   if (rc != MDG_OK) return rc;
-  const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 32 * ENS_BIN_NW)), static_cast<unsigned>(n_labels));
-  hipLaunchKernelGGL((ensemble_bincount_kernel<MODE, SPLIT, ENS_BIN_CH>), grid, dim3(64 * ENS_BIN_NW), lds, st, a);
+  constexpr int lds = ens_bin_lds<SPLIT>;
+  rc = mdg_raise_dynamic_lds(reinterpret_cast<const void*>(ensemble_bincount_kernel<MODE, SPLIT, ENS_CH>), lds, fn);
+  if (rc != MDG_OK) return rc;
+  const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 32 * ENS_NW)), static_cast<unsigned>(n_labels));
+  hipLaunchKernelGGL((ensemble_bincount_kernel<MODE, SPLIT, ENS_CH>), grid, dim3(64 * ENS_NW), lds, st, a);
   MDG_CHECK_LAUNCH(fn);
   return MDG_OK;
 }
 
-// Both entry points: the checks (ens_select_check's, in its order, plus n_edges and bincount's n_tail rule), the zeroing of `tables`
+// Both entry points: the checks (the family's, plus n_edges and bincount's n_tail rule), the zeroing of `tables`
 // count tables on the stream, the launch.  SPLIT: the sweep keeps two tables by the bit of `mask`; tables == 2 without SPLIT is the
 // split entry point without a mask (table 1 stays zero).
 template <bool SPLIT>
@@ -469,15 +363,10 @@ int ens_bincount_run(const char* fn, int tables, const float* const* z_head, con
                      int n_models, const float* edges, int64_t* counts, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_,
                      int n_edges, int precision, int eligible, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* mask,
                      int64_t plane_stride) {
-  MDG_CHECK_ARG(n_models >= 1 && n_models <= MAXK, "%s: n_models must be in 1..%d (got %d)", fn, MAXK, n_models);
-  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  int rc = ens_check_sizes(fn, n_models, n_head, n_tail, n_labels, D_, precision, eligible);
   if (rc != MDG_OK) return rc;
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3, "%s: precision %d not offered (MDG_PREC_F32 or MDG_PREC_BF16X3)", fn,
-                precision);
   MDG_CHECK_ARG(n_edges >= 1 && n_edges <= ENS_BIN_MAX_EDGES, "%s: n_edges must be in 1..%d (got %d)", fn, ENS_BIN_MAX_EDGES, n_edges);
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 23), "%s: n_tail %lld does not fit the 32-bit workgroup counters (< 2^23)", fn, (long long)n_tail);
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail, "%s: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)",
-                fn, (long long)n_head, (long long)n_tail);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t count_bytes = static_cast<size_t>(tables) * n_labels * (n_edges + 1) * sizeof(int64_t);
   auto zero = [&]() -> int {
@@ -489,18 +378,8 @@ int ens_bincount_run(const char* fn, int tables, const float* const* z_head, con
     return MDG_OK;
   };
   if (n_head == 0 || n_labels == 0) return counts ? zero() : MDG_OK;        // no pair at all: every count is 0
-  MDG_CHECK_ARG(n_tail >= 1, "%s: n_tail must be at least 1", fn);
-  MDG_CHECK_ARG(z_head && z_tail && w_sym && edges && counts, "%s: null pointer", fn);
-  for (int m = 0; m < n_models; ++m) {
-    MDG_CHECK_ARG(z_head[m] && z_tail[m] && w_sym[m], "%s: null pointer for model %d", fn, m);
-    MDG_CHECK_ARG(mdg_aligned16(z_head[m]) && mdg_aligned16(z_tail[m]) && mdg_aligned16(w_sym[m]),
-                  "%s: z_head, z_tail and w_sym must be 16-byte aligned (model %d)", fn, m);
-  }
-  const size_t need = mdg_bilinear_ensemble_bincount_workspace_bytes(n_head, n_tail, n_labels, D_, n_models, precision);
-  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-    mdg_set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", fn, need, workspace_bytes);
-    return MDG_EWORKSPACE;
-  }
+  rc = ens_check_operands(fn, z_head, z_tail, w_sym, n_models, edges && counts, n_tail, n_labels, precision, workspace, workspace_bytes);
+  if (rc != MDG_OK) return rc;
   EnsBinKArgs<SPLIT> a{};
   if constexpr (SPLIT) {
     const int mrc = sweep_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
@@ -508,11 +387,7 @@ int ens_bincount_run(const char* fn, int tables, const float* const* z_head, con
   }
   const int zrc = zero();
   if (zrc != MDG_OK) return zrc;
-  for (int m = 0; m < MAXK; ++m) {
-    a.z_head[m] = z_head[m < n_models ? m : 0];
-    a.zt[m].nrows = n_tail;
-    a.w[m].nrows = D;
-  }
+  ens_fill_operands(a, z_head, n_models, n_tail);
   a.edges = edges;
   a.counts = reinterpret_cast<unsigned long long*>(counts);
   a.n_head = n_head; a.n_tail = n_tail;
@@ -529,8 +404,7 @@ int ens_bincount_run(const char* fn, int tables, const float* const* z_head, con
 extern "C" size_t mdg_bilinear_ensemble_bincount_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_models,
                                                                  int precision) {
   (void)n_head;
-  if (n_models <= 0) return 0;
-  return static_cast<size_t>(n_models) * head_images_workspace_bytes(n_tail, n_labels, D_, precision);
+  return ens_workspace_bytes(n_tail, n_labels, D_, n_models, precision);
 }
 
 extern "C" int mdg_bilinear_ensemble_bincount(const float* const* z_head, const float* const* z_tail, const float* const* w_sym,

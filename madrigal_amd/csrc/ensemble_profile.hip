@@ -22,8 +22,8 @@
 //                one packed u32 (count << 16 | best + 1, hence n_labels <= 65535 per call) and one fp32 margin are updated, the
 //                margin only on u > margin: the lowest l of a tie stays.  A NaN is never counted and never best.
 //   end          three plain vector stores per element, lane = column (128-byte segments), once, after the loop.
-// build_t, pick, sigmoid_head, the ring and the eligibility test are copies: ensemble.hip, ensemble_topk.hip, ensemble_select.hip and
-// profile.hip stay as they are (sharing sweep text has moved hipcc's schedule before).  The score arithmetic per
+// build_t, pick, sigmoid_head, the eligibility test and the layout's constants are ensemble_sweep.h's, shared by the family; the
+// ring is this file's own text (sharing sweep text has moved hipcc's schedule before).  The score arithmetic per
 // accumulator element is therefore ensemble.hip's general (non-symmetric) sweep bit for bit, in F32 and BF16X3.
 // Grid = (column groups, row blocks), column groups fastest: the resident workgroups walk l in step and share each W_sym_m[l] and
 // the models' tail images in L2.  LOWER: row blocks are reversed (the last one has the most work); a workgroup wholly on or above
@@ -35,24 +35,17 @@
 // No atomics, no LDS beyond the stage buffers and the slabs (96 KiB): bit-identical from launch to launch.
 // Registers: T 64 + accumulators 32 + psum 32 G + state 64 G of the 512 a wave has at one wave per SIMD; the kernel must compile to
 // ZERO scratch (check with -Rpass-analysis=kernel-resource-usage; DESIGN.md 4aj has the table).
-#include "sweep_reduce.h"
+#include "ensemble_sweep.h"
 
 #include <math.h>
 #include <vector>
 
 namespace {
 
-constexpr int MAXK = 8;
-constexpr int ENS_PRO_NW = 4;               // waves per workgroup, one per SIMD
 constexpr int ENS_PRO_G = 3;                // tail tiles a workgroup owns (the register table behind the choice)
-constexpr int ENS_PRO_BM = 32 * ENS_PRO_NW;
-constexpr int SLAB_BYTES = 8192;            // per wave: [32 rows][64 columns] fp32, T half while rebuilding
-constexpr int ENS_PRO_LDS = 2 * STAGE_BYTES + ENS_PRO_NW * SLAB_BYTES;
+constexpr int ENS_PRO_BM = 32 * ENS_NW;
 
-struct EnsProArgs {
-  const float* z_head[MAXK];   // fp32 rows (T prologue)
-  TileSrc zt[MAXK];            // tail operand images (fp32, or hi/lo bf16)
-  TileSrc w[MAXK];             // W_sym images, all outcomes; nrows = D
+struct EnsProArgs : EnsOperands {
   const float* thr;            // [n_labels]
   const float* scale;          // [n_labels] or null (all ones)
   int* count;                  // [n_head, ldo]
@@ -64,104 +57,10 @@ struct EnsProArgs {
   int eligible;                // mdg_topk_eligible
 };
 
-// a[k] for a wave-uniform k without dynamic indexing of the kernel arguments (scalar selects)
-template <typename T>
-__device__ __forceinline__ T pick(const T (&a)[MAXK], int k) {
-  T v = a[0];
-#pragma unroll
-  for (int i = 1; i < MAXK; ++i)
-    if (k == i) v = a[i];
-  return v;
-}
-
-__device__ __forceinline__ float sigmoid_head(float s) { return 1.0f / (1.0f + expf(-s)); }   // MDG_EPI_STORE_SIGMOID's formula
-
-// Eligibility of the element in row wrow0 + lr, column tcol0 + lc of a tile from the tile's 32-bit distances (wave-uniform, clamped):
-// dcr = tcol0 - wrow0, nr = n_head - wrow0, nc = n_tail - tcol0.  ensemble_select.hip's test.
-__device__ __forceinline__ int ens_pro_clamp(int64_t x) {
-  return static_cast<int>(x < -(int64_t(1) << 30) ? -(int64_t(1) << 30) : (x > (int64_t(1) << 30) ? (int64_t(1) << 30) : x));
-}
-__device__ __forceinline__ bool ens_pro_eligible(int mode, int lr, int lc, int dcr, int nr, int nc) {
-  const int d = dcr + lc - lr;                                                          // column - row
-  const bool pair = mode == MDG_TOPK_NOT_SELF ? d != 0 : d < 0;                         // (bitwise: selects, no branches)
-  return (lr < nr) & (lc < nc) & ((mode == MDG_TOPK_ALL) | pair);
-}
-
-// T = z_head[32 rows of this wave] . W_sym[l] -> At: ensemble.hip's build_t (k-outer loop nest, the head's products in the head's
-// order per accumulator element).  W_sym[l] is staged whole, rows 0..63 in stage buffer 0 and 64..127 in buffer 1.
-template <int MODE, int NW>
-__device__ __forceinline__ void build_t(AFrag<MODE>& At, const float* zrow, const TileSrc& wl, char* smem, char* slab, int tid,
-                                        int r, int h) {
-  {
-    u32x4 r0[32 / NW], r1[32 / NW];
-    stage_load<MODE, NW>(wl, 0, tid, r0);
-    stage_load<MODE, NW>(wl, 64, tid, r1);
-    __syncthreads();                                // every wave is done with the stage buffers
-    stage_write<MODE, NW>(smem, tid, r0);
-    stage_write<MODE, NW>(smem + STAGE_BYTES, tid, r1);
-    __syncthreads();
-  }
-  f32x16 acc[4];                                    // output columns 32 c .. 32 c + 31
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[c][v] = 0.f;
-  if constexpr (MODE == MDG_PREC_F32) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float4 a = *reinterpret_cast<const float4*>(zrow + 8 * q + 4 * h);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 b = *reinterpret_cast<const float4*>(smem + (c >> 1) * STAGE_BYTES + tile_off<512>(32 * (c & 1) + r, 2 * q + h));
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);          // one k step of operands live at a time
-    }
-  } else {
-    static_assert(MODE == MDG_PREC_BF16X3, "fp32 and split-bf16 operands");
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float4 v0 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h);
-      const float4 v1 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h + 4);
-      bf16x8 ahi, alo;
-      split8<MODE>(v0, v1, ahi, alo);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const char* lds = smem + (c >> 1) * STAGE_BYTES;
-        const int j = 32 * (c & 1) + r;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(j, 2 * s + h));
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lds + LO_OFF + tile_off<256>(j, 2 * s + h));
-        acc[c] = mma16<MODE>(alo, bh, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bl, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bh, acc[c]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // T (fp32) -> this wave's slab, one 64-column half at a time, and back as the A fragment (the head's afrag_from_slab)
-#pragma unroll
-  for (int st = 0; st < 2; ++st) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = acc_row(v, h), n = 32 * t + r;
-        *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[2 * st + t][v];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    afrag_from_slab<MODE>(At, slab, st, r, h);
-  }
-  __syncthreads();                                  // every wave is done reading W from the stage buffers
-}
-
 template <int MODE, int G>
-__global__ __launch_bounds__(64 * ENS_PRO_NW, 1) void ensemble_profile_kernel(const EnsProArgs p) {
+__global__ __launch_bounds__(64 * ENS_NW, 1) void ensemble_profile_kernel(const EnsProArgs p) {
   static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "the ensemble's precisions");
-  constexpr int NW = ENS_PRO_NW, BM = ENS_PRO_BM;
+  constexpr int NW = ENS_NW, BM = ENS_PRO_BM;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int K = p.n_models, mode = p.eligible, L = p.n_labels;
@@ -281,12 +180,12 @@ __global__ __launch_bounds__(64 * ENS_PRO_NW, 1) void ensemble_profile_kernel(co
             const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 32 <= p.n_head &&
                                (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 31));
             if (!plain) {
-              const int dcr = ens_pro_clamp(tcol0 - wrow0), nr = ens_pro_clamp(p.n_head - wrow0), ncl = ens_pro_clamp(p.n_tail - tcol0);
+              const int dcr = ens_clamp(tcol0 - wrow0), nr = ens_clamp(p.n_head - wrow0), ncl = ens_clamp(p.n_tail - tcol0);
 #pragma unroll
               for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int v = 0; v < 16; ++v)
-                  pr[t][v] = ens_pro_eligible(mode, acc_row(v, h), 32 * t + r, dcr, nr, ncl) ? pr[t][v] : __builtin_nanf("");
+                  pr[t][v] = ens_eligible(mode,acc_row(v, h), 32 * t + r, dcr, nr, ncl) ? pr[t][v] : __builtin_nanf("");
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -332,15 +231,11 @@ __global__ __launch_bounds__(64 * ENS_PRO_NW, 1) void ensemble_profile_kernel(co
 template <int MODE>
 int launch_ens_profile(EnsProArgs& a, const float* const* z_tail, const float* const* w_sym, char* ws, hipStream_t st, const char* fn) {
   if (a.n_labels > 0) {
-    // per model the operand images of the single-model head (zhi | whi | zlo | wlo), one after the other
-    const size_t per = head_images_workspace_bytes(a.n_tail, a.n_labels, D, MODE);
-    for (int m = 0; m < a.n_models; ++m)
-      make_head_images<MODE>(a.zt[m], a.w[m], z_tail[m], w_sym[m], a.n_tail, a.n_labels, ws ? ws + m * per : nullptr, st);
-    MDG_CHECK_LAUNCH(fn);
-    for (int m = a.n_models; m < MAXK; ++m) { a.zt[m] = a.zt[0]; a.w[m] = a.w[0]; }      // unused slots repeat model 0 (never read)
+    const int rc = ens_make_images<MODE>(a, z_tail, w_sym, a.n_models, a.n_tail, a.n_labels, ws, st, fn);
+    if (rc != MDG_OK) return rc;
   }
   const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_tail, ENS_PRO_G * BN)), static_cast<unsigned>(mdg_cdiv(a.n_head, ENS_PRO_BM)));
-  hipLaunchKernelGGL((ensemble_profile_kernel<MODE, ENS_PRO_G>), grid, dim3(64 * ENS_PRO_NW), ENS_PRO_LDS, st, a);
+  hipLaunchKernelGGL((ensemble_profile_kernel<MODE, ENS_PRO_G>), grid, dim3(64 * ENS_NW), ENS_LDS, st, a);
   MDG_CHECK_LAUNCH(fn);
   return MDG_OK;
 }
@@ -352,8 +247,7 @@ extern "C" int mdg_bilinear_ensemble_profile_tiles(void) { return ENS_PRO_G; }
 extern "C" size_t mdg_bilinear_ensemble_profile_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_models,
                                                                 int precision) {
   (void)n_head;
-  if (n_models <= 0) return 0;
-  return static_cast<size_t>(n_models) * head_images_workspace_bytes(n_tail, n_labels, D_, precision);
+  return ens_workspace_bytes(n_tail, n_labels, D_, n_models, precision);
 }
 
 extern "C" int mdg_bilinear_ensemble_profile(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
@@ -361,32 +255,18 @@ extern "C" int mdg_bilinear_ensemble_profile(const float* const* z_head, const f
                                              int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible,
                                              void* workspace, size_t workspace_bytes, void* stream) {
   const char* const fn = "mdg_bilinear_ensemble_profile";
-  MDG_CHECK_ARG(n_models >= 1 && n_models <= MAXK, "%s: n_models must be in 1..%d (got %d)", fn, MAXK, n_models);
-  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  int rc = ens_check_sizes(fn, n_models, n_head, n_tail, n_labels, D_, precision, eligible);
   if (rc != MDG_OK) return rc;
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3, "%s: precision %d not offered (MDG_PREC_F32 or MDG_PREC_BF16X3)", fn,
-                precision);
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 31) - BN, "%s: n_tail %lld does not fit the int32 column indices", fn, (long long)n_tail);
   MDG_CHECK_ARG(n_head <= int64_t(65535) * ENS_PRO_BM, "%s: n_head %lld > %lld rows per call", fn, (long long)n_head,
                 (long long)(int64_t(65535) * ENS_PRO_BM));
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail, "%s: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)",
-                fn, (long long)n_head, (long long)n_tail);
   MDG_CHECK_ARG(ldo >= n_tail, "%s: ldo %lld < n_tail %lld", fn, (long long)ldo, (long long)n_tail);
   if (n_head == 0 || n_tail == 0) return MDG_OK;
   MDG_CHECK_ARG(count && best && margin, "%s: null output pointer", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n_labels > 0) {
-    MDG_CHECK_ARG(z_head && z_tail && w_sym && thr, "%s: null pointer", fn);
-    for (int m = 0; m < n_models; ++m) {
-      MDG_CHECK_ARG(z_head[m] && z_tail[m] && w_sym[m], "%s: null pointer for model %d", fn, m);
-      MDG_CHECK_ARG(mdg_aligned16(z_head[m]) && mdg_aligned16(z_tail[m]) && mdg_aligned16(w_sym[m]),
-                    "%s: z_head, z_tail and w_sym must be 16-byte aligned (model %d)", fn, m);
-    }
-    const size_t need = mdg_bilinear_ensemble_profile_workspace_bytes(n_head, n_tail, n_labels, D_, n_models, precision);
-    if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-      mdg_set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", fn, need, workspace_bytes);
-      return MDG_EWORKSPACE;
-    }
+    rc = ens_check_operands(fn, z_head, z_tail, w_sym, n_models, thr != nullptr, n_tail, n_labels, precision, workspace, workspace_bytes);
+    if (rc != MDG_OK) return rc;
     // the cuts and scales are read back (at most 2 x 256 KB) and checked before anything is launched, as mdg_bilinear_profile does
     std::vector<float> host(static_cast<size_t>(n_labels) * (scale ? 2 : 1));
     hipError_t e = hipMemcpyAsync(host.data(), thr, static_cast<size_t>(n_labels) * 4, hipMemcpyDeviceToHost, st);
@@ -405,11 +285,7 @@ extern "C" int mdg_bilinear_ensemble_profile(const float* const* z_head, const f
     }
   }
   EnsProArgs a{};
-  for (int m = 0; m < MAXK; ++m) {
-    a.z_head[m] = n_labels > 0 ? z_head[m < n_models ? m : 0] : nullptr;
-    a.zt[m].nrows = n_tail;
-    a.w[m].nrows = D;
-  }
+  ens_fill_operands(a, n_labels > 0 ? z_head : nullptr, n_models, n_tail);
   a.thr = thr;
   a.scale = scale;
   a.count = count; a.best = best; a.margin = margin;

@@ -14,8 +14,8 @@
 //     T_m = z_head_m[rows] . W_sym_m[l] (build_t) for m = 0..K-1 and sweeps the chunk with it (compute_tile_spread), sigmoid
 //     1 / (1 + expf(-s)), the running sums of the chunk (psum, CH x 32 VGPRs) staying in registers across the models, divided once
 //     by K; the compare is on that quotient (P >= thr, not sum >= thr * K).  With K = 1 the one T is built for the first chunk only.
-//     build_t, pick, sigmoid_head and the two-buffer ring are copies: ensemble.hip and ensemble_topk.hip stay as they are (sharing
-//     sweep text has moved hipcc's schedule before).
+//     build_t, pick, sigmoid_head, the eligibility test and the layout's constants are ensemble_sweep.h's, shared by the family;
+//     the two-buffer ring is this file's own text (sharing sweep text has moved hipcc's schedule before).
 //   epilogue: select.hip's, run on the chunk's finished tiles after its last model, in ascending tile order.  The tile index of that
 //     loop is a run-time value and the tile's sums are picked by wave-uniform selects: ONE copy of the 32 inlined takes (DESIGN.md
 //     4af: six copies inside the unrolled stage loop sent psum to scratch).  Every wave owns 32 head rows, 32 lanes per row (the
@@ -47,20 +47,11 @@
 // retires in order for loads, and 0 covers everything).  A counted wait would have to bound those stores; the measurement
 //  shows no gap between the passes at a sparse cut that would pay for one.
 // No atomics, no LDS beyond the stage buffers and the slabs: bit-identical from launch to launch.
-#include "sweep_reduce.h"
+#include "ensemble_sweep.h"
 
 namespace {
 
-constexpr int MAXK = 8;
-constexpr int ENS_SEL_NW = 4;               // waves per workgroup, one per SIMD (512 VGPRs: T, the chunk's running sums, the counters)
-constexpr int ENS_SEL_CH = 6;               // tail tiles per chunk, as ensemble.hip and ensemble_topk.hip
-constexpr int SLAB_BYTES = 8192;            // per wave: [32 rows][64 columns] fp32, T half while rebuilding
-constexpr int ENS_SEL_LDS = 2 * STAGE_BYTES + ENS_SEL_NW * SLAB_BYTES;
-
-struct EnsSelArgs {
-  const float* z_head[MAXK];   // fp32 rows (T prologue)
-  TileSrc zt[MAXK];            // tail operand images (fp32, or hi/lo bf16)
-  TileSrc w[MAXK];             // W_sym images, all outcomes; nrows = D
+struct EnsSelArgs : EnsOperands {
   const float* thr;            // [n_labels]
   int* row_counts;             // count pass: [n_labels, n_head]
   const long long* row_ptr;    // fill pass: [n_labels * n_head + 1]
@@ -73,30 +64,6 @@ struct EnsSelArgs {
 
 template <bool MASKED> struct EnsSelKArgs : EnsSelArgs {};
 template <> struct EnsSelKArgs<true> : EnsSelArgs { PairMask mask; };
-
-// a[k] for a wave-uniform k without dynamic indexing of the kernel arguments (scalar selects)
-template <typename T>
-__device__ __forceinline__ T pick(const T (&a)[MAXK], int k) {
-  T v = a[0];
-#pragma unroll
-  for (int i = 1; i < MAXK; ++i)
-    if (k == i) v = a[i];
-  return v;
-}
-
-__device__ __forceinline__ float sigmoid_head(float s) { return 1.0f / (1.0f + expf(-s)); }   // MDG_EPI_STORE_SIGMOID's formula
-
-// Eligibility of the element in row wrow0 + lr, column tcol0 + lc of a tile from the tile's 32-bit distances (wave-uniform, clamped):
-// dcr = tcol0 - wrow0, nr = n_head - wrow0, nc = n_tail - tcol0.  select.hip's test: col - row keeps its sign and its zero through
-// the clamp; a lane's lr and lc differ from element to element by compile-time constants only.
-__device__ __forceinline__ int ens_sel_clamp(int64_t x) {
-  return static_cast<int>(x < -(int64_t(1) << 30) ? -(int64_t(1) << 30) : (x > (int64_t(1) << 30) ? (int64_t(1) << 30) : x));
-}
-__device__ __forceinline__ bool ens_sel_eligible(int mode, int lr, int lc, int dcr, int nr, int nc) {
-  const int d = dcr + lc - lr;                                                          // column - row
-  const bool pair = mode == MDG_TOPK_NOT_SELF ? d != 0 : d < 0;                         // (bitwise: selects, no branches)
-  return (lr < nr) & (lc < nc) & ((mode == MDG_TOPK_ALL) | pair);
-}
 
 // Hit path of one accumulator register: select.hip's select_take<32, FILL>.  Must be called in wave-uniform control flow.  The 32
 // lanes of one h share the row whose row_ptr entry is `rp` (FILL; read by lanes with a hit only); `run`: the row's hits so far.
@@ -118,81 +85,10 @@ __device__ __forceinline__ void ens_sel_take(const EnsSelArgs& p, unsigned& run,
   run += __builtin_popcount(mine);
 }
 
-// T = z_head[32 rows of this wave] . W_sym[l] -> At: ensemble.hip's build_t (k-outer loop nest, the head's products in the head's
-// order per accumulator element).  W_sym[l] is staged whole, rows 0..63 in stage buffer 0 and 64..127 in buffer 1.
-template <int MODE, int NW>
-__device__ __forceinline__ void build_t(AFrag<MODE>& At, const float* zrow, const TileSrc& wl, char* smem, char* slab, int tid,
-                                        int r, int h) {
-  {
-    u32x4 r0[32 / NW], r1[32 / NW];
-    stage_load<MODE, NW>(wl, 0, tid, r0);
-    stage_load<MODE, NW>(wl, 64, tid, r1);
-    __syncthreads();                                // every wave is done with the stage buffers
-    stage_write<MODE, NW>(smem, tid, r0);
-    stage_write<MODE, NW>(smem + STAGE_BYTES, tid, r1);
-    __syncthreads();
-  }
-  f32x16 acc[4];                                    // output columns 32 c .. 32 c + 31
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[c][v] = 0.f;
-  if constexpr (MODE == MDG_PREC_F32) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float4 a = *reinterpret_cast<const float4*>(zrow + 8 * q + 4 * h);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 b = *reinterpret_cast<const float4*>(smem + (c >> 1) * STAGE_BYTES + tile_off<512>(32 * (c & 1) + r, 2 * q + h));
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);          // one k step of operands live at a time
-    }
-  } else {
-    static_assert(MODE == MDG_PREC_BF16X3, "fp32 and split-bf16 operands");
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float4 v0 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h);
-      const float4 v1 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h + 4);
-      bf16x8 ahi, alo;
-      split8<MODE>(v0, v1, ahi, alo);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const char* lds = smem + (c >> 1) * STAGE_BYTES;
-        const int j = 32 * (c & 1) + r;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(j, 2 * s + h));
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lds + LO_OFF + tile_off<256>(j, 2 * s + h));
-        acc[c] = mma16<MODE>(alo, bh, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bl, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bh, acc[c]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // T (fp32) -> this wave's slab, one 64-column half at a time, and back as the A fragment (the head's afrag_from_slab)
-#pragma unroll
-  for (int st = 0; st < 2; ++st) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = acc_row(v, h), n = 32 * t + r;
-        *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[2 * st + t][v];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    afrag_from_slab<MODE>(At, slab, st, r, h);
-  }
-  __syncthreads();                                  // every wave is done reading W from the stage buffers
-}
-
 template <int MODE, bool FILL, bool MASKED, int CH>
-__global__ __launch_bounds__(64 * ENS_SEL_NW, 1) void ensemble_select_kernel(const EnsSelKArgs<MASKED> p) {
+__global__ __launch_bounds__(64 * ENS_NW, 1) void ensemble_select_kernel(const EnsSelKArgs<MASKED> p) {
   static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "the ensemble's precisions");
-  constexpr int NW = ENS_SEL_NW, BM = 32 * NW;
+  constexpr int NW = ENS_NW, BM = 32 * NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t l = blockIdx.y;
@@ -327,12 +223,12 @@ __global__ __launch_bounds__(64 * ENS_SEL_NW, 1) void ensemble_select_kernel(con
         const bool plain = tcol0 + BN <= p.n_tail && wrow0 + 32 <= p.n_head &&
                            (mode == MDG_TOPK_ALL || tcol0 + BN <= wrow0 || (mode == MDG_TOPK_NOT_SELF && tcol0 > wrow0 + 31));
         if (!plain) {
-          const int dcr = ens_sel_clamp(tcol0 - wrow0), nr = ens_sel_clamp(p.n_head - wrow0), ncl = ens_sel_clamp(p.n_tail - tcol0);
+          const int dcr = ens_clamp(tcol0 - wrow0), nr = ens_clamp(p.n_head - wrow0), ncl = ens_clamp(p.n_tail - tcol0);
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v)
-              pr[t][v] = ens_sel_eligible(mode, acc_row(v, h), 32 * t + r, dcr, nr, ncl) ? pr[t][v] : __builtin_nanf("");
+              pr[t][v] = ens_eligible(mode,acc_row(v, h), 32 * t + r, dcr, nr, ncl) ? pr[t][v] : __builtin_nanf("");
         }
         if constexpr (MASKED) {
           if (__ballot((w0 | w1) != 0u) != 0) {                                // wave-uniform: a tile without a known pair costs this ballot
@@ -374,47 +270,27 @@ __global__ __launch_bounds__(64 * ENS_SEL_NW, 1) void ensemble_select_kernel(con
 template <int MODE, bool FILL, bool MASKED>
 int launch_ens_select(EnsSelKArgs<MASKED>& a, const float* const* z_tail, const float* const* w_sym, int64_t n_labels, char* ws,
                       hipStream_t st, const char* fn) {
-  // per model the operand images of the single-model head (zhi | whi | zlo | wlo), one after the other
-  const size_t per = head_images_workspace_bytes(a.n_tail, n_labels, D, MODE);
-  for (int m = 0; m < a.n_models; ++m)
-    make_head_images<MODE>(a.zt[m], a.w[m], z_tail[m], w_sym[m], a.n_tail, n_labels, ws ? ws + m * per : nullptr, st);
-  MDG_CHECK_LAUNCH(fn);
-  for (int m = a.n_models; m < MAXK; ++m) { a.zt[m] = a.zt[0]; a.w[m] = a.w[0]; }      // unused slots repeat model 0 (never read)
-  const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 32 * ENS_SEL_NW)), static_cast<unsigned>(n_labels));
-  hipLaunchKernelGGL((ensemble_select_kernel<MODE, FILL, MASKED, ENS_SEL_CH>), grid, dim3(64 * ENS_SEL_NW), ENS_SEL_LDS, st, a);
+  const int rc = ens_make_images<MODE>(a, z_tail, w_sym, a.n_models, a.n_tail, n_labels, ws, st, fn);
+  if (rc != MDG_OK) return rc;
+  const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 32 * ENS_NW)), static_cast<unsigned>(n_labels));
+  hipLaunchKernelGGL((ensemble_select_kernel<MODE, FILL, MASKED, ENS_CH>), grid, dim3(64 * ENS_NW), ENS_LDS, st, a);
   MDG_CHECK_LAUNCH(fn);
   return MDG_OK;
 }
 
-// The checks both entry points share (mdg_bilinear_ensemble_topk's minus k); `outputs`: none of the pass's own pointers is null.
-// Returns MDG_OK with *launch = false when there is nothing to do.
+// The checks both entry points share; `outputs`: none of the pass's own pointers is null.  Returns MDG_OK with *launch = false when
+// there is nothing to do.
 int ens_select_check(const char* fn, const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
                      const float* thr, bool outputs, int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int precision, int eligible,
                      void* workspace, size_t workspace_bytes, bool* launch) {
   *launch = false;
-  MDG_CHECK_ARG(n_models >= 1 && n_models <= MAXK, "%s: n_models must be in 1..%d (got %d)", fn, MAXK, n_models);
-  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  int rc = ens_check_sizes(fn, n_models, n_head, n_tail, n_labels, D_, precision, eligible);
   if (rc != MDG_OK) return rc;
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3, "%s: precision %d not offered (MDG_PREC_F32 or MDG_PREC_BF16X3)", fn,
-                precision);
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 31) - BN, "%s: n_tail %lld does not fit the int32 column indices", fn, (long long)n_tail);
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail, "%s: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)",
-                fn, (long long)n_head, (long long)n_tail);
   if (n_head == 0 || n_labels == 0) return MDG_OK;
-  MDG_CHECK_ARG(n_tail >= 1, "%s: n_tail must be at least 1", fn);
-  MDG_CHECK_ARG(z_head && z_tail && w_sym && thr && outputs, "%s: null pointer", fn);
-  for (int m = 0; m < n_models; ++m) {
-    MDG_CHECK_ARG(z_head[m] && z_tail[m] && w_sym[m], "%s: null pointer for model %d", fn, m);
-    MDG_CHECK_ARG(mdg_aligned16(z_head[m]) && mdg_aligned16(z_tail[m]) && mdg_aligned16(w_sym[m]),
-                  "%s: z_head, z_tail and w_sym must be 16-byte aligned (model %d)", fn, m);
-  }
-  const size_t need = mdg_bilinear_ensemble_select_workspace_bytes(n_head, n_tail, n_labels, D_, n_models, precision);
-  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-    mdg_set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", fn, need, workspace_bytes);
-    return MDG_EWORKSPACE;
-  }
-  *launch = true;
-  return MDG_OK;
+  rc = ens_check_operands(fn, z_head, z_tail, w_sym, n_models, thr && outputs, n_tail, n_labels, precision, workspace, workspace_bytes);
+  *launch = rc == MDG_OK;
+  return rc;
 }
 
 template <bool FILL, bool MASKED>
@@ -426,11 +302,7 @@ int ens_select_run(const char* fn, const float* const* z_head, const float* cons
     const int mrc = sweep_mask_args(fn, a.mask, mask, plane_stride, n_head, n_tail);
     if (mrc != MDG_OK) return mrc;
   }
-  for (int m = 0; m < MAXK; ++m) {
-    a.z_head[m] = z_head[m < n_models ? m : 0];
-    a.zt[m].nrows = n_tail;
-    a.w[m].nrows = D;
-  }
+  ens_fill_operands(a, z_head, n_models, n_tail);
   a.thr = thr;
   a.row_counts = row_counts;
   a.row_ptr = reinterpret_cast<const long long*>(row_ptr);
@@ -450,8 +322,7 @@ int ens_select_run(const char* fn, const float* const* z_head, const float* cons
 extern "C" size_t mdg_bilinear_ensemble_select_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_models,
                                                                int precision) {
   (void)n_head;
-  if (n_models <= 0) return 0;
-  return static_cast<size_t>(n_models) * head_images_workspace_bytes(n_tail, n_labels, D_, precision);
+  return ens_workspace_bytes(n_tail, n_labels, D_, n_models, precision);
 }
 
 extern "C" int mdg_bilinear_ensemble_select_count(const float* const* z_head, const float* const* z_tail, const float* const* w_sym,

@@ -12,8 +12,9 @@
 //   score arithmetic: ensemble.hip's general (non-symmetric) sweep, bit for bit.  A workgroup (4 waves, 128 head rows of one
 //     outcome, one wave per SIMD) walks its tail tiles in chunks of CH; for every chunk it rebuilds T_m = z_head_m[rows] . W_sym_m[l]
 //     (build_t) for m = 0..K-1 and sweeps the chunk with it (compute_tile_spread), sigmoid 1 / (1 + expf(-s)), the running sums of
-//     the chunk (CH x 32 VGPRs) staying in registers across the models, divided once by K.  build_t, pick and sigmoid_head are
-//     copies of ensemble.hip's: that file stays as it is (sharing sweep text has moved hipcc's schedule before).
+//     the chunk (CH x 32 VGPRs) staying in registers across the models, divided once by K.  build_t, pick, sigmoid_head and the
+//     layout's constants are ensemble_sweep.h's, shared with ensemble.hip; the two-buffer ring is this file's own text (sharing
+//     sweep text has moved hipcc's schedule before).
 //     With K = 1 the one T stays resident: it is built for the first chunk only.
 //   epilogue: topk.hip's, run on the chunk's finished tiles after its last model, in ascending tile order.  Every wave owns 32 head
 //     rows; a row's sorted list lives in its 32 lanes (topk_list.h: lv / li / thr per accumulator register).  Ineligible, out-of-range
@@ -30,21 +31,12 @@
 // Waits: the kernel stores nothing inside the sweep; per wave the only vector-memory operations in flight at a stage barrier are
 // the LDS-DMAs of the tile about to be read, so every stage waits vmcnt(0).  (ensemble.hip's vmcnt(32) counts stores that do not
 // exist here.)  No atomics, no memory traffic besides the final k stores per row: bit-identical from launch to launch.
-#include "sweep_reduce.h"
+#include "ensemble_sweep.h"
 #include "topk_list.h"
 
 namespace {
 
-constexpr int MAXK = 8;
-constexpr int ENS_TOPK_NW = 4;              // waves per workgroup, one per SIMD (512 VGPRs: T, the chunk's running sums, the lists)
-constexpr int ENS_TOPK_CH = 6;              // tail tiles per chunk, as ensemble.hip
-constexpr int SLAB_BYTES = 8192;            // per wave: [32 rows][64 columns] fp32, T half while rebuilding
-constexpr int ENS_TOPK_LDS = 2 * STAGE_BYTES + ENS_TOPK_NW * SLAB_BYTES;
-
-struct EnsTopkArgs {
-  const float* z_head[MAXK];   // fp32 rows (T prologue)
-  TileSrc zt[MAXK];            // tail operand images (fp32, or hi/lo bf16)
-  TileSrc w[MAXK];             // W_sym images, all outcomes; nrows = D
+struct EnsTopkArgs : EnsOperands {
   float* vals;                 // [n_labels, n_head, k]
   int* idx;                    // [n_labels, n_head, k]
   int64_t n_head, n_tail;
@@ -56,97 +48,14 @@ struct EnsTopkArgs {
 template <bool MASKED> struct EnsTopkKArgs : EnsTopkArgs {};
 template <> struct EnsTopkKArgs<true> : EnsTopkArgs { PairMask mask; };
 
-// a[k] for a wave-uniform k without dynamic indexing of the kernel arguments (scalar selects)
-template <typename T>
-__device__ __forceinline__ T pick(const T (&a)[MAXK], int k) {
-  T v = a[0];
-#pragma unroll
-  for (int i = 1; i < MAXK; ++i)
-    if (k == i) v = a[i];
-  return v;
-}
-
-__device__ __forceinline__ float sigmoid_head(float s) { return 1.0f / (1.0f + expf(-s)); }   // MDG_EPI_STORE_SIGMOID's formula
-
 __device__ __forceinline__ bool ens_topk_eligible(int mode, int64_t row, int64_t col, int64_t n_tail) {
   return col < n_tail && (mode == MDG_TOPK_ALL || (mode == MDG_TOPK_NOT_SELF ? col != row : col < row));
 }
 
-// T = z_head[32 rows of this wave] . W_sym[l] -> At: ensemble.hip's build_t (k-outer loop nest, the head's products in the head's
-// order per accumulator element).  W_sym[l] is staged whole, rows 0..63 in stage buffer 0 and 64..127 in buffer 1.
-template <int MODE, int NW>
-__device__ __forceinline__ void build_t(AFrag<MODE>& At, const float* zrow, const TileSrc& wl, char* smem, char* slab, int tid,
-                                        int r, int h) {
-  {
-    u32x4 r0[32 / NW], r1[32 / NW];
-    stage_load<MODE, NW>(wl, 0, tid, r0);
-    stage_load<MODE, NW>(wl, 64, tid, r1);
-    __syncthreads();                                // every wave is done with the stage buffers
-    stage_write<MODE, NW>(smem, tid, r0);
-    stage_write<MODE, NW>(smem + STAGE_BYTES, tid, r1);
-    __syncthreads();
-  }
-  f32x16 acc[4];                                    // output columns 32 c .. 32 c + 31
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[c][v] = 0.f;
-  if constexpr (MODE == MDG_PREC_F32) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float4 a = *reinterpret_cast<const float4*>(zrow + 8 * q + 4 * h);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float4 b = *reinterpret_cast<const float4*>(smem + (c >> 1) * STAGE_BYTES + tile_off<512>(32 * (c & 1) + r, 2 * q + h));
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);          // one k step of operands live at a time
-    }
-  } else {
-    static_assert(MODE == MDG_PREC_BF16X3, "fp32 and split-bf16 operands");
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float4 v0 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h);
-      const float4 v1 = *reinterpret_cast<const float4*>(zrow + 16 * s + 8 * h + 4);
-      bf16x8 ahi, alo;
-      split8<MODE>(v0, v1, ahi, alo);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const char* lds = smem + (c >> 1) * STAGE_BYTES;
-        const int j = 32 * (c & 1) + r;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(lds + tile_off<256>(j, 2 * s + h));
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lds + LO_OFF + tile_off<256>(j, 2 * s + h));
-        acc[c] = mma16<MODE>(alo, bh, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bl, acc[c]);
-        acc[c] = mma16<MODE>(ahi, bh, acc[c]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // T (fp32) -> this wave's slab, one 64-column half at a time, and back as the A fragment (the head's afrag_from_slab)
-#pragma unroll
-  for (int st = 0; st < 2; ++st) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = acc_row(v, h), n = 32 * t + r;
-        *reinterpret_cast<float*>(slab + tile_off<256>(row, n >> 2) + (n & 3) * 4) = acc[2 * st + t][v];
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    afrag_from_slab<MODE>(At, slab, st, r, h);
-  }
-  __syncthreads();                                  // every wave is done reading W from the stage buffers
-}
-
 template <int MODE, bool MASKED, int CH>
-__global__ __launch_bounds__(64 * ENS_TOPK_NW, 1) void ensemble_topk_kernel(const EnsTopkKArgs<MASKED> p) {
+__global__ __launch_bounds__(64 * ENS_NW, 1) void ensemble_topk_kernel(const EnsTopkKArgs<MASKED> p) {
   static_assert(MODE == MDG_PREC_F32 || MODE == MDG_PREC_BF16X3, "the ensemble's precisions");
-  constexpr int NW = ENS_TOPK_NW, BM = 32 * NW;
+  constexpr int NW = ENS_NW, BM = 32 * NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t l = blockIdx.y;
@@ -330,14 +239,10 @@ template <int MODE, bool MASKED>
 int launch_ens_topk(EnsTopkKArgs<MASKED>& a, const float* const* z_tail, const float* const* w_sym, int64_t n_labels, char* ws,
                     hipStream_t st) {
   const char* const fn = "mdg_bilinear_ensemble_topk";
-  // per model the operand images of the single-model head (zhi | whi | zlo | wlo), one after the other
-  const size_t per = head_images_workspace_bytes(a.n_tail, n_labels, D, MODE);
-  for (int m = 0; m < a.n_models; ++m)
-    make_head_images<MODE>(a.zt[m], a.w[m], z_tail[m], w_sym[m], a.n_tail, n_labels, ws ? ws + m * per : nullptr, st);
-  MDG_CHECK_LAUNCH("mdg_bilinear_ensemble_topk(operand images)");
-  for (int m = a.n_models; m < MAXK; ++m) { a.zt[m] = a.zt[0]; a.w[m] = a.w[0]; }      // unused slots repeat model 0 (never read)
-  const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 32 * ENS_TOPK_NW)), static_cast<unsigned>(n_labels));
-  hipLaunchKernelGGL((ensemble_topk_kernel<MODE, MASKED, ENS_TOPK_CH>), grid, dim3(64 * ENS_TOPK_NW), ENS_TOPK_LDS, st, a);
+  const int rc = ens_make_images<MODE>(a, z_tail, w_sym, a.n_models, a.n_tail, n_labels, ws, st, "mdg_bilinear_ensemble_topk(operand images)");
+  if (rc != MDG_OK) return rc;
+  const dim3 grid(static_cast<unsigned>(mdg_cdiv(a.n_head, 32 * ENS_NW)), static_cast<unsigned>(n_labels));
+  hipLaunchKernelGGL((ensemble_topk_kernel<MODE, MASKED, ENS_CH>), grid, dim3(64 * ENS_NW), ENS_LDS, st, a);
   MDG_CHECK_LAUNCH(fn);
   return MDG_OK;
 }
@@ -351,11 +256,7 @@ int ens_topk_run(const float* const* z_head, const float* const* z_tail, const f
     const int mrc = sweep_mask_args("mdg_bilinear_ensemble_topk", a.mask, mask, plane_stride, n_head, n_tail);
     if (mrc != MDG_OK) return mrc;
   }
-  for (int m = 0; m < MAXK; ++m) {
-    a.z_head[m] = z_head[m < n_models ? m : 0];
-    a.zt[m].nrows = n_tail;
-    a.w[m].nrows = D;
-  }
+  ens_fill_operands(a, z_head, n_models, n_tail);
   a.vals = vals;
   a.idx = idx;
   a.n_head = n_head; a.n_tail = n_tail;
@@ -370,13 +271,12 @@ int ens_topk_run(const float* const* z_head, const float* const* z_tail, const f
 
 }  // namespace
 
-extern "C" int mdg_bilinear_ensemble_topk_chunk_tiles(void) { return ENS_TOPK_CH; }
+extern "C" int mdg_bilinear_ensemble_topk_chunk_tiles(void) { return ENS_CH; }
 
 extern "C" size_t mdg_bilinear_ensemble_topk_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D_, int n_models,
                                                              int precision) {
   (void)n_head;
-  if (n_models <= 0) return 0;
-  return static_cast<size_t>(n_models) * head_images_workspace_bytes(n_tail, n_labels, D_, precision);
+  return ens_workspace_bytes(n_tail, n_labels, D_, n_models, precision);
 }
 
 extern "C" int mdg_bilinear_ensemble_topk(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
@@ -384,30 +284,14 @@ extern "C" int mdg_bilinear_ensemble_topk(const float* const* z_head, const floa
                                           int precision, int k, int eligible, void* workspace, size_t workspace_bytes, void* stream,
                                           const uint32_t* mask, int64_t plane_stride) {
   const char* const fn = "mdg_bilinear_ensemble_topk";
-  MDG_CHECK_ARG(n_models >= 1 && n_models <= MAXK, "mdg_bilinear_ensemble_topk: n_models must be in 1..%d (got %d)", MAXK, n_models);
-  const int rc = sweep_check_sizes(fn, n_head, n_tail, n_labels, D_, precision, eligible);
+  int rc = ens_check_sizes(fn, n_models, n_head, n_tail, n_labels, D_, precision, eligible);
   if (rc != MDG_OK) return rc;
-  MDG_CHECK_ARG(precision == MDG_PREC_F32 || precision == MDG_PREC_BF16X3,
-                "mdg_bilinear_ensemble_topk: precision %d not offered (MDG_PREC_F32 or MDG_PREC_BF16X3)", precision);
   MDG_CHECK_ARG(k >= 1 && k <= TOPK_MAX_K, "mdg_bilinear_ensemble_topk: k must be in 1..%d (got %d)", TOPK_MAX_K, k);
   MDG_CHECK_ARG(n_tail < (int64_t(1) << 31) - BN, "mdg_bilinear_ensemble_topk: n_tail %lld does not fit the int32 column indices",
                 (long long)n_tail);
-  MDG_CHECK_ARG(eligible == MDG_TOPK_ALL || n_head == n_tail,
-                "mdg_bilinear_ensemble_topk: NOT_SELF / LOWER need one drug set against itself (n_head %lld != n_tail %lld)", (long long)n_head,
-                (long long)n_tail);
   if (n_head == 0 || n_labels == 0) return MDG_OK;
-  MDG_CHECK_ARG(n_tail >= 1, "mdg_bilinear_ensemble_topk: n_tail must be at least 1");
-  MDG_CHECK_ARG(z_head && z_tail && w_sym && vals && idx, "mdg_bilinear_ensemble_topk: null pointer");
-  for (int m = 0; m < n_models; ++m) {
-    MDG_CHECK_ARG(z_head[m] && z_tail[m] && w_sym[m], "mdg_bilinear_ensemble_topk: null pointer for model %d", m);
-    MDG_CHECK_ARG(mdg_aligned16(z_head[m]) && mdg_aligned16(z_tail[m]) && mdg_aligned16(w_sym[m]),
-                  "mdg_bilinear_ensemble_topk: z_head, z_tail and w_sym must be 16-byte aligned (model %d)", m);
-  }
-  const size_t need = mdg_bilinear_ensemble_topk_workspace_bytes(n_head, n_tail, n_labels, D_, n_models, precision);
-  if (need && (!workspace || workspace_bytes < need || !mdg_aligned16(workspace))) {
-    mdg_set_error("mdg_bilinear_ensemble_topk: workspace of %zu bytes (16-byte aligned) required, got %zu", need, workspace_bytes);
-    return MDG_EWORKSPACE;
-  }
+  rc = ens_check_operands(fn, z_head, z_tail, w_sym, n_models, vals && idx, n_tail, n_labels, precision, workspace, workspace_bytes);
+  if (rc != MDG_OK) return rc;
   if (!mask)
     return ens_topk_run<false>(z_head, z_tail, w_sym, n_models, vals, idx, n_head, n_tail, n_labels, precision, k, eligible, workspace, stream,
                                nullptr, 0);

@@ -743,33 +743,79 @@ def outcome_topk_merge(a, b, *, largest: bool = True):
 ENSEMBLE_PRECISIONS ={"f32": PREC_F32, "bf16x3": PREC_BF16X3}
 
 
+def _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible="all", own=()):
+    """What every ``bilinear_ensemble_*`` wrapper checks about its model lists, shapes first, on whatever device the tensors live:
+    1..8 models, three lists of one length, the precision and eligible names, float32 tensors of the right rank (model 0's and the
+    product's ``own``: ``(tensor, name, ndim)`` each), every model shaped as model 0, one drug set under a restricted ``eligible``
+    -> (zh, zt, ws) as lists."""
+    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
+    K = len(zh)
+    if not 1 <= K <= 8:
+        raise ValueError(f"{what}: 1..8 models, got {K}")
+    if len(zt) != K or len(ws) != K:
+        raise ValueError(f"{what}: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
+    if precision not in ENSEMBLE_PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    for t, name, nd in ((zh[0], "z_heads[0]", 2), (zt[0], "z_tails[0]", 2), (ws[0], "w_syms[0]", 3), *own):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    L, D = ws[0].shape[0], ws[0].shape[1]
+    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
+    for m in range(K):
+        if tuple(zh[m].shape) != (Nh, D) or tuple(zt[m].shape) != (Nt, D) or tuple(ws[m].shape) != (L, D, D):
+            raise ValueError(f"{what}: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
+                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    return zh, zt, ws
+
+
+def _ensemble_on_gpu(what, zh, zt, ws, *own):
+    """The lists of ``_ensemble_models`` and the product's ``own`` ``(tensor, name, ndim)`` as contiguous fp32 GPU tensors on one
+    device -> (zh, zt, ws, *own)."""
+    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
+    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
+    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
+    own = [_f32_cuda(t, name, nd) for t, name, nd in own]
+    dev = zh[0].device
+    if any(t.device != dev for t in (*zh, *zt, *ws, *own)):
+        raise ValueError(f"{what}: every tensor must be on the same device")
+    return (zh, zt, ws, *own)
+
+
+def _ensemble_calls(product, zh, zt, ws, prec, one_call) -> None:
+    """All outcomes through an entry point of ``product`` (sigmoid, topk, select, bincount), 65 535 per call: the grid's y extent.
+    ``one_call(lo, n, models, scratch)`` makes the call for the ``n`` outcomes from ``lo`` on; ``models`` = the three pointer
+    arrays and K, the entry point's first arguments, ``scratch`` = workspace, its size and the stream, the ones after ``precision``
+    (and ``eligible``)."""
+    K, L, D, Nh, Nt = len(zh), ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
+    dev = zh[0].device
+    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
+    a_h, a_t = arr(zh), arr(zt)
+    for lo in range(0, L, 65535):
+        n = min(L, lo + 65535) - lo
+        wsp, nbytes = _scratch(f"mdg_bilinear_ensemble_{product}_workspace_bytes", dev, Nh, Nt, n, D, K, prec)
+        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
+        one_call(lo, n, (a_h, a_t, a_w, K), (_ptr(wsp), nbytes, _stream(zh[0])))
+
+
 def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Checkpoint ensemble of the all-pairs head: P[l,i,j] = mean_k sigmoid(z_heads[k][i]^T w_syms[k][l] z_tails[k][j]) -> [L,Nh,Nt]
     fp32 (madrigal/evaluate/predict.py:466-499, 582-614), K = len(z_heads) in 1..8, one launch.  Per model the logit is
     ``bilinear_allpairs``'s own arithmetic in ``precision`` ("f32" or "bf16x3"); the sigmoids are summed in model order and divided
     once by K.  When ``z_heads[k] is z_tails[k]`` for every k (one drug set against itself) the symmetric sweep runs and every
     P[l] is exactly symmetric.  ``out``: None (an ``empty_scores`` tensor) or a contiguous / row-pitched fp32 GPU tensor."""
-    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
-    K = len(zh)
-    if not 1 <= K <= 8:
-        raise ValueError(f"bilinear_ensemble_sigmoid: 1..8 models, got {K}")
-    if len(zt) != K or len(ws) != K:
-        raise ValueError(f"bilinear_ensemble_sigmoid: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
-    if precision not in ENSEMBLE_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
+    what = "bilinear_ensemble_sigmoid"
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision)
     sym = all(a is b for a, b in zip(zh, zt))
-    zh = [_f32_cuda(t, f"z_heads[{k}]", 2) for k, t in enumerate(zh)]
-    zt = zh if sym else [_f32_cuda(t, f"z_tails[{k}]", 2) for k, t in enumerate(zt)]
-    ws = [_f32_cuda(t, f"w_syms[{k}]", 3) for k, t in enumerate(ws)]
-    L, D = ws[0].shape[0], ws[0].shape[1]
-    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
+    zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
+    if sym:
+        zt = zh                                    # the library tells the symmetric sweep by the pointers
+    L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
     dev = zh[0].device
-    for k in range(K):
-        if zh[k].shape != (Nh, D) or zt[k].shape != (Nt, D) or ws[k].shape != (L, D, D):
-            raise ValueError(f"bilinear_ensemble_sigmoid: model {k} has z_head {tuple(zh[k].shape)}, z_tail {tuple(zt[k].shape)}, "
-                             f"w_sym {tuple(ws[k].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
-        if zh[k].device != dev or zt[k].device != dev or ws[k].device != dev:
-            raise ValueError("bilinear_ensemble_sigmoid: every tensor must be on the same device")
     shape = (L, Nh, Nt)
     if out is None:
         out = empty_scores(L, Nh, Nt, dev)
@@ -778,14 +824,8 @@ def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", o
         raise ValueError(f"out: expected a float32 GPU tensor {shape}, contiguous or row-pitched (empty_scores)")
     ldo = out.stride(1) if out.numel() else Nt
     prec = ENSEMBLE_PRECISIONS[precision]
-    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
-    a_h, a_t = arr(zh), arr(zt)
-    for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
-        hi = min(L, lo + 65535)
-        wsp, nbytes = _scratch("mdg_bilinear_ensemble_sigmoid_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
-        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
-        call("mdg_bilinear_ensemble_sigmoid", a_h, a_t, a_w, K, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt, hi - lo, D, prec, _ptr(wsp),
-             nbytes, _stream(zh[0]))
+    _ensemble_calls("sigmoid", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+        "mdg_bilinear_ensemble_sigmoid", *models, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt, n, D, prec, *scratch))
     return out
 
 
@@ -805,33 +845,14 @@ def bilinear_ensemble_topk(z_heads, z_tails, w_syms, k: int, *, eligible: str = 
     K = len(z_heads) in 1..8.  P is bit for bit what ``bilinear_ensemble_sigmoid``'s general sweep writes in the same
     ``precision`` ("f32" or "bf16x3") -- the sweep it runs when the head is not the tail object, e.g. a row subset.  ``eligible``,
     ``k``, ``out`` and ``exclude`` as ``bilinear_topk``."""
-    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
-    K = len(zh)
-    if not 1 <= K <= 8:
-        raise ValueError(f"bilinear_ensemble_topk: 1..8 models, got {K}")
-    if len(zt) != K or len(ws) != K:
-        raise ValueError(f"bilinear_ensemble_topk: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
-    if precision not in ENSEMBLE_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    what = "bilinear_ensemble_topk"
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible)
     max_k = bilinear_topk_max_k()
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
         raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
-    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
-    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
-    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
-    L, D = ws[0].shape[0], ws[0].shape[1]
-    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
+    zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
+    L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
     dev = zh[0].device
-    for m in range(K):
-        if zh[m].shape != (Nh, D) or zt[m].shape != (Nt, D) or ws[m].shape != (L, D, D):
-            raise ValueError(f"bilinear_ensemble_topk: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
-                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
-        if zh[m].device != dev or zt[m].device != dev or ws[m].device != dev:
-            raise ValueError("bilinear_ensemble_topk: every tensor must be on the same device")
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
     mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
     shape = (L, Nh, k)
     if out is None:
@@ -849,74 +870,36 @@ def bilinear_ensemble_topk(z_heads, z_tails, w_syms, k: int, *, eligible: str = 
         idx.fill_(-1)
         return vals, idx
     prec = ENSEMBLE_PRECISIONS[precision]
-    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
-    a_h, a_t = arr(zh), arr(zt)
-    for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
-        hi = min(L, lo + 65535)
-        wsp, nbytes = _scratch("mdg_bilinear_ensemble_topk_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
-        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
-        call("mdg_bilinear_ensemble_topk", a_h, a_t, a_w, K, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt,
-             hi - lo, D, prec, int(k), TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]),
-             None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride)
+    _ensemble_calls("topk", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+        "mdg_bilinear_ensemble_topk", *models, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, n, D, prec, int(k),
+        TOPK_ELIGIBLE[eligible], *scratch, None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
     return vals, idx
 
 
 def _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=True):
-    """Validation shared by ``bilinear_ensemble_select_count`` and ``bilinear_ensemble_select``: the lists, the names and the
-    thresholds first (on whatever device the tensors live), then the device -> (zh, zt, ws, thr, precision code).
-    ``nan_check_on_device=False``: the caller reads the NaN flag of GPU thresholds itself, together with another value."""
-    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
-    K = len(zh)
-    if not 1 <= K <= 8:
-        raise ValueError(f"{what}: 1..8 models, got {K}")
-    if len(zt) != K or len(ws) != K:
-        raise ValueError(f"{what}: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
-    if precision not in ENSEMBLE_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
-    for t, name, nd in ((zh[0], "z_heads[0]", 2), (zt[0], "z_tails[0]", 2), (ws[0], "w_syms[0]", 3), (thresholds, "thresholds", 1)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
-            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    """Validation shared by ``bilinear_ensemble_select_count``, ``bilinear_ensemble_select`` and ``bilinear_ensemble_profile``: the
+    lists, the names and the thresholds first (on whatever device the tensors live), then the device -> (zh, zt, ws, thr, precision
+    code).  ``nan_check_on_device=False``: the caller reads the NaN flag of GPU thresholds itself, together with another value."""
+    own = (thresholds, "thresholds", 1)
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible, (own,))
     forward_only(*zh, *zt, *ws, thresholds)
-    L, D = ws[0].shape[0], ws[0].shape[1]
-    Nh, Nt = zh[0].shape[0], zt[0].shape[0]
-    for m in range(K):
-        if tuple(zh[m].shape) != (Nh, D) or tuple(zt[m].shape) != (Nt, D) or tuple(ws[m].shape) != (L, D, D):
-            raise ValueError(f"{what}: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
-                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+    L, Nt = ws[0].shape[0], zt[0].shape[0]
     if thresholds.shape[0] != L:
         raise ValueError(f"thresholds: expected [{L}] (one cut per outcome), got {tuple(thresholds.shape)}")
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
     if Nt >= (1 << 31) - 64:
         raise ValueError(f"z_tails: {Nt} rows do not fit the int32 column indices")
     if L and (nan_check_on_device or not thresholds.is_cuda) and bool(torch.isnan(thresholds).any()):
         raise ValueError(_SELECT_NAN)
-    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
-    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
-    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
-    thr = _f32_cuda(thresholds, "thresholds", 1)
-    dev = zh[0].device
-    if any(t.device != dev for t in (*zh, *zt, *ws, thr)):
-        raise ValueError(f"{what}: every tensor must be on the same device")
-    return zh, zt, ws, thr, ENSEMBLE_PRECISIONS[precision]
+    return (*_ensemble_on_gpu(what, zh, zt, ws, own), ENSEMBLE_PRECISIONS[precision])
 
 
 def _ensemble_select_sweep(entry, zh, zt, ws, thr, prec, eligible, mask, mstride, outputs) -> None:
-    """One pass (``entry``: mdg_bilinear_ensemble_select_count / _fill) over all outcomes, 65 535 per call (the grid's y extent).
-    ``outputs(lo)``: the pass's own pointer arguments for the outcomes from ``lo`` on."""
-    K, L, D, Nh, Nt = len(zh), ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
-    dev = zh[0].device
-    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
-    a_h, a_t = arr(zh), arr(zt)
-    for lo in range(0, L, 65535):
-        hi = min(L, lo + 65535)
-        wsp, nbytes = _scratch("mdg_bilinear_ensemble_select_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
-        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
-        call(entry, a_h, a_t, a_w, K, thr.data_ptr() + lo * 4, *outputs(lo), Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(wsp),
-             nbytes, _stream(zh[0]), None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride)
+    """One pass (``entry``: mdg_bilinear_ensemble_select_count / _fill) over all outcomes.  ``outputs(lo)``: the pass's own pointer
+    arguments for the outcomes from ``lo`` on."""
+    Nh, Nt, D = zh[0].shape[0], zt[0].shape[0], ws[0].shape[1]
+    _ensemble_calls("select", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+        entry, *models, thr.data_ptr() + lo * 4, *outputs(lo), Nh, Nt, n, D, prec, TOPK_ELIGIBLE[eligible], *scratch,
+        None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
 
 
 def _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride, out=None) -> torch.Tensor:
@@ -1012,48 +995,24 @@ def bilinear_ensemble_bincount(z_heads, z_tails, w_syms, edges: torch.Tensor, *,
     those whose bit is set (the known pairs); a bit of an ineligible pair changes nothing.  Nothing is excluded: ``result.sum(0)`` is
     the call without ``split``, exactly."""
     what = "bilinear_ensemble_bincount"
-    zh, zt, ws = list(z_heads), list(z_tails), list(w_syms)
-    K = len(zh)
-    if not 1 <= K <= 8:
-        raise ValueError(f"{what}: 1..8 models, got {K}")
-    if len(zt) != K or len(ws) != K:
-        raise ValueError(f"{what}: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
-    if precision not in ENSEMBLE_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
     # shapes and edge values first (on whatever device the tensors live), then the device: a bad call says what is wrong with it
-    for t, name, nd in ((zh[0], "z_heads[0]", 2), (zt[0], "z_tails[0]", 2), (ws[0], "w_syms[0]", 3), (edges, "edges", 2)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
-            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    own = (edges, "edges", 2)
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible, (own,))
     forward_only(*zh, *zt, *ws, edges)
-    L, D = ws[0].shape[0], ws[0].shape[1]
-    Nh, Nt, B = zh[0].shape[0], zt[0].shape[0], edges.shape[1]
-    for m in range(K):
-        if tuple(zh[m].shape) != (Nh, D) or tuple(zt[m].shape) != (Nt, D) or tuple(ws[m].shape) != (L, D, D):
-            raise ValueError(f"{what}: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
-                             f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
+    L, D, Nh, Nt, B = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0], edges.shape[1]
     max_edges = bilinear_bincount_max_edges()
     if edges.shape[0] != L:
         raise ValueError(f"edges: expected [{L}, B] (one row per outcome), got {tuple(edges.shape)}")
     if not 1 <= B <= max_edges:
         raise ValueError(f"edges: expected 1..{max_edges} edges per outcome, got {B}")
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
     if Nt >= 1 << 23:
         raise ValueError(f"z_tails: {Nt} rows; the 32-bit workgroup counters hold fewer than 2^23")
     if L and not bool(torch.isfinite(edges).all()):
         raise ValueError("edges: must be finite")
     if L and not bool((edges[:, 1:] >= edges[:, :-1]).all()):
         raise ValueError("edges: must be ascending within every outcome (unsorted edges give unspecified counts)")
-    zh = [_f32_cuda(t, f"z_heads[{m}]", 2) for m, t in enumerate(zh)]
-    zt = [_f32_cuda(t, f"z_tails[{m}]", 2) for m, t in enumerate(zt)]
-    ws = [_f32_cuda(t, f"w_syms[{m}]", 3) for m, t in enumerate(ws)]
-    e = _f32_cuda(edges, "edges", 2)
+    zh, zt, ws, e = _ensemble_on_gpu(what, zh, zt, ws, own)
     dev = zh[0].device
-    if any(t.device != dev for t in (*zh, *zt, *ws, e)):
-        raise ValueError(f"{what}: every tensor must be on the same device")
     prec = ENSEMBLE_PRECISIONS[precision]
     mask, mstride = _exclude_args(split, zh[0], Nh, Nt, L)
     tables = () if split is None else (2,)
@@ -1062,21 +1021,19 @@ def bilinear_ensemble_bincount(z_heads, z_tails, w_syms, edges: torch.Tensor, *,
         return counts
     if Nh == 0 or Nt == 0:                       # no pair at all
         return counts.zero_()
-    arr = lambda ts: (ctypes.c_void_p * K)(*[t.data_ptr() for t in ts])    # noqa: E731
-    a_h, a_t = arr(zh), arr(zt)
-    for lo in range(0, L, 65535):                # the grid's y extent caps one call at 65535 outcomes
-        hi = min(L, lo + 65535)
-        wsp, nbytes = _scratch("mdg_bilinear_ensemble_bincount_workspace_bytes", dev, Nh, Nt, hi - lo, D, K, prec)
-        a_w = (ctypes.c_void_p * K)(*[w.data_ptr() + lo * D * D * 4 for w in ws])
+
+    def one_call(lo, n, models, scratch):
+        sizes = (Nh, Nt, n, D, B, prec, TOPK_ELIGIBLE[eligible])
         if split is None:
-            call("mdg_bilinear_ensemble_bincount", a_h, a_t, a_w, K, e.data_ptr() + lo * B * 4, counts.data_ptr() + lo * (B + 1) * 8, Nh, Nt,
-                 hi - lo, D, B, prec, TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]))
-            continue
-        part = counts if hi - lo == L else torch.empty((2, hi - lo, B + 1), dtype=torch.int64, device=dev)   # [2][this call's outcomes]
-        call("mdg_bilinear_ensemble_bincount_split", a_h, a_t, a_w, K, e.data_ptr() + lo * B * 4, _ptr(part), Nh, Nt, hi - lo, D, B, prec,
-             TOPK_ELIGIBLE[eligible], _ptr(wsp), nbytes, _stream(zh[0]), mask.data_ptr() + lo * mstride * 4, mstride)
+            call("mdg_bilinear_ensemble_bincount", *models, e.data_ptr() + lo * B * 4, counts.data_ptr() + lo * (B + 1) * 8, *sizes, *scratch)
+            return
+        part = counts if n == L else torch.empty((2, n, B + 1), dtype=torch.int64, device=dev)   # [2][this call's outcomes]
+        call("mdg_bilinear_ensemble_bincount_split", *models, e.data_ptr() + lo * B * 4, _ptr(part), *sizes, *scratch,
+             mask.data_ptr() + lo * mstride * 4, mstride)
         if part is not counts:
-            counts[:, lo:hi] = part
+            counts[:, lo:lo + n] = part
+
+    _ensemble_calls("bincount", zh, zt, ws, prec, one_call)
     return counts
 
 
