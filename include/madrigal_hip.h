@@ -148,6 +148,25 @@ int mdg_bilinear_ensemble_sigmoid(const float* const* z_head_host, const float* 
                                   int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same tensor in 16 bits (ABI 30): out[(l * n_head + i) * ldo + j] = P[l,i,j] of mdg_bilinear_ensemble_sigmoid -- the mean
+ * probability get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) deliver --
+ * rounded ONCE, to nearest even, to IEEE half (MDG_SCORE_F16) or bfloat16 (MDG_SCORE_BF16): bit for bit the tensor
+ * mdg_bilinear_ensemble_sigmoid writes for the same operands, cast afterwards, with 2 B per probability leaving the chip instead
+ * of 4 + a cast pass (half subnormals and values that round to 0 or to exactly 1 included).  The same sweeps: with z_head_k ==
+ * z_tail_k for every k the symmetric one runs, each element still has one writer and out[l] is exactly symmetric.
+ *   Operands, n_models (1..8), precision (MDG_PREC_F32 or MDG_PREC_BF16X3) and argument checks as mdg_bilinear_ensemble_sigmoid.
+ *   score_type: MDG_SCORE_F16 or MDG_SCORE_BF16; anything else is refused before a launch.
+ *   out: 2-byte aligned, ldo >= n_tail in ELEMENTS, any pitch.  Rows that all start on 4 bytes (out % 4 == 0 and an even ldo;
+ *   ldo = n_tail rounded up to 64 puts them on 128-byte lines) are written as packed column pairs; any other layout is written
+ *   correctly with 2-byte stores, slower.  Nothing outside columns [0, n_tail) of a row is touched, padding included.
+ *   n_labels <= 65535 per call, D == 128, 256 * ldo * 2 < 2^31.
+ *   Workspace: the size mdg_bilinear_ensemble_sigmoid_workspace_bytes gives (0 for F32).  No atomics: bit-identical between
+ *   launches. */
+int mdg_bilinear_ensemble_sigmoid16(const float* const* z_head_host, const float* const* z_tail_host,
+                                    const float* const* w_sym_host, int n_models, void* out, int64_t ldo, int64_t n_head,
+                                    int64_t n_tail, int64_t n_labels, int64_t D, int precision, int score_type,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-row top-k of the checkpoint ensemble (ABI 25): for every outcome l and head row i the k largest
  *   P[l,i,j] = mean_m sigmoid(z_head_m[i]^T W_sym_m[l] z_tail_m[j])
  * over the ELIGIBLE tail columns j, and those columns, without materialising [L,N,N].  The probability is the one

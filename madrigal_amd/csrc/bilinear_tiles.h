@@ -279,6 +279,14 @@ __device__ __forceinline__ void compute_tile_spread(const AFrag<MODE>& A, const 
 // accumulator register v of lane (r,h) is element [row (v&3)+8(v>>2)+4h][col r] of the 32x32 tile
 __device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
 
+// ---- 16-bit destinations (store16.hip, ensemble_store16.hip): one rounding to nearest even (a plain cast; fp16 overflow becomes
+// +-inf) -> the bits of an IEEE half (MDG_SCORE_F16) or a bfloat16 (MDG_SCORE_BF16)
+template <int TY>
+__device__ __forceinline__ unsigned round16(float x) {
+  if constexpr (TY == MDG_SCORE_F16) return __builtin_bit_cast(unsigned short, static_cast<_Float16>(x));
+  else return __builtin_bit_cast(unsigned short, static_cast<__bf16>(x));
+}
+
 // ---- pre-pass: the 16-bit operand images of z_tail and W_sym (the images mdg_bilinear_allpairs makes) ----------------------
 template <int MODE>
 __global__ void operand_images_kernel(const float* __restrict__ x, __bf16* __restrict__ hi, __bf16* __restrict__ lo, int64_t n4) {

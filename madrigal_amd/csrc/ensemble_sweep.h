@@ -1,5 +1,5 @@
-// What the sweeps over a checkpoint ensemble of the all-pairs head -- ensemble.hip, ensemble_topk.hip, ensemble_select.hip,
-// ensemble_bincount.hip, ensemble_profile.hip -- share.
+// What the sweeps over a checkpoint ensemble of the all-pairs head -- ensemble.hip, ensemble_store16.hip, ensemble_topk.hip,
+// ensemble_select.hip, ensemble_bincount.hip, ensemble_profile.hip -- share.
 //
 // In each of them a workgroup owns head rows of one outcome at a time, 32 per wave; per model m it rebuilds T_m = z_head_m[rows] .
 // W_sym_m[l] (build_t) and sweeps 64-column tiles of z_tail_m through two stage buffers filled by LDS-DMA, the sigmoids of the
@@ -54,6 +54,35 @@ __device__ __forceinline__ bool ens_eligible(int mode, int lr, int lc, int dcr, 
   const int d = dcr + lc - lr;                                                          // column - row
   const bool pair = mode == MDG_TOPK_NOT_SELF ? d != 0 : d < 0;                         // (bitwise: selects, no branches)
   return (lr < nr) & (lc < nc) & ((mode == MDG_TOPK_ALL) | pair);
+}
+
+// stage_dma (bilinear_tiles.h) of a workgroup of NW = 4 or 8 waves with the tail rows of the tile permuted on the SOURCE address:
+// LDS row 32 t + r <- tail row row0 + 2 r + t (store16.hip's store16_stage_dma).  The LDS image, its swizzle and compute_tile_spread
+// are those of stage_dma; lane (r, h) of the product then holds columns 2 r (accumulator tile 0) and 2 r + 1 (tile 1) of the same 16
+// rows -- the column pair of one dword of a 16-bit tensor (ensemble_store16.hip).
+template <int MODE, int NW>
+__device__ __forceinline__ void stage_dma_pairs(const TileSrc& s, int64_t row0, char* lds, int wave, int lane) {
+  static_assert(NW == 4 || NW == 8, "the K >= 2 and the K = 1 workgroup");
+  if constexpr (MODE == MDG_PREC_F32) {
+#pragma unroll
+    for (int i = 0; i < 32 / NW; ++i) {
+      const int p = wave + NW * i;
+      const int row = 2 * p + (lane >> 5), c = (lane & 31) ^ (row & 15);
+      int64_t gr = row0 + 2 * (row & 31) + (row >> 5);
+      gr = gr < s.nrows ? gr : s.nrows - 1;
+      glds16(s.f32 + gr * D + c * 4, lds_addr(lds + p * 1024));
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16 / NW; ++i) {
+      const int p = wave + NW * i;
+      const int row = 4 * p + (lane >> 4), c = (lane & 15) ^ (row & 15);
+      int64_t gr = row0 + 2 * (row & 31) + (row >> 5);
+      gr = gr < s.nrows ? gr : s.nrows - 1;
+      glds16(s.hi + gr * D + c * 8, lds_addr(lds + p * 1024));
+      if constexpr (MODE == MDG_PREC_BF16X3) glds16(s.lo + gr * D + c * 8, lds_addr(lds + LO_OFF + p * 1024));
+    }
+  }
 }
 
 // T = z_head[32 rows of this wave] . W_sym[l] -> At, the same fp32 values as the head's prologue: per 32-column tile the MFMA

@@ -66,13 +66,6 @@ __device__ __forceinline__ void store16_stage_dma(const TileSrc& s, int64_t row0
   }
 }
 
-// one rounding to nearest even (a plain cast; fp16 overflow becomes +-inf)
-template <int TY>
-__device__ __forceinline__ unsigned round16(float x) {
-  if constexpr (TY == MDG_SCORE_F16) return __builtin_bit_cast(unsigned short, static_cast<_Float16>(x));
-  else return __builtin_bit_cast(unsigned short, static_cast<__bf16>(x));
-}
-
 template <int MODE, int EPI, int TY>
 __global__ __launch_bounds__(512, 2) void bilinear_store16_kernel(const Store16Args p) {
   constexpr int NW = 8, BM = 32 * NW;

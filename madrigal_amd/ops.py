@@ -802,13 +802,26 @@ def _ensemble_calls(product, zh, zt, ws, prec, one_call) -> None:
         one_call(lo, n, (a_h, a_t, a_w, K), (_ptr(wsp), nbytes, _stream(zh[0])))
 
 
-def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", out: Optional[torch.Tensor] = None,
+                              out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """Checkpoint ensemble of the all-pairs head: P[l,i,j] = mean_k sigmoid(z_heads[k][i]^T w_syms[k][l] z_tails[k][j]) -> [L,Nh,Nt]
     fp32 (madrigal/evaluate/predict.py:466-499, 582-614), K = len(z_heads) in 1..8, one launch.  Per model the logit is
     ``bilinear_allpairs``'s own arithmetic in ``precision`` ("f32" or "bf16x3"); the sigmoids are summed in model order and divided
     once by K.  When ``z_heads[k] is z_tails[k]`` for every k (one drug set against itself) the symmetric sweep runs and every
-    P[l] is exactly symmetric.  ``out``: None (an ``empty_scores`` tensor) or a contiguous / row-pitched fp32 GPU tensor."""
+    P[l] is exactly symmetric.  ``out``: None (an ``empty_scores`` tensor) or a contiguous / row-pitched GPU tensor.
+
+    ``out_dtype`` = ``torch.float16`` / ``torch.bfloat16`` (or an ``out`` of that dtype): the tensor in 16 bits, rounded once to
+    nearest even inside the sweep (mdg_bilinear_ensemble_sigmoid16) -- bit for bit the fp32 result of the same call
+    ``.to(out_dtype)``, symmetric sweep and exact symmetry included, with half the bytes written and no fp32 tensor next to it.
+    Without ``out`` it comes in the ``empty_scores(dtype=...)`` layout; a view at an odd element offset or with an odd pitch is
+    written correctly by 2-byte stores, slower."""
     what = "bilinear_ensemble_sigmoid"
+    if out_dtype is None:
+        out_dtype = out.dtype if (isinstance(out, torch.Tensor) and out.dtype in SCORE_TYPES) else torch.float32
+    if out_dtype != torch.float32 and out_dtype not in SCORE_TYPES:
+        raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
+    if isinstance(out, torch.Tensor) and out.dtype != out_dtype:
+        raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
     zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision)
     sym = all(a is b for a, b in zip(zh, zt))
     zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
@@ -818,14 +831,19 @@ def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", o
     dev = zh[0].device
     shape = (L, Nh, Nt)
     if out is None:
-        out = empty_scores(L, Nh, Nt, dev)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+        out = empty_scores(L, Nh, Nt, dev, dtype=out_dtype)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == out_dtype and tuple(out.shape) == shape
               and (out.numel() == 0 or (out.stride(2) == 1 and out.stride(1) >= Nt and out.stride(0) == Nh * out.stride(1)))):
-        raise ValueError(f"out: expected a float32 GPU tensor {shape}, contiguous or row-pitched (empty_scores)")
+        raise ValueError(f"out: expected a {str(out_dtype).replace('torch.', '')} GPU tensor {shape}, contiguous or row-pitched (empty_scores)")
     ldo = out.stride(1) if out.numel() else Nt
     prec = ENSEMBLE_PRECISIONS[precision]
-    _ensemble_calls("sigmoid", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
-        "mdg_bilinear_ensemble_sigmoid", *models, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt, n, D, prec, *scratch))
+    if out_dtype == torch.float32:
+        _ensemble_calls("sigmoid", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+            "mdg_bilinear_ensemble_sigmoid", *models, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt, n, D, prec, *scratch))
+    else:                                          # the same workspace query; the pointer steps in bytes of the 16-bit type
+        _ensemble_calls("sigmoid", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+            "mdg_bilinear_ensemble_sigmoid16", *models, out.data_ptr() + lo * out.stride(0) * 2, ldo, Nh, Nt, n, D, prec,
+            SCORE_TYPES[out_dtype], *scratch))
     return out
 
 
@@ -1096,8 +1114,8 @@ def empty_scores(L: int, Nh: int, Nt: int, device, dtype: torch.dtype = torch.fl
     generate_embeddings.ipynb -- are not multiples of anything).  For Nt % 32 == 0 this is a plain contiguous tensor; otherwise a
     [:, :, :Nt] view of the padded storage: same values and indexing, ``.contiguous()`` compacts it.
 
-    ``dtype`` = ``torch.float16`` / ``torch.bfloat16`` (the 16-bit destinations of ``bilinear_allpairs``): the pitch unit is 64
-    elements, still one 128-byte line."""
+    ``dtype`` = ``torch.float16`` / ``torch.bfloat16`` (the 16-bit destinations of ``bilinear_allpairs`` and
+    ``bilinear_ensemble_sigmoid``): the pitch unit is 64 elements, still one 128-byte line."""
     if dtype != torch.float32 and dtype not in SCORE_TYPES:
         raise ValueError(f"dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {dtype}")
     unit = 32 if dtype == torch.float32 else 64                   # elements: one 128-byte line (scripts/head_ragged_bench.py compared 4 .. 64 floats)

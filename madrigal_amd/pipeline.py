@@ -1052,9 +1052,10 @@ def _index(inds, n: int, name: str, device) -> Optional[torch.Tensor]:
 
 
 @torch.no_grad()
-def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_inds=None, out=None, host_chunk: int = 16):
+def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_inds=None, out=None, host_chunk: int = 16,
+                       out_dtype=None):
     """Mean interaction probability over checkpoints for every drug pair: P[o, a, b] = mean_k sigmoid(S_k[outcome_inds[o],
-    drug_inds[a], drug_2_inds[b]]) -> [O, A, B] fp32, in one sweep of ``ops.bilinear_ensemble_sigmoid``.  Replaces
+    drug_inds[a], drug_2_inds[b]]) -> [O, A, B] fp32 (or 16-bit: ``out_dtype``), in one sweep of ``ops.bilinear_ensemble_sigmoid``.  Replaces
     get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614), which write K raw-score
     memmaps and stack, sigmoid and average them on the host.
 
@@ -1066,8 +1067,26 @@ def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_ind
 
     ``out``: None / a CUDA tensor (one launch into HBM) or a numpy array / ``np.memmap`` (outcome chunks of ``host_chunk`` streamed
     through two pinned buffers, as ``score_all_pairs`` does).  Multi-GPU: give each rank its slice of ``outcome_inds``; the slices
-    are independent and no collective is involved."""
+    are independent and no collective is involved.
+
+    ``out_dtype`` = ``torch.float16`` / ``torch.bfloat16`` (or an ``out`` of a 16-bit type): the tensor in 16 bits, rounded once inside
+    the sweep (``ops.bilinear_ensemble_sigmoid``), bit for bit the fp32 tensor cast afterwards -- half the HBM and, with a host
+    destination (a ``np.float16`` array or memmap; numpy has no bfloat16), half the PCIe and disk bytes: the staging buffers and
+    copies are 16-bit too."""
     from .models import get_precision
+    if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
+    if isinstance(out, torch.Tensor):
+        if out_dtype is not None and out.dtype != out_dtype:
+            raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
+    elif out is not None:
+        if out_dtype == torch.bfloat16:
+            raise ValueError("out_dtype torch.bfloat16 needs an HBM destination: numpy has no bfloat16 (use torch.float16 for a host array / memmap)")
+        host_dtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}.get(getattr(out, "dtype", None))
+        if host_dtype is None:
+            raise ValueError("out: expected a CUDA tensor, or a float32 / float16 numpy array or memmap")
+        if out_dtype is not None and out_dtype != host_dtype:
+            raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
     K = len(models)
     if not 1 <= K <= 8 or len(zs) != K:
         raise ValueError(f"ensemble_all_pairs: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
@@ -1090,12 +1109,12 @@ def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_ind
     prec = get_precision()
     L, A, B = wsel[0].shape[0], heads[0].shape[0], tails[0].shape[0]
     if out is None or isinstance(out, torch.Tensor):
-        return ops.bilinear_ensemble_sigmoid(heads, tails, wsel, precision=prec, out=out)
-    if tuple(out.shape) != (L, A, B) or out.dtype != np.float32:
-        raise ValueError(f"out: expected float32 array of shape {(L, A, B)}")
+        return ops.bilinear_ensemble_sigmoid(heads, tails, wsel, precision=prec, out=out, out_dtype=out_dtype)
+    if tuple(out.shape) != (L, A, B):
+        raise ValueError(f"out: expected a float32 or float16 array of shape {(L, A, B)}")
     copy_stream = torch.cuda.Stream(device=dev)
-    dev_buf = [ops.empty_scores(host_chunk, A, B, dev) for _ in range(2)]
-    pin_buf = [torch.empty((host_chunk, A, B), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+    dev_buf = [ops.empty_scores(host_chunk, A, B, dev, dtype=host_dtype) for _ in range(2)]     # row-pitched on the device, compacted by the copy
+    pin_buf = [torch.empty((host_chunk, A, B), dtype=host_dtype, pin_memory=True) for _ in range(2)]
     done = [None, None]
     pending = [None, None]
     for k, s in enumerate(range(0, L, host_chunk)):
