@@ -296,6 +296,49 @@ int mdg_bilinear_ensemble_profile(const float* const* z_head, const float* const
                                   int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int precision, int eligible,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Spread of the checkpoint ensemble: how much the n_models checkpoints agree on a pair.  For every outcome l, head row i, tail column j
+ *   p_m   = sigmoid(z_head_m[i]^T W_sym_m[l] z_tail_m[j])                    m = 0..K-1, K = n_models in 1..8
+ *   mean  = (p_0 + ... + p_{K-1}) / K      bit for bit mdg_bilinear_ensemble_sigmoid's general sweep (z_head != z_tail) for the same call
+ *   std   = sqrt((1/K) sum_m (p_m - mean)^2)                                 population standard deviation (ddof = 0, numpy's default)
+ *   bound = fmaf(kappa, std, mean)                                           one rounding; kappa a finite fp32 scalar per call
+ * get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) keep every checkpoint's
+ * score tensor in memory before they average.  The reference has NO std call of its own: its users take np.stack(...).std(0) of
+ * those stored tensors next to the .mean(0) it returns.  Here the per-checkpoint tensors never exist; the second moment is kept in
+ * registers beside the running sum of the sweep.  kappa < 0 ranks by a lower confidence bound (hits the seeds agree on), kappa > 0
+ * by an upper bound (contested pairs), kappa == 0 gives the mean bit for bit.  The bound is not monotone in the mean, so no
+ * composition of the mean's lists gives its ranking.
+ *   std is computed in fp32 by Welford's one-pass recurrence (mu += (p - mu) / n; M2 += (p - mu_old) * (p - mu_new)), which does
+ *   not cancel; the running sum behind `mean` is untouched by it.  std >= 0 always, never NaN for finite logits, exactly 0.0f for
+ *   K == 1 and whenever the K values p_m are equal.  Both entry points share the recurrence's text: their std and bound agree bit
+ *   for bit.
+ *   Operands as mdg_bilinear_ensemble_topk (HOST arrays of n_models device pointers, 16-byte aligned, D == 128); precision
+ *   MDG_PREC_F32 or MDG_PREC_BF16X3; n_labels <= 65535 per call.  A non-finite kappa is refused before a launch.
+ *   mdg_bilinear_ensemble_spread: the dense product.  mean, std, bound: fp32 [n_labels, n_head, ldo], ldo >= n_tail, ONE row pitch
+ *     for all three (the layout of mdg_bilinear_allpairs_ld), 128 * ldo * 4 < 2^31; a NULL pointer skips that tensor, at least one
+ *     must be given (kappa is ignored without `bound`, but must be finite).  Always the general sweep: no mirrored symmetric
+ *     variant, no 16-bit outputs.  Nothing outside columns [0, n_tail) of a row is touched.
+ *   mdg_bilinear_ensemble_spread_topk: for every outcome and head row the k <= 32 ELIGIBLE tail columns with the largest bound,
+ *     ordered by (bound descending, column ascending), which is also the tie rule for what is kept.  bound [n_labels,n_head,k]
+ *     fp32, idx [n_labels,n_head,k] int32, mean and std [n_labels,n_head,k] fp32: the kept column's own mean and std, equal bit for
+ *     bit to the dense product's at idx.  Rows with fewer than k eligible columns are padded with -inf / -1 / NaN / NaN.
+ *     eligible, k, n_tail, mask / plane_stride as mdg_bilinear_ensemble_topk (mask == NULL: the unmasked kernel, no mask memory is
+ *     read).  Nothing of [L,N,N] is materialised.
+ *   mdg_bilinear_ensemble_spread_chunk_tiles: the 64-column tail tiles a workgroup of either kernel sweeps between two rebuilds of
+ *     the models' z_head . W_sym products (narrower than mdg_bilinear_ensemble_topk_chunk_tiles: three registers of state per
+ *     element, not one); for tests that want sizes at that boundary.
+ *   Workspace: the size mdg_bilinear_ensemble_sigmoid_workspace_bytes gives (0 for F32).
+ * Deterministic: no atomics, the state and the lists live in registers; bit-identical from launch to launch. */
+int mdg_bilinear_ensemble_spread_chunk_tiles(void);
+size_t mdg_bilinear_ensemble_spread_workspace_bytes(int64_t n_head, int64_t n_tail, int64_t n_labels, int64_t D, int n_models,
+                                                    int precision);
+int mdg_bilinear_ensemble_spread(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                                 float* mean, float* std_, float* bound, float kappa, int64_t ldo, int64_t n_head, int64_t n_tail,
+                                 int64_t n_labels, int64_t D, int precision, void* workspace, size_t workspace_bytes, void* stream);
+int mdg_bilinear_ensemble_spread_topk(const float* const* z_head, const float* const* z_tail, const float* const* w_sym, int n_models,
+                                      float kappa, float* bound, int32_t* idx, float* mean, float* std_, int64_t n_head,
+                                      int64_t n_tail, int64_t n_labels, int64_t D, int precision, int k, int eligible, void* workspace,
+                                      size_t workspace_bytes, void* stream, const uint32_t* mask, int64_t plane_stride);
+
 /* Per-row top-k of the all-pairs sweep: for every outcome l and head row i the k largest scores S[l,i,j] (the arithmetic of
  * mdg_bilinear_allpairs' general sweep in `precision`, bit for bit in F32 / BF16X3; the 16-bit modes run the row-statistics
  * sweep, whose fp32 sums are grouped differently: <= 2e-6 of the scale) over the ELIGIBLE tail columns j, and those columns.

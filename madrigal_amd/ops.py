@@ -8,6 +8,8 @@ assertion errors in the same situations) and ``MadrigalHipError`` if the library
 from __future__ import annotations
 
 import ctypes
+import math
+import numbers
 import os
 from typing import Optional
 
@@ -892,6 +894,128 @@ def bilinear_ensemble_topk(z_heads, z_tails, w_syms, k: int, *, eligible: str = 
         "mdg_bilinear_ensemble_topk", *models, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, n, D, prec, int(k),
         TOPK_ELIGIBLE[eligible], *scratch, None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
     return vals, idx
+
+
+def bilinear_ensemble_spread_chunk_tiles() -> int:
+    """The 64-column tail tiles ``bilinear_ensemble_spread`` and ``bilinear_ensemble_spread_topk`` sweep between two rebuilds of the
+    models' z_head . W_sym products (fewer than ``bilinear_ensemble_topk_chunk_tiles``: three registers of state per element)."""
+    return lib().mdg_bilinear_ensemble_spread_chunk_tiles()
+
+
+def _kappa(kappa, what: str) -> float:
+    """``kappa`` of the confidence bound as a Python float: a finite Python or numpy real that stays finite in fp32."""
+    if isinstance(kappa, bool) or not isinstance(kappa, numbers.Real) or not math.isfinite(kappa) or abs(float(kappa)) > 3.4028234663852886e38:
+        raise ValueError(f"{what}: kappa must be a finite real number (fp32 range), got {kappa!r}")
+    return float(kappa)
+
+
+def bilinear_ensemble_spread(z_heads, z_tails, w_syms, *, kappa=None, precision="bf16x3", out=None):
+    """Mean and spread of the checkpoint ensemble -> ``(mean, std)``, or ``(mean, std, bound)`` when ``kappa`` is given, each
+    [L,Nh,Nt] fp32: over the K = len(z_heads) in 1..8 probabilities p_m = sigmoid(z_heads[m][i]^T w_syms[m][l] z_tails[m][j]),
+    ``mean`` = their mean, ``std`` = their population standard deviation (ddof = 0, ``np.stack(...).std(0)``) and ``bound`` =
+    fmaf(kappa, std, mean), one rounding.  madrigal/evaluate/predict.py:466-499, 582-614 keep every checkpoint's tensor before they
+    average; the reference has no std call of its own, one takes it from those stored tensors.  Here they never exist: one sweep,
+    the second moment kept in registers beside the running sum (``mdg_bilinear_ensemble_spread``).
+
+    ``mean`` is bit for bit ``bilinear_ensemble_sigmoid``'s general-sweep tensor in ``precision`` ("f32" or "bf16x3"); this product
+    always runs the general sweep.  ``std`` comes from Welford's recurrence in fp32, which does not cancel: >= 0, never NaN for
+    finite logits, exactly 0 for K = 1 and for K equal probabilities.  ``out``: None (``empty_scores`` tensors) or a tuple
+    (mean, std) / (mean, std, bound) to reuse -- contiguous or row-pitched fp32 GPU tensors with ONE common pitch; a ``None`` entry
+    skips that tensor (it is returned as None), at least one must be given."""
+    what = "bilinear_ensemble_spread"
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision)
+    n_out = 2 if kappa is None else 3
+    kap = 0.0 if kappa is None else _kappa(kappa, what)
+    L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
+    shape = (L, Nh, Nt)
+    names = ("mean", "std", "bound")[:n_out]
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == n_out):
+            raise ValueError(f"out: expected a ({', '.join(names)}) tuple")
+        if all(t is None for t in out):
+            raise ValueError("out: at least one tensor must be given")
+        for t, name in zip(out, names):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape):
+                raise ValueError(f"out ({name}): expected a float32 tensor of shape {shape}")
+    zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
+    dev = zh[0].device
+    if out is None:
+        res = [empty_scores(L, Nh, Nt, dev) for _ in names]
+    else:
+        res = list(out)
+        for t, name in zip(res, names):
+            if t is not None and not (t.is_cuda and t.device == dev and
+                                      (t.numel() == 0 or (t.stride(2) == 1 and t.stride(1) >= Nt and t.stride(0) == Nh * t.stride(1)))):
+                raise ValueError(f"out ({name}): expected a GPU tensor on {dev}, contiguous or row-pitched (empty_scores)")
+    given = [t for t in res if t is not None]
+    if given[0].numel() and any(t.stride(1) != given[0].stride(1) for t in given):
+        raise ValueError("out: the tensors must share one row pitch")
+    if given[0].numel() == 0:
+        return tuple(res)
+    ldo, s0 = given[0].stride(1), given[0].stride(0)
+    prec = ENSEMBLE_PRECISIONS[precision]
+    at = lambda t, lo: None if t is None else t.data_ptr() + lo * s0 * 4    # noqa: E731
+    _ensemble_calls("spread", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+        "mdg_bilinear_ensemble_spread", *models, at(res[0], lo), at(res[1], lo), at(res[2], lo) if n_out == 3 else None, kap, ldo, Nh, Nt, n, D,
+        prec, *scratch))
+    return tuple(res)
+
+
+def bilinear_ensemble_spread_topk(z_heads, z_tails, w_syms, k: int, kappa, *, eligible: str = "all", precision="bf16x3", out=None,
+                                  exclude: Optional[torch.Tensor] = None):
+    """Per-row top-k of the checkpoint ensemble under a confidence bound -> ``(bound [L,Nh,k] fp32, idx [L,Nh,k] int32, mean
+    [L,Nh,k] fp32, std [L,Nh,k] fp32)``: for every outcome and head row the ``k`` eligible tail columns with the largest
+    bound = fmaf(kappa, std, mean) of ``bilinear_ensemble_spread``, ordered by (bound descending, column ascending), with each kept
+    column's own mean and std; rows with fewer than ``k`` eligible columns are padded with ``-inf`` / ``-1`` / NaN / NaN.
+    ``kappa < 0`` ranks by a lower confidence bound (hits the seeds agree on), ``kappa > 0`` by an upper bound (contested pairs),
+    ``kappa = 0`` gives ``bilinear_ensemble_topk``'s lists bit for bit.  The bound is not monotone in the mean, so no composition
+    of the mean's lists gives this ranking; nothing of [L,Nh,Nt] is materialised (``mdg_bilinear_ensemble_spread_topk``; the
+    per-checkpoint tensors of madrigal/evaluate/predict.py:466-499, 582-614, from which the reference's users take a std, never
+    exist here).
+
+    Bound, mean and std are bit for bit the dense product's at ``idx``.  ``eligible``, ``k``, ``out`` (a 4-tuple to reuse) and
+    ``exclude`` as ``bilinear_ensemble_topk``."""
+    what = "bilinear_ensemble_spread_topk"
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible)
+    max_k = bilinear_topk_max_k()
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
+        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
+    kap = _kappa(kappa, what)
+    L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
+    shape = (L, Nh, k)
+    kinds = ((torch.float32, "out[0] (bound)"), (torch.int32, "out[1] (idx)"), (torch.float32, "out[2] (mean)"), (torch.float32, "out[3] (std)"))
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 4):
+            raise ValueError("out: expected a (bound, idx, mean, std) tuple")
+        for t, (dt, name) in zip(out, kinds):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {shape}")
+    zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
+    dev = zh[0].device
+    mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
+    if out is None:
+        res = tuple(torch.empty(shape, dtype=dt, device=dev) for dt, _ in kinds)
+    else:
+        res = tuple(out)
+        for t, (_, name) in zip(res, kinds):
+            if not (t.is_cuda and t.device == dev):
+                raise ValueError(f"{name}: must live on the device of the embeddings ({dev})")
+    bound, idx, mean, std = res
+    if bound.numel() == 0:
+        return res
+    if Nt == 0:                                  # no column at all: every row is padding
+        bound.fill_(float("-inf"))
+        idx.fill_(-1)
+        mean.fill_(float("nan"))
+        std.fill_(float("nan"))
+        return res
+    prec = ENSEMBLE_PRECISIONS[precision]
+    step = Nh * k * 4
+    _ensemble_calls("spread", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+        "mdg_bilinear_ensemble_spread_topk", *models, kap, bound.data_ptr() + lo * step, idx.data_ptr() + lo * step,
+        mean.data_ptr() + lo * step, std.data_ptr() + lo * step, Nh, Nt, n, D, prec, int(k), TOPK_ELIGIBLE[eligible], *scratch,
+        None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
+    return res
 
 
 def _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=True):

@@ -1211,6 +1211,42 @@ def ensemble_top_partners(models, zs, k: int, label_range: Optional[Tuple[int, i
 
 
 @torch.no_grad()
+def ensemble_spread_all_pairs(models, zs, label_range: Optional[Tuple[int, int]] = None, kappa=None, out=None):
+    """Mean and spread of a checkpoint ensemble for one drug set against itself -> ``(mean, std)``, or ``(mean, std, bound)`` when
+    ``kappa`` is given, each [L', N, N] fp32 over the outcomes of ``label_range``: mean and population standard deviation of the K
+    probabilities sigmoid(S_m[l, i, j]) and bound = fmaf(kappa, std, mean) (``ops.bilinear_ensemble_spread``).
+    get_twosides_scores_wrapper / get_drugbank_scores_wrapper (madrigal/evaluate/predict.py:466-499, 582-614) keep every
+    checkpoint's tensor before they average, so there the spread is ``.std(0)`` of what is stored; here those tensors never exist.
+
+    ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``out`` as ``ops.bilinear_ensemble_spread``.  ``mean`` is bit
+    for bit the general sweep's of ``ops.bilinear_ensemble_sigmoid``: (z_i W) z_j, not mirrored, so it is symmetric only up to
+    rounding.  Precision follows ``models.precision(...)``."""
+    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_spread_all_pairs")
+    return ops.bilinear_ensemble_spread(zs, zs, ws, kappa=kappa, precision=prec, out=out)
+
+
+@torch.no_grad()
+def ensemble_confident_partners(models, zs, k: int, kappa=-1.0, label_range: Optional[Tuple[int, int]] = None, drug_rows=None,
+                                eligible: str = "not_self", exclude: Optional[torch.Tensor] = None):
+    """``ensemble_top_partners`` under a confidence bound -> ``(bound, partner, mean, std)``, each [L', rows, k] (fp32, int32, fp32,
+    fp32): row i of outcome l holds the k eligible partners j with the largest bound = fmaf(kappa, std, mean) -- mean and std over
+    the K checkpoints' probabilities sigmoid(S_m[l, i, j]) -- ordered by (bound descending, j ascending), with each partner's own
+    mean and std, padded with -inf / -1 / NaN / NaN (``ops.bilinear_ensemble_spread_topk``).  The default ``kappa = -1`` ranks by
+    mean - std: partners the seeds agree on, which a list ranked by the mean cannot tell from two seeds at 1.0 and three at 0.88;
+    ``kappa > 0`` lists contested pairs, ``kappa = 0`` is ``ensemble_top_partners`` bit for bit.  Nothing of [L', N, N] and none of
+    the per-checkpoint tensors of madrigal/evaluate/predict.py:466-499, 582-614 is materialised.
+
+    ``models`` / ``zs`` / ``label_range`` / ``drug_rows`` / ``exclude`` as ``ensemble_top_partners``; ``eligible``: "not_self"
+    (j != i), "lower" (j < i) or "all"."""
+    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_confident_partners")
+    N, dev = zs[0].shape[0], zs[0].device
+    rows = _index(drug_rows, N, "drug_rows", dev)
+    excl = _ensemble_exclusion(exclude, L_all)
+    res = ops.bilinear_ensemble_spread_topk(zs, zs, ws, k, kappa, eligible=eligible, precision=prec, exclude=_planes(excl, lo, hi))
+    return res if rows is None else tuple(t[:, rows] for t in res)
+
+
+@torch.no_grad()
 def ensemble_top_pairs(models, zs, K: int, label_range: Optional[Tuple[int, int]] = None, k_row: Optional[int] = None,
                        max_temp_bytes: int = 1 << 30, info: Optional[dict] = None, exclude: Optional[torch.Tensor] = None):
     """``top_pairs`` over a checkpoint ensemble -> ``(vals [L', K] fp32, head [L', K], tail [L', K] int64)``: the ``K`` unordered
