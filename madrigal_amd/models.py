@@ -1804,6 +1804,14 @@ class BilinearDDIScorer(nn.Bilinear):
         ops.forward_only(input1, input2)
         return ops.bilinear_allpairs(input1, input2, weight, precision=_state["precision"], epilogue=epilogue, out_dtype=out_dtype, out=out)
 
+    def _sliced(self, label_range, w=None):
+        """The outcomes ``label_range`` of W_sym (``w``: of the parameter itself, which the differentiable branch of ``forward`` slices)."""
+        w = self.symmetric_weight() if w is None else w
+        if label_range is not None:
+            assert len(label_range) == 2
+            w = w[label_range[0]:label_range[1]]
+        return w
+
     def _exclude_planes(self, exclude, label_range):
         """An exclusion mask with one plane per outcome of the head, sliced like the weight (a shared plane serves every range)."""
         if label_range is None or not isinstance(exclude, torch.Tensor) or exclude.dim() != 3 or exclude.shape[0] == 1 \
@@ -1818,11 +1826,7 @@ class BilinearDDIScorer(nn.Bilinear):
         [L', n1, n2] is materialised (``ops.bilinear_topk``).  ``exclude``: an ``ops.pair_mask`` of pairs to leave out -- one plane,
         or one per outcome of the WHOLE head (sliced by ``label_range`` like the weight).  Inference only."""
         ops.forward_only(input1, input2)
-        w = self.symmetric_weight()
-        if label_range is not None:
-            assert len(label_range) == 2
-            w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_topk(input1, input2, w, k, eligible=eligible, precision=_state["precision"],
+        return ops.bilinear_topk(input1, input2, self._sliced(label_range), k, eligible=eligible, precision=_state["precision"],
                                  exclude=self._exclude_planes(exclude, label_range))
 
     def bincount(self, input1, input2, edges, label_range: tuple = None, eligible: str = "all", split=None):
@@ -1832,13 +1836,7 @@ class BilinearDDIScorer(nn.Bilinear):
         plane, or one per outcome of the WHOLE head (sliced by ``label_range`` like the weight) -> int64 [2, L', B+1], the pairs whose
         bit is clear and those whose bit is set counted separately in the same sweep.  Inference only."""
         ops.forward_only(input1, input2)
-        w = self.symmetric_weight()
-        if label_range is not None:
-            assert len(label_range) == 2
-            w = w[label_range[0]:label_range[1]]
-        if split is None:
-            return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"])
-        return ops.bilinear_bincount(input1, input2, w, edges, eligible=eligible, precision=_state["precision"],
+        return ops.bilinear_bincount(input1, input2, self._sliced(label_range), edges, eligible=eligible, precision=_state["precision"],
                                      split=self._exclude_planes(split, label_range))
 
     def select_count(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", exclude=None):
@@ -1846,11 +1844,7 @@ class BilinearDDIScorer(nn.Bilinear):
         ``forward(input1, input2, label_range)`` at or above ``thresholds`` [L'], in the precision ``forward`` uses; nothing of
         [L', n1, n2] is materialised (``ops.bilinear_select_count``).  ``exclude``: as in ``topk``.  Inference only."""
         ops.forward_only(input1, input2)
-        w = self.symmetric_weight()
-        if label_range is not None:
-            assert len(label_range) == 2
-            w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_select_count(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"],
+        return ops.bilinear_select_count(input1, input2, self._sliced(label_range), thresholds, eligible=eligible, precision=_state["precision"],
                                          exclude=self._exclude_planes(exclude, label_range))
 
     def select(self, input1, input2, thresholds, label_range: tuple = None, eligible: str = "all", max_bytes: int = 1 << 30, exclude=None):
@@ -1859,12 +1853,8 @@ class BilinearDDIScorer(nn.Bilinear):
         columns ascending: ``torch.nonzero`` of the dense mask, in the precision ``forward`` uses; nothing of [L', n1, n2] is
         materialised (``ops.bilinear_select``).  ``exclude``: as in ``topk``.  Inference only."""
         ops.forward_only(input1, input2)
-        w = self.symmetric_weight()
-        if label_range is not None:
-            assert len(label_range) == 2
-            w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_select(input1, input2, w, thresholds, eligible=eligible, precision=_state["precision"], max_bytes=max_bytes,
-                                   exclude=self._exclude_planes(exclude, label_range))
+        return ops.bilinear_select(input1, input2, self._sliced(label_range), thresholds, eligible=eligible, precision=_state["precision"],
+                                   max_bytes=max_bytes, exclude=self._exclude_planes(exclude, label_range))
 
     def profile(self, input1, input2, thresholds, scale=None, label_range: tuple = None, eligible: str = "all", out=None):
         """Extension (screening): ``(count int32, best int32, margin fp32)`` [n1, n2] -- per pair, over the outcomes of
@@ -1872,11 +1862,8 @@ class BilinearDDIScorer(nn.Bilinear):
         ``(score - threshold) * scale`` and the lowest outcome (an index into the range) attaining it, in the precision ``forward``
         uses; nothing of [L', n1, n2] is materialised (``ops.bilinear_profile``; L' <= 65535).  Inference only."""
         ops.forward_only(input1, input2)
-        w = self.symmetric_weight()
-        if label_range is not None:
-            assert len(label_range) == 2
-            w = w[label_range[0]:label_range[1]]
-        return ops.bilinear_profile(input1, input2, w, thresholds, scale=scale, eligible=eligible, precision=_state["precision"], out=out)
+        return ops.bilinear_profile(input1, input2, self._sliced(label_range), thresholds, scale=scale, eligible=eligible,
+                                    precision=_state["precision"], out=out)
 
     def score_triples(self, input1, input2, plan: dict) -> torch.Tensor:
         """Extension (finetune step): scores of the plan's (label, head, tail) triples only, in the plan's
@@ -1892,16 +1879,8 @@ class BilinearDDIScorer(nn.Bilinear):
             # backward cost proportional to L*Nh*Nt, as in the reference; score_triples() is the fast path)
             if epilogue != ops.EPI_STORE or out is not None or out_dtype not in (None, torch.float32):
                 raise ValueError("epilogue / out / out_dtype are inference-only arguments")
-            w = self.weight
-            if label_range is not None:
-                assert len(label_range) == 2
-                w = w[label_range[0]:label_range[1]]
-            return ag.bilinear_allpairs(input1, input2, w.contiguous(), _state["precision"])
-        w = self.symmetric_weight()
-        if label_range is not None:
-            assert len(label_range) == 2
-            w = w[label_range[0]:label_range[1]]
-        return self.bilinear(input1, input2, w, epilogue, out, out_dtype)
+            return ag.bilinear_allpairs(input1, input2, self._sliced(label_range, self.weight).contiguous(), _state["precision"])
+        return self.bilinear(input1, input2, self._sliced(label_range), epilogue, out, out_dtype)
 
 
 # ------------------------------------------------------------------------------------- position encodings

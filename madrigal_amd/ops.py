@@ -23,11 +23,11 @@ HEAD_PRECISIONS = dict(PRECISIONS, f16=PREC_F16)          # the all-pairs head a
 EPI_STORE, EPI_STORE_SIGMOID, EPI_ROWSTATS, EPI_TRIKEYS = 0, 1, 2, 3
 
 
-def _prec(p) -> int:
+def _prec(p, names=PRECISIONS) -> int:
     if isinstance(p, str):
-        if p not in PRECISIONS:
-            raise ValueError(f"unknown precision {p!r}; expected one of {sorted(PRECISIONS)}")
-        return PRECISIONS[p]
+        if p not in names:
+            raise ValueError(f"unknown precision {p!r}; expected one of {sorted(names)}")
+        return names[p]
     return int(p)
 
 
@@ -101,6 +101,200 @@ def symmetrize(w_original: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
 SCORE_TYPES = {torch.float16: 1, torch.bfloat16: 2}      # enum mdg_score_type
 
 
+# ---- what the wrappers of the all-pairs sweeps share, the single-model family and the checkpoint ensemble's alike ----
+def _f32_dims(t, name: str, nd: int) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
+        raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
+                         f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+
+
+def _eligible_arg(eligible, Nh: int, Nt: int) -> None:
+    if eligible not in TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
+    if eligible != "all" and Nh != Nt:
+        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+
+
+_HEAD_OPERANDS = ("z_head", "z_tail", "w_sym")
+
+
+def _head_models(z_head, z_tail, w_sym, precision, eligible="all", own=()) -> int:
+    """What every single-model sweep wrapper checks about its operands, shapes first, on whatever device the tensors live: float32
+    tensors of the right rank (the three operands and the product's ``own``: ``(tensor, name, ndim)`` each), one feature dim, the
+    eligible and precision names, one drug set under a restricted ``eligible`` -> the precision code.  (``_ensemble_models`` is the
+    ensemble's.)"""
+    for t, name, nd in (*zip((z_head, z_tail, w_sym), _HEAD_OPERANDS, (2, 2, 3)), *own):
+        _f32_dims(t, name, nd)
+    D = z_head.shape[1]
+    if z_tail.shape[1] != D or w_sym.shape[1] != D or w_sym.shape[2] != D:
+        raise ValueError(f"feature dims disagree: z_head {tuple(z_head.shape)}, z_tail {tuple(z_tail.shape)}, w {tuple(w_sym.shape)}")
+    _eligible_arg(eligible, z_head.shape[0], z_tail.shape[0])
+    return _prec(precision, HEAD_PRECISIONS)
+
+
+def _head_on_gpu(z_head, z_tail, w_sym, *own):
+    """The operands of ``_head_models`` and the product's ``own`` as contiguous fp32 GPU tensors on one device -> [zh, zt, w, *own]."""
+    names = (*_HEAD_OPERANDS, *(name for _, name, _ in own))
+    ts = [_f32_cuda(t, name, nd) for t, name, nd in (*zip((z_head, z_tail, w_sym), _HEAD_OPERANDS, (2, 2, 3)), *own)]
+    if any(t.device != ts[0].device for t in ts):
+        raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} must be on the same device")
+    return ts
+
+
+def _head_calls(product, zh, zt, w, one_call, *query) -> None:
+    """All outcomes through a single-model entry point of ``product`` (allpairs, topk, bincount, select), 65 535 per call: the grid's
+    y extent.  ``one_call(lo, n, operands, scratch)`` makes the call for the ``n`` outcomes from ``lo`` on; ``operands`` = the three
+    pointers, the entry point's first arguments, ``scratch`` = workspace, its size and the stream; ``query``: what the product's
+    workspace query takes after D.  (``_ensemble_calls`` is the ensemble's.)"""
+    L, D, Nh, Nt = w.shape[0], w.shape[1], zh.shape[0], zt.shape[0]
+    for lo in range(0, L, 65535):
+        n = min(L, lo + 65535) - lo
+        ws, nbytes = _scratch(f"mdg_bilinear_{product}_workspace_bytes", zh.device, Nh, Nt, n, D, *query)
+        one_call(lo, n, (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4), (_ptr(ws), nbytes, _stream(zh)))
+
+
+def _call_masked(entry: str, args, mask, mstride: int, lo: int) -> None:
+    """``entry``, or ``entry_masked`` with the planes of the outcomes from ``lo`` on (single-model family: two entry points)."""
+    if mask is None:
+        call(entry, *args)
+    else:
+        call(entry + "_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
+
+
+def _row_pitched(t: torch.Tensor, Nh: int, Nt: int) -> bool:
+    """[L, Nh, Nt] contiguous, or a view of row-padded storage (``empty_scores``): unit inner stride and one pitch for every row."""
+    return t.numel() == 0 or (t.stride(2) == 1 and t.stride(1) >= Nt and t.stride(0) == Nh * t.stride(1))
+
+
+def _topk_k(k) -> None:
+    max_k = bilinear_topk_max_k()
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
+        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
+
+
+_TOPK_OUT = (("vals", torch.float32, float("-inf")), ("idx", torch.int32, -1))          # (name, dtype, padding) of a per-row top-k's results
+
+
+def _topk_out_shapes(out, kinds, shape) -> None:
+    """The caller's ``out`` of a per-row top-k, on whatever device it lives: one contiguous tensor of ``shape`` per entry of ``kinds``."""
+    if out is None:
+        return
+    if not (isinstance(out, (tuple, list)) and len(out) == len(kinds)):
+        raise ValueError(f"out: expected a ({', '.join(name for name, _, _ in kinds)}) tuple")
+    for n, (t, (name, dt, _)) in enumerate(zip(out, kinds)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError(f"out[{n}] ({name}): expected a contiguous {dt} tensor of shape {shape}")
+
+
+def _topk_results(out, kinds, shape, Nt: int, device):
+    """The result tensors of a per-row top-k -- fresh, or the ``out`` that passed ``_topk_out_shapes`` -- on ``device`` ->
+    (tensors, done); done: nothing is left to sweep (no entry, or no column at all: every row is padding, written here)."""
+    if out is None:
+        res = tuple(torch.empty(shape, dtype=dt, device=device) for _, dt, _ in kinds)
+    else:
+        res = tuple(out)
+        for n, t in enumerate(res):
+            if not (t.is_cuda and t.device == device):
+                raise ValueError(f"out[{n}] ({kinds[n][0]}): must live on the device of the embeddings ({device})")
+    if res[0].numel() and Nt == 0:
+        for t, (_, _, pad) in zip(res, kinds):
+            t.fill_(pad)
+    return res, res[0].numel() == 0 or Nt == 0
+
+
+def _edges_arg(edges: torch.Tensor, L: int, Nt: int, z_tail: str) -> int:
+    """``edges`` [L, B] of the counting sweeps, on whatever device they live: their number, the ``z_tail`` rows the 32-bit counters
+    hold, finite and ascending values -> B."""
+    B, max_edges = edges.shape[1], bilinear_bincount_max_edges()
+    if edges.shape[0] != L:
+        raise ValueError(f"edges: expected [{L}, B] (one row per outcome), got {tuple(edges.shape)}")
+    if not 1 <= B <= max_edges:
+        raise ValueError(f"edges: expected 1..{max_edges} edges per outcome, got {B}")
+    if Nt >= 1 << 23:
+        raise ValueError(f"{z_tail}: {Nt} rows; the 32-bit workgroup counters hold fewer than 2^23")
+    if L and not bool(torch.isfinite(edges).all()):
+        raise ValueError("edges: must be finite")
+    if L and not bool((edges[:, 1:] >= edges[:, :-1]).all()):
+        raise ValueError("edges: must be ascending within every outcome (unsorted edges give unspecified counts)")
+    return B
+
+
+def _bincount_call(entry: str, e, counts, mask, mstride: int, Nh: int, Nt: int, D: int, prec: int, eligible: str):
+    """``one_call`` of ``_head_calls`` / ``_ensemble_calls`` for the counting sweep ``entry`` over the edges ``e`` [L, B] into
+    ``counts`` [L, B+1], or with a ``mask`` ``entry_split`` into ``counts`` [2, L, B+1]."""
+    L, B = e.shape
+
+    def one_call(lo, n, operands, scratch):
+        sizes = (Nh, Nt, n, D, B, prec, TOPK_ELIGIBLE[eligible])
+        if mask is None:
+            call(entry, *operands, e.data_ptr() + lo * B * 4, counts.data_ptr() + lo * (B + 1) * 8, *sizes, *scratch)
+            return
+        part = counts if n == L else torch.empty((2, n, B + 1), dtype=torch.int64, device=e.device)   # [2][this call's outcomes]
+        call(entry + "_split", *operands, e.data_ptr() + lo * B * 4, _ptr(part), *sizes, *scratch, mask.data_ptr() + lo * mstride * 4, mstride)
+        if part is not counts:
+            counts[:, lo:lo + n] = part
+
+    return one_call
+
+
+_SELECT_NAN = "thresholds: NaN (use -inf to select every eligible pair, +inf to select none)"
+
+
+def _cuts_own(thresholds, scale):
+    return ((thresholds, "thresholds", 1),) + (() if scale is None else ((scale, "scale", 1),))
+
+
+def _cuts_arg(thresholds, scale, L: int, Nt: int, z_tail: str, w_sym: str, nan_check_on_device: bool, one_call: bool) -> None:
+    """``thresholds`` [L] of the selecting sweeps (and the profile's ``scale`` [L]; ``one_call``: its limit of outcomes), on whatever
+    device they live.  ``nan_check_on_device=False``: the caller reads the NaN flag of GPU thresholds itself, together with another
+    value (one synchronisation instead of two), or leaves it to the library."""
+    if one_call and L > 65535:
+        raise ValueError(f"{w_sym}: {L} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
+    if thresholds.shape[0] != L:
+        raise ValueError(f"thresholds: expected [{L}] (one cut per outcome), got {tuple(thresholds.shape)}")
+    if scale is not None and scale.shape[0] != L:
+        raise ValueError(f"scale: expected a float32 tensor [{L}] (one per outcome)")
+    if Nt >= (1 << 31) - 64:
+        raise ValueError(f"{z_tail}: {Nt} rows do not fit the int32 column indices")
+    if L and (nan_check_on_device or not thresholds.is_cuda) and bool(torch.isnan(thresholds).any()):
+        raise ValueError(_SELECT_NAN)
+
+
+def _select_counts(L: int, Nh: int, Nt: int, device, out=None):
+    """int32 [L, Nh] for a counting sweep, fresh or the caller's ``out`` -> (counts, done); done: nothing is left to sweep (no entry,
+    or no column at all: zeros, written here)."""
+    if out is None:
+        out = torch.empty((L, Nh), dtype=torch.int32, device=device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == torch.int32
+              and tuple(out.shape) == (L, Nh) and out.is_contiguous()):
+        raise ValueError(f"out: expected a contiguous int32 GPU tensor of shape {(L, Nh)}")
+    if out.numel() and Nt == 0:
+        out.zero_()
+    return out, out.numel() == 0 or Nt == 0
+
+
+def _select_csr(what: str, counts: torch.Tensor, thr: torch.Tensor, max_bytes: int, fill):
+    """From the counting sweep's ``counts`` [L, Nh] to the CSR of a selection: ``torch.cumsum``, the one host read -- the total ``T``
+    and the NaN flag of the thresholds with it --, the ``max_bytes`` refusal, the allocation, and ``fill(row_ptr, cols, vals)``, the
+    filling sweep, where anything was selected -> (row_ptr, cols, vals)."""
+    dev = counts.device
+    row_ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
+    T = 0
+    if counts.shape[0]:
+        row_ptr[1:] = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+        T, bad = torch.stack([row_ptr[-1], torch.isnan(thr).any().to(torch.int64)]).tolist()          # the one host read
+        if bad:
+            raise ValueError(_SELECT_NAN)
+    if 8 * T > int(max_bytes):
+        raise ValueError(f"{what}: T = {T} selected pairs need {8 * T} bytes, more than max_bytes = {int(max_bytes)}; "
+                         "raise the thresholds, pass fewer outcomes per call, or raise max_bytes")
+    cols = torch.empty(T, dtype=torch.int32, device=dev)
+    vals = torch.empty(T, dtype=torch.float32, device=dev)
+    if T:
+        fill(row_ptr, cols, vals)
+    return row_ptr, cols, vals
+
+
 def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tensor, *, precision="bf16x3",
                       epilogue: int = EPI_STORE, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """All-pairs scores S[l,i,j] = z_head[i]^T W_sym[l] z_tail[j]  -> [L,Nh,Nt] fp32
@@ -118,74 +312,37 @@ def bilinear_allpairs(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
         out_dtype = out.dtype if (isinstance(out, torch.Tensor) and out.dtype in SCORE_TYPES) else torch.float32
     if out_dtype != torch.float32 and out_dtype not in SCORE_TYPES:
         raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
-    if out_dtype in SCORE_TYPES:
-        return _bilinear_allpairs16(z_head, z_tail, w_sym, precision, epilogue, out_dtype, out)
-    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
-    D = zh.shape[1]
-    if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
-        raise ValueError(f"feature dims disagree: z_head {tuple(zh.shape)}, z_tail {tuple(zt.shape)}, w {tuple(w.shape)}")
-    if zh.device != zt.device or zh.device != w.device:
-        raise ValueError("z_head, z_tail and w_sym must be on the same device")
-    L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
-    shape = (L, Nh, 2) if epilogue == EPI_ROWSTATS else (L, Nh, Nt)
-    out_dtype = torch.int32 if epilogue == EPI_TRIKEYS else torch.float32
-    if out is None:
-        out = empty_scores(L, Nh, Nt, zh.device).view(torch.int32) if epilogue == EPI_TRIKEYS else torch.empty(shape, dtype=torch.float32, device=zh.device)
-    else:
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == out_dtype):
-            raise ValueError(f"out: expected a {out_dtype} GPU tensor")
-        # contiguous, or a view of row-padded storage (empty_scores): unit inner stride and one pitch for every row
-        if tuple(out.shape) != shape or (out.numel() and (out.stride(2) != 1 or out.stride(1) < shape[2] or out.stride(0) != shape[1] * out.stride(1))):
-            raise ValueError(f"out: expected {shape}, contiguous or row-pitched (empty_scores), got {tuple(out.shape)} strides {tuple(out.stride())}")
-    ldo = out.stride(1) if out.numel() else shape[2]
-    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
-    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    # the grid's y extent caps one call at 65535 outcomes; chunk above that
-    for lo in range(0, max(L, 1), 65535):
-        hi = min(L, lo + 65535)
-        if hi <= lo:
-            break
-        ws, nbytes = _scratch("mdg_bilinear_allpairs_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
-        call("mdg_bilinear_allpairs_ld", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, out.data_ptr() + lo * out.stride(0) * 4, ldo, Nh, Nt,
-             hi - lo, D, prec, int(epilogue), _ptr(ws), nbytes, _stream(zh), what="mdg_bilinear_allpairs")
-    return out
-
-
-def _bilinear_allpairs16(z_head, z_tail, w_sym, precision, epilogue, out_dtype, out) -> torch.Tensor:
-    """The 16-bit destination of ``bilinear_allpairs`` (mdg_bilinear_allpairs16_ld)."""
-    if epilogue not in (EPI_STORE, EPI_STORE_SIGMOID):
+    narrow = out_dtype in SCORE_TYPES                       # the 16-bit destination (mdg_bilinear_allpairs16_ld)
+    if narrow and epilogue not in (EPI_STORE, EPI_STORE_SIGMOID):
         raise ValueError(f"out_dtype {out_dtype}: only EPI_STORE and EPI_STORE_SIGMOID have a 16-bit form (row statistics and "
                          "lower-triangle keys are fp32 / int32 products)")
-    if isinstance(out, torch.Tensor) and out.dtype != out_dtype:
+    if narrow and isinstance(out, torch.Tensor) and out.dtype != out_dtype:
         raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
-    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
-    D = zh.shape[1]
-    if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
-        raise ValueError(f"feature dims disagree: z_head {tuple(zh.shape)}, z_tail {tuple(zt.shape)}, w {tuple(w.shape)}")
-    if zh.device != zt.device or zh.device != w.device:
-        raise ValueError("z_head, z_tail and w_sym must be on the same device")
-    L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
-    shape = (L, Nh, Nt)
+    prec = _head_models(z_head, z_tail, w_sym, precision)
+    zh, zt, w = _head_on_gpu(z_head, z_tail, w_sym)
+    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
+    shape = (L, Nh, 2) if epilogue == EPI_ROWSTATS else (L, Nh, Nt)
+    if epilogue == EPI_TRIKEYS:
+        out_dtype = torch.int32
     if out is None:
-        out = empty_scores(L, Nh, Nt, zh.device, dtype=out_dtype)
-    else:
-        if not (isinstance(out, torch.Tensor) and out.is_cuda):
-            raise ValueError(f"out: expected a {out_dtype} GPU tensor")
-        # contiguous, or a view of row-padded storage (empty_scores): unit inner stride and one pitch for every row
-        if tuple(out.shape) != shape or (out.numel() and (out.stride(2) != 1 or out.stride(1) < Nt or out.stride(0) != Nh * out.stride(1))):
-            raise ValueError(f"out: expected {shape}, contiguous or row-pitched (empty_scores), got {tuple(out.shape)} strides {tuple(out.stride())}")
-    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
-    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    if not out.numel():
+        if narrow:
+            out = empty_scores(L, Nh, Nt, zh.device, dtype=out_dtype)
+        elif epilogue == EPI_TRIKEYS:
+            out = empty_scores(L, Nh, Nt, zh.device).view(torch.int32)
+        else:
+            out = torch.empty(shape, dtype=torch.float32, device=zh.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == out_dtype):
+        raise ValueError(f"out: expected a {out_dtype} GPU tensor")
+    elif tuple(out.shape) != shape or not _row_pitched(out, shape[1], shape[2]):
+        raise ValueError(f"out: expected {shape}, contiguous or row-pitched (empty_scores), got {tuple(out.shape)} strides {tuple(out.stride())}")
+    if narrow and not out.numel():
         return out
-    ldo = out.stride(1)
-    for lo in range(0, L, 65535):                          # the grid's y extent caps one call at 65535 outcomes
-        hi = min(L, lo + 65535)
-        ws, nbytes = _scratch("mdg_bilinear_allpairs_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
-        call("mdg_bilinear_allpairs16_ld", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, out.data_ptr() + lo * out.stride(0) * 2, ldo, Nh, Nt,
-             hi - lo, D, prec, int(epilogue), SCORE_TYPES[out_dtype], _ptr(ws), nbytes, _stream(zh))
+    ldo = out.stride(1) if out.numel() else shape[2]
+    # the two entry points share the workspace query; the 16-bit one takes the score type too, and its pointer steps in 2-byte elements
+    entry, what, elem, kind = (("mdg_bilinear_allpairs16_ld", "", 2, (SCORE_TYPES[out_dtype],)) if narrow else
+                               ("mdg_bilinear_allpairs_ld", "mdg_bilinear_allpairs", 4, ()))
+    _head_calls("allpairs", zh, zt, w, lambda lo, n, operands, scratch: call(
+        entry, *operands, out.data_ptr() + lo * out.stride(0) * elem, ldo, Nh, Nt, n, D, prec, int(epilogue), *kind, *scratch, what=what), prec)
     return out
 
 
@@ -317,49 +474,17 @@ def bilinear_topk(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Tenso
     ``exclude``: a mask from ``pair_mask`` (``[1, ...]`` shared by all outcomes or ``[L, ...]``, one plane per outcome): a pair
     whose bit is set is not eligible, on top of ``eligible`` -- the known interactions of a screening run.  The scores that remain
     and their order are those of the call without it."""
-    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
-    D = zh.shape[1]
-    if zt.shape[1] != D or w.shape[1] != D or w.shape[2] != D:
-        raise ValueError(f"feature dims disagree: z_head {tuple(zh.shape)}, z_tail {tuple(zt.shape)}, w {tuple(w.shape)}")
-    if zh.device != zt.device or zh.device != w.device:
-        raise ValueError("z_head, z_tail and w_sym must be on the same device")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
-    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
-    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    max_k = bilinear_topk_max_k()
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
-        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
-    L, Nh, Nt = w.shape[0], zh.shape[0], zt.shape[0]
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    prec = _head_models(z_head, z_tail, w_sym, precision, eligible)
+    _topk_k(k)
+    _topk_out_shapes(out, _TOPK_OUT, (w_sym.shape[0], z_head.shape[0], k))
+    zh, zt, w = _head_on_gpu(z_head, z_tail, w_sym)
+    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
     mask, mstride = _exclude_args(exclude, zh, Nh, Nt, L)
-    shape = (L, Nh, k)
-    if out is None:
-        vals = torch.empty(shape, dtype=torch.float32, device=zh.device)
-        idx = torch.empty(shape, dtype=torch.int32, device=zh.device)
-    else:
-        vals, idx = out
-        for t, dt, name in ((vals, torch.float32, "out[0]"), (idx, torch.int32, "out[1]")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"{name}: expected a contiguous {dt} GPU tensor of shape {shape}")
-    if vals.numel() == 0:
-        return vals, idx
-    if Nt == 0:                                  # no column at all: every row is padding
-        vals.fill_(float("-inf"))
-        idx.fill_(-1)
-        return vals, idx
-    # the grid's y extent caps one call at 65535 outcomes; chunk above that
-    for lo in range(0, L, 65535):
-        hi = min(L, lo + 65535)
-        ws, nbytes = _scratch("mdg_bilinear_topk_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec, int(k))
-        args = (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt,
-                hi - lo, D, prec, int(k), TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
-        if mask is None:
-            call("mdg_bilinear_topk", *args)
-        else:
-            call("mdg_bilinear_topk_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
+    (vals, idx), done = _topk_results(out, _TOPK_OUT, (L, Nh, k), Nt, zh.device)
+    if not done:
+        _head_calls("topk", zh, zt, w, lambda lo, n, operands, scratch: _call_masked("mdg_bilinear_topk", (
+            *operands, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, n, D, prec, int(k), TOPK_ELIGIBLE[eligible],
+            *scratch), mask, mstride, lo), prec, int(k))
     return vals, idx
 
 
@@ -384,111 +509,42 @@ def bilinear_bincount(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.T
     those whose bit is set (the known pairs); a bit of an ineligible pair changes nothing.  Nothing is excluded: ``result.sum(0)`` is
     the call without ``split``, exactly, in every precision."""
     # shapes and edge values first (on whatever device the tensors live), then the device: a bad call says what is wrong with it
-    for t, name, nd in ((z_head, "z_head", 2), (z_tail, "z_tail", 2), (w_sym, "w_sym", 3), (edges, "edges", 2)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
-            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
-    D = z_head.shape[1]
-    if z_tail.shape[1] != D or w_sym.shape[1] != D or w_sym.shape[2] != D:
-        raise ValueError(f"feature dims disagree: z_head {tuple(z_head.shape)}, z_tail {tuple(z_tail.shape)}, w {tuple(w_sym.shape)}")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
-    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
-    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    L, Nh, Nt, B = w_sym.shape[0], z_head.shape[0], z_tail.shape[0], edges.shape[1]
-    max_edges = bilinear_bincount_max_edges()
-    if edges.shape[0] != L:
-        raise ValueError(f"edges: expected [{L}, B] (one row per outcome), got {tuple(edges.shape)}")
-    if not 1 <= B <= max_edges:
-        raise ValueError(f"edges: expected 1..{max_edges} edges per outcome, got {B}")
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
-    if Nt >= 1 << 23:
-        raise ValueError(f"z_tail: {Nt} rows; the 32-bit workgroup counters hold fewer than 2^23")
-    if L and not bool(torch.isfinite(edges).all()):
-        raise ValueError("edges: must be finite")
-    if L and not bool((edges[:, 1:] >= edges[:, :-1]).all()):
-        raise ValueError("edges: must be ascending within every outcome (unsorted edges give unspecified counts)")
-    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
-    e = _f32_cuda(edges, "edges", 2)
-    if zh.device != zt.device or zh.device != w.device or zh.device != e.device:
-        raise ValueError("z_head, z_tail, w_sym and edges must be on the same device")
-    if split is not None:
-        mask, mstride = _exclude_args(split, zh, Nh, Nt, L)
-        counts = torch.empty((2, L, B + 1), dtype=torch.int64, device=zh.device)
-        for lo in range(0, L, 65535):
-            hi = min(L, lo + 65535)
-            part = counts if hi - lo == L else torch.empty((2, hi - lo, B + 1), dtype=torch.int64, device=zh.device)   # [2][this call's outcomes]
-            ws, nbytes = _scratch("mdg_bilinear_bincount_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, B, prec)
-            call("mdg_bilinear_bincount_split", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, e.data_ptr() + lo * B * 4, _ptr(part), Nh, Nt,
-                 hi - lo, D, B, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh), mask.data_ptr() + lo * mstride * 4, mstride)
-            if part is not counts:
-                counts[:, lo:hi] = part
-        return counts
-    counts = torch.empty((L, B + 1), dtype=torch.int64, device=zh.device)
-    # the grid's y extent caps one call at 65535 outcomes; chunk above that
-    for lo in range(0, L, 65535):
-        hi = min(L, lo + 65535)
-        ws, nbytes = _scratch("mdg_bilinear_bincount_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, B, prec)
-        call("mdg_bilinear_bincount", _ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, e.data_ptr() + lo * B * 4,
-             counts.data_ptr() + lo * (B + 1) * 8, Nh, Nt, hi - lo, D, B, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
+    own = (edges, "edges", 2)
+    prec = _head_models(z_head, z_tail, w_sym, precision, eligible, (own,))
+    L, Nh, Nt, D = w_sym.shape[0], z_head.shape[0], z_tail.shape[0], z_head.shape[1]
+    B = _edges_arg(edges, L, Nt, "z_tail")
+    zh, zt, w, e = _head_on_gpu(z_head, z_tail, w_sym, own)
+    mask, mstride = _exclude_args(split, zh, Nh, Nt, L)
+    counts = torch.empty((L, B + 1) if split is None else (2, L, B + 1), dtype=torch.int64, device=zh.device)
+    _head_calls("bincount", zh, zt, w, _bincount_call("mdg_bilinear_bincount", e, counts, mask, mstride, Nh, Nt, D, prec, eligible), B, prec)
     return counts
 
 
-_SELECT_NAN = "thresholds: NaN (use -inf to select every eligible pair, +inf to select none)"
-
-
-def _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=True):
-    """Validation shared by ``bilinear_select_count`` and ``bilinear_select``: shapes and threshold values first (on whatever device the
-    tensors live), then the device -> (zh, zt, w, thr, precision code).  ``nan_check_on_device=False``: the caller reads the NaN flag of
-    GPU thresholds itself, together with another value (one synchronisation instead of two)."""
-    for t, name, nd in ((z_head, "z_head", 2), (z_tail, "z_tail", 2), (w_sym, "w_sym", 3), (thresholds, "thresholds", 1)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
-            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+def _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=True, scale=None, one_call=False):
+    """Validation shared by ``bilinear_select_count``, ``bilinear_select`` and ``bilinear_profile`` (its ``scale`` and ``one_call``
+    limit): shapes and threshold values first (on whatever device the tensors live, ``_cuts_arg``), then the device -> (zh, zt, w,
+    thr, scale, precision code)."""
+    own = _cuts_own(thresholds, scale)
+    prec = _head_models(z_head, z_tail, w_sym, precision, eligible, own)
     forward_only(z_head, z_tail, w_sym, thresholds)
-    D = z_head.shape[1]
-    if z_tail.shape[1] != D or w_sym.shape[1] != D or w_sym.shape[2] != D:
-        raise ValueError(f"feature dims disagree: z_head {tuple(z_head.shape)}, z_tail {tuple(z_tail.shape)}, w {tuple(w_sym.shape)}")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
-    if isinstance(precision, str) and precision not in HEAD_PRECISIONS:
-        raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(HEAD_PRECISIONS)}")
-    prec = HEAD_PRECISIONS[precision] if isinstance(precision, str) else int(precision)
-    L, Nh, Nt = w_sym.shape[0], z_head.shape[0], z_tail.shape[0]
-    if thresholds.shape[0] != L:
-        raise ValueError(f"thresholds: expected [{L}] (one cut per outcome), got {tuple(thresholds.shape)}")
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
-    if Nt >= (1 << 31) - 64:
-        raise ValueError(f"z_tail: {Nt} rows do not fit the int32 column indices")
-    if L and (nan_check_on_device or not thresholds.is_cuda) and bool(torch.isnan(thresholds).any()):
-        raise ValueError(_SELECT_NAN)
-    zh, zt, w = _f32_cuda(z_head, "z_head", 2), _f32_cuda(z_tail, "z_tail", 2), _f32_cuda(w_sym, "w_sym", 3)
-    thr = _f32_cuda(thresholds, "thresholds", 1)
-    if zh.device != zt.device or zh.device != w.device or zh.device != thr.device:
-        raise ValueError("z_head, z_tail, w_sym and thresholds must be on the same device")
-    return zh, zt, w, thr, prec
+    _cuts_arg(thresholds, scale, w_sym.shape[0], z_tail.shape[0], "z_tail", "w_sym", nan_check_on_device, one_call)
+    zh, zt, w, thr, *sc = _head_on_gpu(z_head, z_tail, w_sym, *own)
+    return zh, zt, w, thr, (sc[0] if sc else None), prec
+
+
+def _select_sweep(entry, zh, zt, w, thr, prec, eligible, mask, mstride, outputs) -> None:
+    """One pass (``entry``: mdg_bilinear_select_count / _fill) over all outcomes.  ``outputs(lo)``: the pass's own pointer arguments
+    for the outcomes from ``lo`` on."""
+    Nh, Nt, D = zh.shape[0], zt.shape[0], zh.shape[1]
+    _head_calls("select", zh, zt, w, lambda lo, n, operands, scratch: _call_masked(entry, (
+        *operands, thr.data_ptr() + lo * 4, *outputs(lo), Nh, Nt, n, D, prec, TOPK_ELIGIBLE[eligible], *scratch), mask, mstride, lo), prec)
 
 
 def _select_count(zh, zt, w, thr, prec, eligible, mask=None, mstride=0) -> torch.Tensor:
-    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
-    counts = torch.empty((L, Nh), dtype=torch.int32, device=zh.device)
-    if counts.numel() == 0:
-        return counts
-    if Nt == 0:                                  # no column at all
-        return counts.zero_()
-    # the grid's y extent caps one call at 65535 outcomes; chunk above that
-    for lo in range(0, L, 65535):
-        hi = min(L, lo + 65535)
-        ws, nbytes = _scratch("mdg_bilinear_select_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
-        args = (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4, counts.data_ptr() + lo * Nh * 4, Nh, Nt, hi - lo, D,
-                prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
-        if mask is None:
-            call("mdg_bilinear_select_count", *args)
-        else:
-            call("mdg_bilinear_select_count_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
+    Nh = zh.shape[0]
+    counts, done = _select_counts(w.shape[0], Nh, zt.shape[0], zh.device)
+    if not done:
+        _select_sweep("mdg_bilinear_select_count", zh, zt, w, thr, prec, eligible, mask, mstride, lambda lo: (counts.data_ptr() + lo * Nh * 4,))
     return counts
 
 
@@ -500,7 +556,7 @@ def bilinear_select_count(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: tor
     ``-inf`` counts every eligible column, ``+inf`` none.  ``eligible`` and the score arithmetic are those of ``bilinear_topk``.
     ``exclude``: a mask from ``pair_mask`` (one plane or one per outcome); a pair whose bit is set is not counted.
     Deterministic: no atomics."""
-    zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision)
+    zh, zt, w, thr, _, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision)
     mask, mstride = _exclude_args(exclude, zh, zh.shape[0], zt.shape[0], w.shape[0])
     return _select_count(zh, zt, w, thr, prec, eligible, mask, mstride)
 
@@ -521,34 +577,12 @@ def bilinear_select(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Ten
 
     ``exclude``: a mask from ``pair_mask`` (one plane or one per outcome); a pair whose bit is set is not eligible, so the known
     network is neither counted nor stored.  What remains is what the call without it returns, minus those pairs."""
-    zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False)
-    L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
-    mask, mstride = _exclude_args(exclude, zh, Nh, Nt, L)
-    counts = _select_count(zh, zt, w, thr, prec, eligible, mask, mstride)          # (a NaN cut selects nothing: harmless until it is refused below)
-    row_ptr = torch.zeros(L * Nh + 1, dtype=torch.int64, device=zh.device)
-    T = 0
-    if L:
-        row_ptr[1:] = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
-        T, bad = torch.stack([row_ptr[-1], torch.isnan(thr).any().to(torch.int64)]).tolist()          # the one host read
-        if bad:
-            raise ValueError(_SELECT_NAN)
-    if 8 * T > int(max_bytes):
-        raise ValueError(f"bilinear_select: T = {T} selected pairs need {8 * T} bytes, more than max_bytes = {int(max_bytes)}; "
-                         "raise the thresholds, pass fewer outcomes per call, or raise max_bytes")
-    cols = torch.empty(T, dtype=torch.int32, device=zh.device)
-    vals = torch.empty(T, dtype=torch.float32, device=zh.device)
-    if T == 0:
-        return row_ptr, cols, vals
-    for lo in range(0, L, 65535):
-        hi = min(L, lo + 65535)
-        ws, nbytes = _scratch("mdg_bilinear_select_workspace_bytes", zh.device, Nh, Nt, hi - lo, D, prec)
-        args = (_ptr(zh), _ptr(zt), w.data_ptr() + lo * D * D * 4, thr.data_ptr() + lo * 4, row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols),
-                _ptr(vals), Nh, Nt, hi - lo, D, prec, TOPK_ELIGIBLE[eligible], _ptr(ws), nbytes, _stream(zh))
-        if mask is None:
-            call("mdg_bilinear_select_fill", *args)
-        else:
-            call("mdg_bilinear_select_fill_masked", *args, mask.data_ptr() + lo * mstride * 4, mstride)
-    return row_ptr, cols, vals
+    zh, zt, w, thr, _, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False)
+    Nh = zh.shape[0]
+    mask, mstride = _exclude_args(exclude, zh, Nh, zt.shape[0], w.shape[0])
+    counts = _select_count(zh, zt, w, thr, prec, eligible, mask, mstride)          # (a NaN cut selects nothing: harmless until it is refused)
+    return _select_csr("bilinear_select", counts, thr, max_bytes, lambda row_ptr, cols, vals: _select_sweep(
+        "mdg_bilinear_select_fill", zh, zt, w, thr, prec, eligible, mask, mstride, lambda lo: (row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols), _ptr(vals))))
 
 
 def _profile_out(out, Nh: int, Nt: int, device):
@@ -579,18 +613,9 @@ def bilinear_profile(z_head: torch.Tensor, z_tail: torch.Tensor, w_sym: torch.Te
     (``bilinear_allpairs``) bit for bit in all four precisions.  L <= 65535 per call: merge chunks with ``profile_merge``.
     ``out``: an optional (count, best, margin) triple to reuse, contiguous or with one common row pitch.  The values of
     ``thresholds`` and ``scale`` are checked by the library, which synchronises the stream once.  Deterministic: no atomics."""
-    if scale is not None and isinstance(w_sym, torch.Tensor) and w_sym.dim() == 3:           # shapes first, then the device
-        if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or tuple(scale.shape) != (w_sym.shape[0],):
-            raise ValueError(f"scale: expected a float32 tensor [{w_sym.shape[0]}] (one per outcome)")
-    zh, zt, w, thr, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False)
+    zh, zt, w, thr, sc, prec = _select_args(z_head, z_tail, w_sym, thresholds, eligible, precision, nan_check_on_device=False,
+                                            scale=scale, one_call=True)
     L, Nh, Nt, D = w.shape[0], zh.shape[0], zt.shape[0], zh.shape[1]
-    if L > 65535:
-        raise ValueError(f"w_sym: {L} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
-    sc = None
-    if scale is not None:
-        sc = _f32_cuda(scale, "scale", 1)
-        if sc.device != zh.device:
-            raise ValueError("scale must be on the device of z_head")
     res = _profile_out(out, Nh, Nt, zh.device)
     if Nh == 0 or Nt == 0:
         return res
@@ -758,20 +783,15 @@ def _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible="all", 
         raise ValueError(f"{what}: {K} z_heads, {len(zt)} z_tails, {len(ws)} w_syms")
     if precision not in ENSEMBLE_PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}; expected one of {sorted(ENSEMBLE_PRECISIONS)}")
-    if eligible not in TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(TOPK_ELIGIBLE)}")
     for t, name, nd in ((zh[0], "z_heads[0]", 2), (zt[0], "z_tails[0]", 2), (ws[0], "w_syms[0]", 3), *own):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != nd:
-            raise ValueError(f"{name}: expected a float32 tensor with {nd} dims, got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        _f32_dims(t, name, nd)
     L, D = ws[0].shape[0], ws[0].shape[1]
     Nh, Nt = zh[0].shape[0], zt[0].shape[0]
     for m in range(K):
         if tuple(zh[m].shape) != (Nh, D) or tuple(zt[m].shape) != (Nt, D) or tuple(ws[m].shape) != (L, D, D):
             raise ValueError(f"{what}: model {m} has z_head {tuple(zh[m].shape)}, z_tail {tuple(zt[m].shape)}, "
                              f"w_sym {tuple(ws[m].shape)}; model 0 has {(Nh, D)}, {(Nt, D)}, {(L, D, D)}")
-    if eligible != "all" and Nh != Nt:
-        raise ValueError(f"eligible={eligible!r} needs one drug set against itself (Nh {Nh} != Nt {Nt})")
+    _eligible_arg(eligible, Nh, Nt)
     return zh, zt, ws
 
 
@@ -835,7 +855,7 @@ def bilinear_ensemble_sigmoid(z_heads, z_tails, w_syms, *, precision="bf16x3", o
     if out is None:
         out = empty_scores(L, Nh, Nt, dev, dtype=out_dtype)
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == out_dtype and tuple(out.shape) == shape
-              and (out.numel() == 0 or (out.stride(2) == 1 and out.stride(1) >= Nt and out.stride(0) == Nh * out.stride(1)))):
+              and _row_pitched(out, Nh, Nt)):
         raise ValueError(f"out: expected a {str(out_dtype).replace('torch.', '')} GPU tensor {shape}, contiguous or row-pitched (empty_scores)")
     ldo = out.stride(1) if out.numel() else Nt
     prec = ENSEMBLE_PRECISIONS[precision]
@@ -867,32 +887,17 @@ def bilinear_ensemble_topk(z_heads, z_tails, w_syms, k: int, *, eligible: str = 
     ``k``, ``out`` and ``exclude`` as ``bilinear_topk``."""
     what = "bilinear_ensemble_topk"
     zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible)
-    max_k = bilinear_topk_max_k()
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
-        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
-    zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
+    _topk_k(k)
     L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
-    dev = zh[0].device
+    _topk_out_shapes(out, _TOPK_OUT, (L, Nh, k))
+    zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
     mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
-    shape = (L, Nh, k)
-    if out is None:
-        vals = torch.empty(shape, dtype=torch.float32, device=dev)
-        idx = torch.empty(shape, dtype=torch.int32, device=dev)
-    else:
-        vals, idx = out
-        for t, dt, name in ((vals, torch.float32, "out[0]"), (idx, torch.int32, "out[1]")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"{name}: expected a contiguous {dt} GPU tensor of shape {shape}")
-    if vals.numel() == 0:
-        return vals, idx
-    if Nt == 0:                                  # no column at all: every row is padding
-        vals.fill_(float("-inf"))
-        idx.fill_(-1)
-        return vals, idx
-    prec = ENSEMBLE_PRECISIONS[precision]
-    _ensemble_calls("topk", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
-        "mdg_bilinear_ensemble_topk", *models, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, n, D, prec, int(k),
-        TOPK_ELIGIBLE[eligible], *scratch, None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
+    (vals, idx), done = _topk_results(out, _TOPK_OUT, (L, Nh, k), Nt, zh[0].device)
+    if not done:
+        prec = ENSEMBLE_PRECISIONS[precision]
+        _ensemble_calls("topk", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+            "mdg_bilinear_ensemble_topk", *models, vals.data_ptr() + lo * Nh * k * 4, idx.data_ptr() + lo * Nh * k * 4, Nh, Nt, n, D, prec, int(k),
+            TOPK_ELIGIBLE[eligible], *scratch, None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
     return vals, idx
 
 
@@ -944,8 +949,7 @@ def bilinear_ensemble_spread(z_heads, z_tails, w_syms, *, kappa=None, precision=
     else:
         res = list(out)
         for t, name in zip(res, names):
-            if t is not None and not (t.is_cuda and t.device == dev and
-                                      (t.numel() == 0 or (t.stride(2) == 1 and t.stride(1) >= Nt and t.stride(0) == Nh * t.stride(1)))):
+            if t is not None and not (t.is_cuda and t.device == dev and _row_pitched(t, Nh, Nt)):
                 raise ValueError(f"out ({name}): expected a GPU tensor on {dev}, contiguous or row-pitched (empty_scores)")
     given = [t for t in res if t is not None]
     if given[0].numel() and any(t.stride(1) != given[0].stride(1) for t in given):
@@ -977,67 +981,39 @@ def bilinear_ensemble_spread_topk(z_heads, z_tails, w_syms, k: int, kappa, *, el
     ``exclude`` as ``bilinear_ensemble_topk``."""
     what = "bilinear_ensemble_spread_topk"
     zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible)
-    max_k = bilinear_topk_max_k()
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= max_k:
-        raise ValueError(f"k: expected an int in 1..{max_k}, got {k!r}")
+    _topk_k(k)
     kap = _kappa(kappa, what)
     L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
-    shape = (L, Nh, k)
-    kinds = ((torch.float32, "out[0] (bound)"), (torch.int32, "out[1] (idx)"), (torch.float32, "out[2] (mean)"), (torch.float32, "out[3] (std)"))
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 4):
-            raise ValueError("out: expected a (bound, idx, mean, std) tuple")
-        for t, (dt, name) in zip(out, kinds):
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {shape}")
+    nan = float("nan")
+    kinds = (("bound", torch.float32, float("-inf")), ("idx", torch.int32, -1), ("mean", torch.float32, nan), ("std", torch.float32, nan))
+    _topk_out_shapes(out, kinds, (L, Nh, k))
     zh, zt, ws = _ensemble_on_gpu(what, zh, zt, ws)
-    dev = zh[0].device
     mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
-    if out is None:
-        res = tuple(torch.empty(shape, dtype=dt, device=dev) for dt, _ in kinds)
-    else:
-        res = tuple(out)
-        for t, (_, name) in zip(res, kinds):
-            if not (t.is_cuda and t.device == dev):
-                raise ValueError(f"{name}: must live on the device of the embeddings ({dev})")
-    bound, idx, mean, std = res
-    if bound.numel() == 0:
-        return res
-    if Nt == 0:                                  # no column at all: every row is padding
-        bound.fill_(float("-inf"))
-        idx.fill_(-1)
-        mean.fill_(float("nan"))
-        std.fill_(float("nan"))
-        return res
-    prec = ENSEMBLE_PRECISIONS[precision]
-    step = Nh * k * 4
-    _ensemble_calls("spread", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
-        "mdg_bilinear_ensemble_spread_topk", *models, kap, bound.data_ptr() + lo * step, idx.data_ptr() + lo * step,
-        mean.data_ptr() + lo * step, std.data_ptr() + lo * step, Nh, Nt, n, D, prec, int(k), TOPK_ELIGIBLE[eligible], *scratch,
-        None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
+    res, done = _topk_results(out, kinds, (L, Nh, k), Nt, zh[0].device)
+    if not done:
+        bound, idx, mean, std = res
+        prec = ENSEMBLE_PRECISIONS[precision]
+        step = Nh * k * 4
+        _ensemble_calls("spread", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
+            "mdg_bilinear_ensemble_spread_topk", *models, kap, bound.data_ptr() + lo * step, idx.data_ptr() + lo * step,
+            mean.data_ptr() + lo * step, std.data_ptr() + lo * step, Nh, Nt, n, D, prec, int(k), TOPK_ELIGIBLE[eligible], *scratch,
+            None if mask is None else mask.data_ptr() + lo * mstride * 4, mstride))
     return res
 
 
-def _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=True):
-    """Validation shared by ``bilinear_ensemble_select_count``, ``bilinear_ensemble_select`` and ``bilinear_ensemble_profile``: the
-    lists, the names and the thresholds first (on whatever device the tensors live), then the device -> (zh, zt, ws, thr, precision
-    code).  ``nan_check_on_device=False``: the caller reads the NaN flag of GPU thresholds itself, together with another value."""
-    own = (thresholds, "thresholds", 1)
-    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible, (own,))
+def _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=True, scale=None, one_call=False):
+    """``_select_args`` of the ensemble, for ``bilinear_ensemble_select_count``, ``bilinear_ensemble_select`` and
+    ``bilinear_ensemble_profile`` -> (zh, zt, ws, thr, scale, precision code)."""
+    own = _cuts_own(thresholds, scale)
+    zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible, own)
     forward_only(*zh, *zt, *ws, thresholds)
-    L, Nt = ws[0].shape[0], zt[0].shape[0]
-    if thresholds.shape[0] != L:
-        raise ValueError(f"thresholds: expected [{L}] (one cut per outcome), got {tuple(thresholds.shape)}")
-    if Nt >= (1 << 31) - 64:
-        raise ValueError(f"z_tails: {Nt} rows do not fit the int32 column indices")
-    if L and (nan_check_on_device or not thresholds.is_cuda) and bool(torch.isnan(thresholds).any()):
-        raise ValueError(_SELECT_NAN)
-    return (*_ensemble_on_gpu(what, zh, zt, ws, own), ENSEMBLE_PRECISIONS[precision])
+    _cuts_arg(thresholds, scale, ws[0].shape[0], zt[0].shape[0], "z_tails", "w_syms", nan_check_on_device, one_call)
+    zh, zt, ws, thr, *sc = _ensemble_on_gpu(what, zh, zt, ws, *own)
+    return zh, zt, ws, thr, (sc[0] if sc else None), ENSEMBLE_PRECISIONS[precision]
 
 
 def _ensemble_select_sweep(entry, zh, zt, ws, thr, prec, eligible, mask, mstride, outputs) -> None:
-    """One pass (``entry``: mdg_bilinear_ensemble_select_count / _fill) over all outcomes.  ``outputs(lo)``: the pass's own pointer
-    arguments for the outcomes from ``lo`` on."""
+    """``_select_sweep`` of the ensemble (``entry``: mdg_bilinear_ensemble_select_count / _fill; one entry point, the mask optional)."""
     Nh, Nt, D = zh[0].shape[0], zt[0].shape[0], ws[0].shape[1]
     _ensemble_calls("select", zh, zt, ws, prec, lambda lo, n, models, scratch: call(
         entry, *models, thr.data_ptr() + lo * 4, *outputs(lo), Nh, Nt, n, D, prec, TOPK_ELIGIBLE[eligible], *scratch,
@@ -1045,20 +1021,11 @@ def _ensemble_select_sweep(entry, zh, zt, ws, thr, prec, eligible, mask, mstride
 
 
 def _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride, out=None) -> torch.Tensor:
-    L, Nh, Nt = ws[0].shape[0], zh[0].shape[0], zt[0].shape[0]
-    if out is None:
-        counts = torch.empty((L, Nh), dtype=torch.int32, device=zh[0].device)
-    else:
-        counts = out
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == zh[0].device and out.dtype == torch.int32
-                and tuple(out.shape) == (L, Nh) and out.is_contiguous()):
-            raise ValueError(f"out: expected a contiguous int32 GPU tensor of shape {(L, Nh)}")
-    if counts.numel() == 0:
-        return counts
-    if Nt == 0:                                  # no column at all
-        return counts.zero_()
-    _ensemble_select_sweep("mdg_bilinear_ensemble_select_count", zh, zt, ws, thr, prec, eligible, mask, mstride,
-                           lambda lo: (counts.data_ptr() + lo * Nh * 4,))
+    Nh = zh[0].shape[0]
+    counts, done = _select_counts(ws[0].shape[0], Nh, zt[0].shape[0], zh[0].device, out)
+    if not done:
+        _ensemble_select_sweep("mdg_bilinear_ensemble_select_count", zh, zt, ws, thr, prec, eligible, mask, mstride,
+                               lambda lo: (counts.data_ptr() + lo * Nh * 4,))
     return counts
 
 
@@ -1073,7 +1040,7 @@ def bilinear_ensemble_select_count(z_heads, z_tails, w_syms, thresholds: torch.T
     ``thresholds``: fp32 [L] probabilities, no NaN; ``-inf`` (or 0.0) counts every eligible column, ``+inf`` none.  ``eligible`` and
     ``exclude`` as ``bilinear_select_count``.  ``out``: optional contiguous int32 [L, Nh] GPU tensor; every entry is written, zeros
     included.  Deterministic: no atomics."""
-    zh, zt, ws, thr, prec = _ensemble_select_args("bilinear_ensemble_select_count", z_heads, z_tails, w_syms, thresholds, eligible, precision)
+    zh, zt, ws, thr, _, prec = _ensemble_select_args("bilinear_ensemble_select_count", z_heads, z_tails, w_syms, thresholds, eligible, precision)
     mask, mstride = _exclude_args(exclude, zh[0], zh[0].shape[0], zt[0].shape[0], ws[0].shape[0])
     return _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride, out)
 
@@ -1093,28 +1060,13 @@ def bilinear_ensemble_select(z_heads, z_tails, w_syms, thresholds: torch.Tensor,
     it (at saturated inputs many probabilities are exactly 1.0).  ``eligible``, ``max_bytes`` and ``exclude`` as ``bilinear_select``.
     Deterministic: no atomics; bit-identical from call to call."""
     what = "bilinear_ensemble_select"
-    zh, zt, ws, thr, prec = _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=False)
-    L, Nh, Nt = ws[0].shape[0], zh[0].shape[0], zt[0].shape[0]
-    dev = zh[0].device
-    mask, mstride = _exclude_args(exclude, zh[0], Nh, Nt, L)
-    counts = _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride)      # (a NaN cut selects nothing: harmless until it is refused below)
-    row_ptr = torch.zeros(L * Nh + 1, dtype=torch.int64, device=dev)
-    T = 0
-    if L:
-        row_ptr[1:] = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
-        T, bad = torch.stack([row_ptr[-1], torch.isnan(thr).any().to(torch.int64)]).tolist()          # the one host read
-        if bad:
-            raise ValueError(_SELECT_NAN)
-    if 8 * T > int(max_bytes):
-        raise ValueError(f"{what}: T = {T} selected pairs need {8 * T} bytes, more than max_bytes = {int(max_bytes)}; "
-                         "raise the thresholds, pass fewer outcomes per call, or raise max_bytes")
-    cols = torch.empty(T, dtype=torch.int32, device=dev)
-    vals = torch.empty(T, dtype=torch.float32, device=dev)
-    if T == 0:
-        return row_ptr, cols, vals
-    _ensemble_select_sweep("mdg_bilinear_ensemble_select_fill", zh, zt, ws, thr, prec, eligible, mask, mstride,
-                           lambda lo: (row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols), _ptr(vals)))
-    return row_ptr, cols, vals
+    zh, zt, ws, thr, _, prec = _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=False)
+    Nh = zh[0].shape[0]
+    mask, mstride = _exclude_args(exclude, zh[0], Nh, zt[0].shape[0], ws[0].shape[0])
+    counts = _ensemble_select_count(zh, zt, ws, thr, prec, eligible, mask, mstride)      # (a NaN cut selects nothing: harmless until it is refused)
+    return _select_csr(what, counts, thr, max_bytes, lambda row_ptr, cols, vals: _ensemble_select_sweep(
+        "mdg_bilinear_ensemble_select_fill", zh, zt, ws, thr, prec, eligible, mask, mstride,
+        lambda lo: (row_ptr.data_ptr() + lo * Nh * 8, _ptr(cols), _ptr(vals))))
 
 
 def bilinear_ensemble_bincount(z_heads, z_tails, w_syms, edges: torch.Tensor, *, eligible: str = "all", precision="bf16x3",
@@ -1141,41 +1093,17 @@ def bilinear_ensemble_bincount(z_heads, z_tails, w_syms, edges: torch.Tensor, *,
     own = (edges, "edges", 2)
     zh, zt, ws = _ensemble_models(what, z_heads, z_tails, w_syms, precision, eligible, (own,))
     forward_only(*zh, *zt, *ws, edges)
-    L, D, Nh, Nt, B = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0], edges.shape[1]
-    max_edges = bilinear_bincount_max_edges()
-    if edges.shape[0] != L:
-        raise ValueError(f"edges: expected [{L}, B] (one row per outcome), got {tuple(edges.shape)}")
-    if not 1 <= B <= max_edges:
-        raise ValueError(f"edges: expected 1..{max_edges} edges per outcome, got {B}")
-    if Nt >= 1 << 23:
-        raise ValueError(f"z_tails: {Nt} rows; the 32-bit workgroup counters hold fewer than 2^23")
-    if L and not bool(torch.isfinite(edges).all()):
-        raise ValueError("edges: must be finite")
-    if L and not bool((edges[:, 1:] >= edges[:, :-1]).all()):
-        raise ValueError("edges: must be ascending within every outcome (unsorted edges give unspecified counts)")
+    L, D, Nh, Nt = ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
+    B = _edges_arg(edges, L, Nt, "z_tails")
     zh, zt, ws, e = _ensemble_on_gpu(what, zh, zt, ws, own)
-    dev = zh[0].device
     prec = ENSEMBLE_PRECISIONS[precision]
     mask, mstride = _exclude_args(split, zh[0], Nh, Nt, L)
-    tables = () if split is None else (2,)
-    counts = torch.empty((*tables, L, B + 1), dtype=torch.int64, device=dev)
+    counts = torch.empty((L, B + 1) if split is None else (2, L, B + 1), dtype=torch.int64, device=zh[0].device)
     if counts.numel() == 0:
         return counts
     if Nh == 0 or Nt == 0:                       # no pair at all
         return counts.zero_()
-
-    def one_call(lo, n, models, scratch):
-        sizes = (Nh, Nt, n, D, B, prec, TOPK_ELIGIBLE[eligible])
-        if split is None:
-            call("mdg_bilinear_ensemble_bincount", *models, e.data_ptr() + lo * B * 4, counts.data_ptr() + lo * (B + 1) * 8, *sizes, *scratch)
-            return
-        part = counts if n == L else torch.empty((2, n, B + 1), dtype=torch.int64, device=dev)   # [2][this call's outcomes]
-        call("mdg_bilinear_ensemble_bincount_split", *models, e.data_ptr() + lo * B * 4, _ptr(part), *sizes, *scratch,
-             mask.data_ptr() + lo * mstride * 4, mstride)
-        if part is not counts:
-            counts[:, lo:lo + n] = part
-
-    _ensemble_calls("bincount", zh, zt, ws, prec, one_call)
+    _ensemble_calls("bincount", zh, zt, ws, prec, _bincount_call("mdg_bilinear_ensemble_bincount", e, counts, mask, mstride, Nh, Nt, D, prec, eligible))
     return counts
 
 
@@ -1204,24 +1132,10 @@ def bilinear_ensemble_profile(z_heads, z_tails, w_syms, thresholds: torch.Tensor
     what = "bilinear_ensemble_profile"
     if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 3):
         raise ValueError("out: expected a (count, best, margin) triple")
-    w0 = next(iter(w_syms), None) if isinstance(w_syms, (list, tuple)) else None
-    if isinstance(w0, torch.Tensor) and w0.dim() == 3:                                       # shapes first, then the device
-        if scale is not None and (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or tuple(scale.shape) != (w0.shape[0],)):
-            raise ValueError(f"scale: expected a float32 tensor [{w0.shape[0]}] (one per outcome)")
-        if w0.shape[0] > 65535:
-            raise ValueError(f"w_syms: {w0.shape[0]} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
-    zh, zt, ws, thr, prec = _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=False)
+    zh, zt, ws, thr, sc, prec = _ensemble_select_args(what, z_heads, z_tails, w_syms, thresholds, eligible, precision, nan_check_on_device=False,
+                                                      scale=scale, one_call=True)
     K, L, D, Nh, Nt = len(zh), ws[0].shape[0], ws[0].shape[1], zh[0].shape[0], zt[0].shape[0]
     dev = zh[0].device
-    if L > 65535:
-        raise ValueError(f"w_syms: {L} outcomes; one call takes at most 65535 (merge chunks with profile_merge)")
-    sc = None
-    if scale is not None:
-        if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or tuple(scale.shape) != (L,):
-            raise ValueError(f"scale: expected a float32 tensor [{L}] (one per outcome)")
-        sc = _f32_cuda(scale, "scale", 1)
-        if sc.device != dev:
-            raise ValueError("scale must be on the device of z_heads")
     res = _profile_out(out, Nh, Nt, dev)
     if Nh == 0 or Nt == 0:
         return res

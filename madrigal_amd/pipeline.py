@@ -96,8 +96,7 @@ def score_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int
     ``out`` a numpy array or ``np.memmap`` (the reference's destination, predict.py:410-429): outcome chunks
     of ``host_chunk`` are produced on the GPU and copied out through two pinned staging buffers."""
     dec = model.decoder
-    L_all = dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
-    lo, hi = (0, L_all) if label_range is None else label_range
+    lo, hi = (0, _n_outcomes(model)) if label_range is None else label_range
     N = z.shape[0]
     if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
@@ -165,8 +164,7 @@ def rank_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int]
     the ranks over them: half the head's store stream and no score tensor next to the rank tensor.  Bit-identical to
     ``ops.rank_normalize(score_all_pairs(...))``."""
     dec = model.decoder
-    L_all = dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
-    lo, hi = (0, L_all) if label_range is None else label_range
+    lo, hi = (0, _n_outcomes(model)) if label_range is None else label_range
     N = z.shape[0]
     if out is None:
         out = ops.empty_scores(hi - lo, N, N, z.device)
@@ -187,15 +185,6 @@ def rank_all_pairs(model, z: torch.Tensor, label_range: Optional[Tuple[int, int]
     return ops.rank_normalize(keys, max_workspace_bytes=max_workspace_bytes)
 
 
-def _outcomes(model, label_range) -> Tuple[int, int]:
-    dec = model.decoder
-    L_all = dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
-    lo, hi = (0, L_all) if label_range is None else label_range
-    if not (0 <= lo <= hi <= L_all):
-        raise ValueError(f"label_range {label_range} outside [0, {L_all}]")
-    return lo, hi
-
-
 def known_pairs_mask(N: int, heads, tails, labels=None, n_labels: Optional[int] = None, device=None) -> torch.Tensor:
     """Exclusion mask of the KNOWN interactions of one drug set, for the ``exclude=`` of the screening products below: the pairs
     {heads[q], tails[q]} (indices into z; any order, duplicates allowed) are taken out from both sides -- (h, t) and (t, h) --
@@ -208,21 +197,152 @@ def known_pairs_mask(N: int, heads, tails, labels=None, n_labels: Optional[int] 
     return ops.pair_mask(heads, tails, N, N, labels=labels, n_labels=n_labels, symmetric=True, device=device)
 
 
-def _exclusion(exclude, model) -> Optional[torch.Tensor]:
-    """``exclude`` of the screening products, checked against the head: one shared plane, or one plane per outcome of the WHOLE head
-    (the decoder slices those by the ``label_range`` of each call, like the weight)."""
-    if exclude is None:
-        return None
-    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 3:
-        raise ValueError("exclude: expected a mask from known_pairs_mask / ops.pair_mask")
-    if exclude.shape[0] not in (1, _n_outcomes(model)):
-        raise ValueError(f"exclude: {exclude.shape[0]} planes; expected 1 or one per outcome of the head ({_n_outcomes(model)})")
-    return exclude
-
-
 def _n_outcomes(model) -> int:
     dec = model.decoder
     return dec.parametrizations.weight.original.shape[0] if hasattr(dec, "parametrizations") else dec.weight.shape[0]
+
+
+def _mask3(mask, name: str):
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 3:
+        raise ValueError(f"{name}: expected a mask from known_pairs_mask / ops.pair_mask")
+    return mask
+
+
+def _planes(excl, s: int, e: int):
+    """The planes of outcomes [s, e) of an exclusion mask (a shared plane serves every range)."""
+    return None if excl is None else (excl if excl.shape[0] == 1 else excl[s:e])
+
+
+# ---- what scores all pairs of one drug set: one model, or a checkpoint ensemble.  Every screen below is written once, over a head ----
+class _Head:
+    """The sweeps of one drug set against itself, as the screen bodies (``_top_pairs`` ...) call them: ``N`` drugs on ``device``,
+    ``n_outcomes`` in the whole head, and per product one method over the outcomes [s, e) -- ``topk``, ``select_count``, ``select``,
+    ``bincount``, ``profile`` (of the drug slices ``rows`` x ``cols``, None = all) and ``dense_rows`` (the general sweep's values
+    [e - s, len(rows), N]), with the contracts of the ``ops`` wrappers they end in.  ``exclude`` / ``split`` arrive as
+    ``exclusion`` returned them and the head takes the planes of [s, e) itself.  ``scores``: what the values are called in messages.
+    Constructing a head looks at nothing: the operands are checked when a body first reads one of these attributes, which it does
+    after it has checked its own plain arguments, so a bad ``K`` is reported whatever is wrong with the embeddings."""
+    scores = "scores"
+
+    def outcomes(self, label_range) -> Tuple[int, int]:
+        lo, hi = (0, self.n_outcomes) if label_range is None else label_range
+        if not (0 <= lo <= hi <= self.n_outcomes):
+            raise ValueError(f"label_range {label_range} outside [0, {self.n_outcomes}]")
+        return lo, hi
+
+    def exclusion(self, mask, name: str = "exclude") -> Optional[torch.Tensor]:
+        """``exclude`` / ``known`` of the screens, checked against the head: one shared plane, or one plane per outcome of the WHOLE
+        head (sliced by the outcome range of each sweep, like the weight)."""
+        if mask is None:
+            return None
+        _mask3(mask, name)
+        if mask.shape[0] not in (1, self.n_outcomes):
+            raise ValueError(f"{name}: {mask.shape[0]} planes; expected 1 or one per outcome of the head ({self.n_outcomes})")
+        return mask
+
+
+class _ModelHead(_Head):
+    """One model and its embeddings ``z``: every product through ``model.decoder``'s methods, looked up at call time (the decoder
+    slices weight and mask planes by the range)."""
+
+    def __init__(self, model, z: torch.Tensor):
+        self.model, self.z, self.N, self.device = model, z, z.shape[0], z.device
+
+    n_outcomes = property(lambda self: _n_outcomes(self.model))
+
+    def topk(self, k, s, e, eligible, exclude):
+        return self.model.decoder.topk(self.z, self.z, k, (s, e), eligible=eligible, exclude=exclude)
+
+    def dense_rows(self, rows, s, e):
+        return self.model.decoder(self.z[rows].contiguous(), self.z, (s, e))
+
+    def select_count(self, thr, s, e, eligible, exclude):
+        return self.model.decoder.select_count(self.z, self.z, thr, (s, e), eligible=eligible, exclude=exclude)
+
+    def select(self, thr, s, e, eligible, max_bytes, exclude):
+        return self.model.decoder.select(self.z, self.z, thr, (s, e), eligible=eligible, max_bytes=max_bytes, exclude=exclude)
+
+    def bincount(self, edges, s, e, eligible, split):
+        return self.model.decoder.bincount(self.z, self.z, edges, (s, e), eligible=eligible, split=split)
+
+    def profile(self, rows, cols, thr, scale, s, e, eligible):
+        z = self.z
+        return self.model.decoder.profile(z if rows is None else z[rows], z if cols is None else z[cols], thr, scale, (s, e), eligible=eligible)
+
+
+class _EnsembleHead(_Head):
+    """Checkpoints ``models`` (``_ensemble_weight`` says what one may be) and their embeddings ``zs`` of the same drugs: every product
+    through ``ops.bilinear_ensemble_*`` on the W_sym slices, in the precision of ``models.precision(...)``.  ``what``: the public
+    function, for the messages."""
+    scores = "probs"
+
+    def __init__(self, models, zs, what: str):
+        self.models, self.zs, self.what = list(models), list(zs), what
+
+    def __getattr__(self, name):
+        """``ws`` (W_sym per checkpoint), ``n_outcomes``, ``N``, ``device``, ``prec``: set by the operand checks, at the first read of one."""
+        from .models import get_precision
+        if name not in ("ws", "n_outcomes", "N", "device", "prec"):
+            raise AttributeError(name)
+        zs, what = self.zs, self.what
+        K = len(self.models)
+        if not 1 <= K <= 8 or len(zs) != K:
+            raise ValueError(f"{what}: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
+        z0 = zs[0]
+        if not (isinstance(z0, torch.Tensor) and z0.is_cuda):
+            raise ValueError("zs: embeddings must be GPU tensors")
+        ws = [_ensemble_weight(m) for m in self.models]
+        for k in range(K):
+            if zs[k].shape != z0.shape or ws[k].shape[0] != ws[0].shape[0]:
+                raise ValueError(f"{what}: checkpoint {k} has z {tuple(zs[k].shape)} and {ws[k].shape[0]} outcomes; "
+                                 f"checkpoint 0 has {tuple(z0.shape)} and {ws[0].shape[0]}")
+        self.ws, self.n_outcomes, self.N, self.device, self.prec = ws, ws[0].shape[0], z0.shape[0], z0.device, get_precision()
+        return self.__dict__[name]
+
+    def w(self, s, e):
+        return [w[s:e] for w in self.ws]
+
+    def topk(self, k, s, e, eligible, exclude):
+        return ops.bilinear_ensemble_topk(self.zs, self.zs, self.w(s, e), k, eligible=eligible, precision=self.prec, exclude=_planes(exclude, s, e))
+
+    def dense_rows(self, rows, s, e):       # a row subset is not the tail object: the general sweep, bit for bit what the lists saw
+        return ops.bilinear_ensemble_sigmoid([z[rows] for z in self.zs], self.zs, self.w(s, e), precision=self.prec)
+
+    def select_count(self, thr, s, e, eligible, exclude):
+        return ops.bilinear_ensemble_select_count(self.zs, self.zs, self.w(s, e), thr, eligible=eligible, precision=self.prec,
+                                                  exclude=_planes(exclude, s, e))
+
+    def select(self, thr, s, e, eligible, max_bytes, exclude):
+        return ops.bilinear_ensemble_select(self.zs, self.zs, self.w(s, e), thr, eligible=eligible, precision=self.prec, max_bytes=max_bytes,
+                                            exclude=_planes(exclude, s, e))
+
+    def bincount(self, edges, s, e, eligible, split):
+        return ops.bilinear_ensemble_bincount(self.zs, self.zs, self.w(s, e), edges, eligible=eligible, precision=self.prec,
+                                              split=_planes(split, s, e))
+
+    def profile(self, rows, cols, thr, scale, s, e, eligible):
+        zh = self.zs if rows is None else [z[rows] for z in self.zs]
+        zt = self.zs if cols is None else [z[cols] for z in self.zs]
+        return ops.bilinear_ensemble_profile(zh, zt, self.w(s, e), thr, scale=scale, eligible=eligible, precision=self.prec)
+
+
+def _top_partners(head: _Head, k, label_range, drug_rows, max_temp_bytes, exclude):
+    lo, hi = head.outcomes(label_range)
+    N, dev = head.N, head.device
+    rows = _index(drug_rows, N, "drug_rows", dev)
+    excl = head.exclusion(exclude)
+    if rows is None:
+        return head.topk(k, lo, hi, "not_self", excl)
+    n = int(rows.numel())
+    vals = torch.empty((hi - lo, n, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((hi - lo, n, k), dtype=torch.int32, device=dev)
+    chunk = max(1, int(max_temp_bytes) // max(N * k * 8, 1))
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        v, i = head.topk(k, s, e, "not_self", excl)
+        vals[s - lo:e - lo] = v[:, rows]
+        idx[s - lo:e - lo] = i[:, rows]
+    return vals, idx
 
 
 @torch.no_grad()
@@ -241,22 +361,7 @@ def top_partners(model, z: torch.Tensor, k: int, label_range: Optional[Tuple[int
     for a drug with hundreds of known partners the lists would otherwise hold nothing else, and no post-filter can bring back
     what the sweep dropped.  A row with fewer than k partners left is padded.
     Multi-GPU: pass the outcome shard the rank owns as ``label_range``; no collective is involved."""
-    lo, hi = _outcomes(model, label_range)
-    N = z.shape[0]
-    rows = _index(drug_rows, N, "drug_rows", z.device)
-    excl = _exclusion(exclude, model)
-    if rows is None:
-        return model.decoder.topk(z, z, k, (lo, hi), eligible="not_self", exclude=excl)
-    n = int(rows.numel())
-    vals = torch.empty((hi - lo, n, k), dtype=torch.float32, device=z.device)
-    idx = torch.empty((hi - lo, n, k), dtype=torch.int32, device=z.device)
-    chunk = max(1, int(max_temp_bytes) // max(N * k * 8, 1))
-    for s in range(lo, hi, chunk):
-        e = min(hi, s + chunk)
-        v, i = model.decoder.topk(z, z, k, (s, e), eligible="not_self", exclude=excl)
-        vals[s - lo:e - lo] = v[:, rows]
-        idx[s - lo:e - lo] = i[:, rows]
-    return vals, idx
+    return _top_partners(_ModelHead(model, z), k, label_range, drug_rows, max_temp_bytes, exclude)
 
 
 @torch.no_grad()
@@ -335,6 +440,45 @@ def merge_row_candidates(vals: torch.Tensor, idx: torch.Tensor, K: int, rescore,
     return out_v, out_h, out_t
 
 
+def _positive_int(K, name: str = "K") -> None:
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"{name}: expected a positive int, got {K!r}")
+
+
+def _top_pairs(head: _Head, K, label_range, k_row, max_temp_bytes, info, exclude):
+    max_k = ops.bilinear_topk_max_k()
+    _positive_int(K)
+    k_row = min(K, 16) if k_row is None else k_row
+    if isinstance(k_row, bool) or not isinstance(k_row, int) or not 1 <= k_row <= max_k:
+        raise ValueError(f"k_row: expected an int in 1..{max_k}, got {k_row!r}")
+    lo, hi = head.outcomes(label_range)
+    N, dev = head.N, head.device
+    excl = head.exclusion(exclude)
+    out_v = torch.empty((hi - lo, K), dtype=torch.float32, device=dev)
+    out_h = torch.empty((hi - lo, K), dtype=torch.int64, device=dev)
+    out_t = torch.empty((hi - lo, K), dtype=torch.int64, device=dev)
+    opened = []
+    chunk = max(1, int(max_temp_bytes) // max(N * k_row * 48, 1))
+    for s in range(lo, hi, chunk):
+        e = min(hi, s + chunk)
+        vals, idx = head.topk(k_row, s, e, "lower", excl)
+        part = {}
+
+        def rescore(l, rows, s=s):
+            dense = head.dense_rows(rows, s + l, s + l + 1)[0]
+            if excl is not None:
+                dense.masked_fill_(ops.pair_mask_rows(excl, 0 if excl.shape[0] == 1 else s + l, rows, N), float("-inf"))
+            return dense
+
+        v, h, t = merge_row_candidates(vals, idx, K, rescore, part)
+        out_v[s - lo:e - lo], out_h[s - lo:e - lo], out_t[s - lo:e - lo] = v, h, t
+        opened += part["open_rows"]
+        del vals, idx, v, h, t
+    if info is not None:
+        info["open_rows"] = opened
+    return out_v, out_h, out_t
+
+
 @torch.no_grad()
 def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, int]] = None, k_row: Optional[int] = None,
               max_temp_bytes: int = 1 << 30, info: Optional[dict] = None, exclude: Optional[torch.Tensor] = None):
@@ -356,39 +500,18 @@ def top_pairs(model, z: torch.Tensor, K: int, label_range: Optional[Tuple[int, i
     ``exclude``: a ``known_pairs_mask``; the K best pairs NOT in it.  The row lists skip its pairs inside the sweep and the re-scored
     rows get -inf at their excluded columns (``ops.pair_mask_rows``), so the result is exact as before: a row is open under the
     same condition (removing columns only shortens what lies behind a row's last entry)."""
-    lo, hi = _outcomes(model, label_range)
-    N = z.shape[0]
-    max_k = ops.bilinear_topk_max_k()
-    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
-        raise ValueError(f"K: expected a positive int, got {K!r}")
-    k_row = min(K, 16) if k_row is None else k_row
-    if isinstance(k_row, bool) or not isinstance(k_row, int) or not 1 <= k_row <= max_k:
-        raise ValueError(f"k_row: expected an int in 1..{max_k}, got {k_row!r}")
-    dec = model.decoder
-    excl = _exclusion(exclude, model)
-    out_v = torch.empty((hi - lo, K), dtype=torch.float32, device=z.device)
-    out_h = torch.empty((hi - lo, K), dtype=torch.int64, device=z.device)
-    out_t = torch.empty((hi - lo, K), dtype=torch.int64, device=z.device)
-    opened = []
-    chunk = max(1, int(max_temp_bytes) // max(N * k_row * 48, 1))
-    for s in range(lo, hi, chunk):
-        e = min(hi, s + chunk)
-        vals, idx = dec.topk(z, z, k_row, (s, e), eligible="lower", exclude=excl)
-        part = {}
+    return _top_pairs(_ModelHead(model, z), K, label_range, k_row, max_temp_bytes, info, exclude)
 
-        def rescore(l, rows, s=s):
-            dense = dec(z[rows].contiguous(), z, (s + l, s + l + 1))[0]
-            if excl is not None:
-                dense.masked_fill_(ops.pair_mask_rows(excl, 0 if excl.shape[0] == 1 else s + l, rows, N), float("-inf"))
-            return dense
 
-        v, h, t = merge_row_candidates(vals, idx, K, rescore, part)
-        out_v[s - lo:e - lo], out_h[s - lo:e - lo], out_t[s - lo:e - lo] = v, h, t
-        opened += part["open_rows"]
-        del vals, idx, v, h, t
-    if info is not None:
-        info["open_rows"] = opened
-    return out_v, out_h, out_t
+def _score_histogram(head: _Head, edges, label_range, eligible, known):
+    split = head.exclusion(known, "known")
+    lo, hi = head.outcomes(label_range)
+    e = torch.as_tensor(edges, dtype=torch.float32, device=head.device)
+    if e.dim() == 1:
+        e = e[None, :].expand(hi - lo, -1)
+    if e.dim() != 2 or e.shape[0] != hi - lo:
+        raise ValueError(f"edges: expected [B] or [{hi - lo}, B], got {tuple(e.shape)}")
+    return head.bincount(e.contiguous(), lo, hi, eligible, split)
 
 
 @torch.no_grad()
@@ -404,15 +527,7 @@ def score_histogram(model, z: torch.Tensor, edges: torch.Tensor, label_range: Op
     pairs (``[1]``, bit set) counted separately; nothing is excluded, ``result.sum(0)`` is the histogram without ``known``
     (``auroc_bounds_from_counts`` reads this form).
     Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
-    lo, hi = _outcomes(model, label_range)
-    e = torch.as_tensor(edges, dtype=torch.float32, device=z.device)
-    if e.dim() == 1:
-        e = e[None, :].expand(hi - lo, -1)
-    if e.dim() != 2 or e.shape[0] != hi - lo:
-        raise ValueError(f"edges: expected [B] or [{hi - lo}, B], got {tuple(e.shape)}")
-    if known is None:
-        return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible)
-    return model.decoder.bincount(z, z, e.contiguous(), (lo, hi), eligible=eligible, split=_exclusion(known, model))
+    return _score_histogram(_ModelHead(model, z), edges, label_range, eligible, known)
 
 
 def _cuts(thresholds, n_out: int, device) -> torch.Tensor:
@@ -441,6 +556,25 @@ def csr_rows(row_ptr: torch.Tensor, n_head: int, total: Optional[int] = None):
     return rows // n_head, rows % n_head, rp[::n_head].clone()
 
 
+def _partner_counts(head: _Head, thresholds, label_range, exclude):
+    lo, hi = head.outcomes(label_range)
+    return head.select_count(_cuts(thresholds, hi - lo, head.device), lo, hi, "not_self", head.exclusion(exclude))
+
+
+def _select_above(head: _Head, thresholds, label_range, eligible, max_bytes, exclude):
+    lo, hi = head.outcomes(label_range)
+    return head.select(_cuts(thresholds, hi - lo, head.device), lo, hi, eligible, max_bytes, head.exclusion(exclude))
+
+
+def _pairs_above(head: _Head, thresholds, label_range, max_bytes, exclude):
+    row_ptr, cols, vals = _select_above(head, thresholds, label_range, "lower", max_bytes, exclude)
+    _, pair_head, offsets = csr_rows(row_ptr, head.N, total=int(cols.numel()))
+    if head.N == 0:
+        lo, hi = head.outcomes(label_range)
+        offsets = torch.zeros(hi - lo + 1, dtype=torch.int64, device=head.device)
+    return offsets, pair_head, cols.long(), vals
+
+
 @torch.no_grad()
 def partner_counts(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[int, int]] = None,
                    exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -449,9 +583,7 @@ def partner_counts(model, z: torch.Tensor, thresholds, label_range: Optional[Tup
     sweep (``decoder.select_count``, ``not_self`` mode) -- no [L', N, N] tensor at any N.  ``thresholds``: a number or [L'], no NaN.
     ``exclude``: a ``known_pairs_mask``; its pairs are not counted (the degree in the NOVEL predicted network).
     Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
-    lo, hi = _outcomes(model, label_range)
-    return model.decoder.select_count(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self",
-                                      exclude=_exclusion(exclude, model))
+    return _partner_counts(_ModelHead(model, z), thresholds, label_range, exclude)
 
 
 @torch.no_grad()
@@ -464,9 +596,7 @@ def partners_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tup
     S[l, i, j] and S[l, j, i] (equal up to the last bits).  The result's size is known only after the counting sweep: more than
     ``max_bytes`` (8 bytes per entry) raises a ValueError naming the size.  ``thresholds``: a number or [L'], no NaN.
     ``exclude``: a ``known_pairs_mask``; its pairs are neither counted nor stored."""
-    lo, hi = _outcomes(model, label_range)
-    return model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="not_self", max_bytes=max_bytes,
-                                exclude=_exclusion(exclude, model))
+    return _select_above(_ModelHead(model, z), thresholds, label_range, "not_self", max_bytes, exclude)
 
 
 @torch.no_grad()
@@ -489,13 +619,7 @@ def pairs_above(model, z: torch.Tensor, thresholds, label_range: Optional[Tuple[
     ``exclude``: a ``known_pairs_mask``; the known network is neither counted nor stored, so a cut low enough to be interesting
     returns (and sizes ``max_bytes`` by) the novel pairs alone.  Ranks stay those over ALL pairs (``normalized_ranks_of``).
     Multi-GPU: pass the rank's outcome shard as ``label_range``; no collective is involved."""
-    lo, hi = _outcomes(model, label_range)
-    row_ptr, cols, vals = model.decoder.select(z, z, _cuts(thresholds, hi - lo, z.device), (lo, hi), eligible="lower", max_bytes=max_bytes,
-                                               exclude=_exclusion(exclude, model))
-    _, head, offsets = csr_rows(row_ptr, z.shape[0], total=int(cols.numel()))
-    if z.shape[0] == 0:
-        offsets = torch.zeros(hi - lo + 1, dtype=torch.int64, device=z.device)
-    return offsets, head, cols.long(), vals
+    return _pairs_above(_ModelHead(model, z), thresholds, label_range, max_bytes, exclude)
 
 
 @torch.no_grad()
@@ -509,24 +633,18 @@ def count_below(model, z: torch.Tensor, scores: torch.Tensor, label_range: Optio
     ``known``: a ``known_pairs_mask`` -> int64 [2, L', Q]: the novel pairs (``[0]``) and the known pairs (``[1]``) below every query,
     counted separately in the same sweeps; ``result.sum(0)`` is the answer without ``known``.
     Multi-GPU: pass the rank's outcome shard as ``label_range``."""
-    return _count_below(model, z, scores, label_range, known)[0]
+    return _count_below(_ModelHead(model, z), scores, label_range, known)[0]
 
 
-def _count_below(model, z, scores, label_range, known):
+def _count_below(head: _Head, scores, label_range, known, name: Optional[str] = None):
     """``count_below`` -> (its result, the row sums of the first chunk's count table(s): the number of eligible pairs per outcome
-    [L'], or per class and outcome [2, L']; None when no sweep ran)."""
-    lo, hi = _outcomes(model, label_range)
-    s = torch.as_tensor(scores, dtype=torch.float32, device=z.device)
+    [L'], or per class and outcome [2, L']; None when no sweep ran).  ``name``: what the queries are called in messages."""
+    split = head.exclusion(known, "known")
+    lo, hi = head.outcomes(label_range)
+    s = torch.as_tensor(scores, dtype=torch.float32, device=head.device)
     if s.dim() != 2 or s.shape[0] != hi - lo:
-        raise ValueError(f"scores: expected [{hi - lo}, Q], got {tuple(s.shape)}")
-    split = _exclusion(known, model)
-
-    def counting(edges):
-        if split is None:
-            return model.decoder.bincount(z, z, edges, (lo, hi), eligible="lower")
-        return model.decoder.bincount(z, z, edges, (lo, hi), eligible="lower", split=split)
-
-    return _count_below_sweeps(counting, s, split is not None)
+        raise ValueError(f"{name or head.scores}: expected [{hi - lo}, Q], got {tuple(s.shape)}")
+    return _count_below_sweeps(lambda edges: head.bincount(edges, lo, hi, "lower", split), s, split is not None)
 
 
 def _count_below_sweeps(counting, s: torch.Tensor, split: bool):
@@ -585,6 +703,19 @@ def recovery_from_counts(less_all: torch.Tensor, less_known: torch.Tensor, total
     return {"selected": selected.contiguous(), "hits": hits.contiguous(), "precision": precision, "recall": recall, "enrichment": enrichment}
 
 
+def _need_known(known) -> None:
+    if known is None:
+        raise ValueError("known: expected a mask from known_pairs_mask")
+
+
+def _recovery_at_cuts(head: _Head, known, cuts, label_range):
+    _need_known(known)
+    less, totals = _count_below(head, cuts, label_range, known, "cuts")
+    if totals is None:                                          # no outcome or no cut: nothing was swept
+        totals = torch.zeros((2, less.shape[1]), dtype=torch.int64, device=less.device)
+    return recovery_from_counts(less[0] + less[1], less[1], (totals[0] + totals[1])[:, None], totals[1][:, None])
+
+
 @torch.no_grad()
 def recovery_at_cuts(model, z: torch.Tensor, known: torch.Tensor, cuts: torch.Tensor, label_range: Optional[Tuple[int, int]] = None) -> dict:
     """How well the ranking of ALL N (N - 1) / 2 pairs recovers the known network -> the dict of ``recovery_from_counts``, every entry
@@ -594,16 +725,7 @@ def recovery_at_cuts(model, z: torch.Tensor, known: torch.Tensor, cuts: torch.Te
     ``recovery_from_counts``; the number of known pairs per outcome is read from the same sweeps (the row sum of a count table is
     its class's size), so a per-outcome mask needs no side information.  A known pair is scored with the sweep's own arithmetic: it
     cannot fall on the wrong side of a cut taken from ``top_pairs`` / ``score_histogram``."""
-    lo, hi = _outcomes(model, label_range)
-    c = torch.as_tensor(cuts, dtype=torch.float32, device=z.device)
-    if c.dim() != 2 or c.shape[0] != hi - lo:
-        raise ValueError(f"cuts: expected [{hi - lo}, B], got {tuple(c.shape)}")
-    if _exclusion(known, model) is None:
-        raise ValueError("known: expected a mask from known_pairs_mask")
-    less, totals = _count_below(model, z, c, (lo, hi), known)
-    if totals is None:                                          # no outcome or no cut: nothing was swept
-        totals = torch.zeros((2, c.shape[0]), dtype=torch.int64, device=z.device)
-    return recovery_from_counts(less[0] + less[1], less[1], (totals[0] + totals[1])[:, None], totals[1][:, None])
+    return _recovery_at_cuts(_ModelHead(model, z), known, cuts, label_range)
 
 
 def auroc_bounds_from_counts(counts: torch.Tensor):
@@ -631,29 +753,67 @@ def auroc_bounds_from_counts(counts: torch.Tensor):
     return lower, upper
 
 
+def _auroc_bounds(head: _Head, known, edges, label_range):
+    _need_known(known)
+    return auroc_bounds_from_counts(_score_histogram(head, edges, label_range, "lower", known))
+
+
 @torch.no_grad()
 def auroc_bounds(model, z: torch.Tensor, known: torch.Tensor, edges: torch.Tensor, label_range: Optional[Tuple[int, int]] = None):
     """Per-outcome AUROC bounds of the model's ranking of ALL strict-lower-triangle pairs against the known network ->
     ``(lower, upper)`` float64 [L']: ``score_histogram(known=)`` followed by ``auroc_bounds_from_counts`` -- one sweep, no [L', N, N]
     tensor, no sampled negatives.  More (or better placed) ``edges`` tighten the interval; up to
     ``ops.bilinear_bincount_max_edges()`` per sweep."""
-    if _exclusion(known, model) is None:
-        raise ValueError("known: expected a mask from known_pairs_mask")
-    return auroc_bounds_from_counts(score_histogram(model, z, edges, label_range, eligible="lower", known=known))
+    return _auroc_bounds(_ModelHead(model, z), known, edges, label_range)
 
 
 PROFILE_CHUNK = 65535          # outcomes per call of the profile sweep (count and best share a register there)
 
 
-def _profile_chunks(model, z_head, z_tail, thr, scale, lo, hi, eligible, chunk):
-    """``decoder.profile`` over the outcomes [lo, hi) in chunks, merged -> (count, best, margin), ``best`` relative to ``lo``."""
+def _profile_chunks(head: _Head, rows, cols, thr, scale, lo, hi, eligible, chunk):
+    """``head.profile`` of the drug slices ``rows`` x ``cols`` over the outcomes [lo, hi) in chunks, merged -> (count, best, margin),
+    ``best`` relative to ``lo``."""
     res = None
     for s in range(lo, max(hi, lo + 1), chunk):
         e = min(hi, s + chunk)
-        part = model.decoder.profile(z_head, z_tail, thr[s - lo:e - lo], None if scale is None else scale[s - lo:e - lo], (s, e),
-                                     eligible=eligible)
+        part = head.profile(rows, cols, thr[s - lo:e - lo], None if scale is None else scale[s - lo:e - lo], s, e, eligible)
         res = part if res is None else ops.profile_merge(res, part, s - lo)
     return res
+
+
+def _outcome_profile(head: _Head, thresholds, scale, label_range, eligible, head_rows, chunk, exclude=None):
+    if eligible not in ops.TOPK_ELIGIBLE:
+        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(ops.TOPK_ELIGIBLE)}")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= PROFILE_CHUNK:
+        raise ValueError(f"chunk: expected an int in 1..{PROFILE_CHUNK}, got {chunk!r}")
+    excl = _shared_plane(exclude)
+    lo, hi = head.outcomes(label_range)
+    N, dev = head.N, head.device
+    thr = _cuts(thresholds, hi - lo, dev)
+    sc = None if scale is None else _cuts(scale, hi - lo, dev)
+    out = None                                  # the entries to blank afterwards
+    if head_rows is None:
+        r0, r1 = 0, N
+        count, best, margin = _profile_chunks(head, None, None, thr, sc, lo, hi, eligible, chunk)
+    else:
+        r0, r1 = head_rows
+        if not (0 <= r0 <= r1 <= N):
+            raise ValueError(f"head_rows {head_rows} outside [0, {N}]")
+        # a rectangle: the sweep runs in "all" mode and the block's self / upper entries are blanked here
+        count, best, margin = _profile_chunks(head, slice(r0, r1), None, thr, sc, lo, hi, "all", chunk)
+        if eligible != "all":
+            i = torch.arange(r0, r1, device=dev)[:, None]
+            j = torch.arange(N, device=dev)[None, :]
+            out = (j == i) if eligible == "not_self" else (j >= i)
+    if excl is not None:
+        known = ops.pair_mask_rows(excl, 0, torch.arange(r0, r1, device=dev), N)
+        out = known if out is None else (out | known)
+    if out is not None:
+        count = count.masked_fill(out, 0)
+        best = best.masked_fill(out, -1)
+        margin = margin.masked_fill(out, float("-inf"))
+    best = best.long()
+    return count, torch.where(best >= 0, best + lo, best), margin
 
 
 @torch.no_grad()
@@ -670,31 +830,7 @@ def outcome_profile(model, z: torch.Tensor, thresholds, scale=None, label_range:
     hold 0 / -1 / -inf.  ``head_rows`` = (r0, r1): only drugs [r0, r1) against all drugs, with the same eligibility in the
     coordinates of the full matrix; the row blocks concatenate to the full result (row sharding across ranks or over time).
     Multi-GPU over outcomes: pass the rank's shard as ``label_range`` and merge the shards with ``ops.profile_merge``."""
-    lo, hi = _outcomes(model, label_range)
-    if eligible not in ops.TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(ops.TOPK_ELIGIBLE)}")
-    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= PROFILE_CHUNK:
-        raise ValueError(f"chunk: expected an int in 1..{PROFILE_CHUNK}, got {chunk!r}")
-    thr = _cuts(thresholds, hi - lo, z.device)
-    sc = None if scale is None else _cuts(scale, hi - lo, z.device)
-    N = z.shape[0]
-    if head_rows is None:
-        count, best, margin = _profile_chunks(model, z, z, thr, sc, lo, hi, eligible, chunk)
-    else:
-        r0, r1 = head_rows
-        if not (0 <= r0 <= r1 <= N):
-            raise ValueError(f"head_rows {head_rows} outside [0, {N}]")
-        # a rectangle: the sweep runs in "all" mode and the block's self / upper entries are blanked here
-        count, best, margin = _profile_chunks(model, z[r0:r1], z, thr, sc, lo, hi, "all", chunk)
-        if eligible != "all":
-            i = torch.arange(r0, r1, device=z.device)[:, None]
-            j = torch.arange(N, device=z.device)[None, :]
-            out = (j == i) if eligible == "not_self" else (j >= i)
-            count = count.masked_fill(out, 0)
-            best = best.masked_fill(out, -1)
-            margin = margin.masked_fill(out, float("-inf"))
-    best = best.long()
-    return count, torch.where(best >= 0, best + lo, best), margin
+    return _outcome_profile(_ModelHead(model, z), thresholds, scale, label_range, eligible, head_rows, chunk)
 
 
 def _profile_keys(count: torch.Tensor, margin: torch.Tensor) -> torch.Tensor:
@@ -708,11 +844,7 @@ def _shared_plane(exclude) -> Optional[torch.Tensor]:
     """``exclude`` of the per-pair products: ONE plane from ``known_pairs_mask``, applied to the finished profile (exact, since a
     pair is excluded under every outcome or under none).  A plane per outcome would change the counts outcome by outcome, inside
     the sweep: out of scope."""
-    if exclude is None:
-        return None
-    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 3:
-        raise ValueError("exclude: expected a mask from known_pairs_mask / ops.pair_mask")
-    if exclude.shape[0] != 1:
+    if exclude is not None and _mask3(exclude, "exclude").shape[0] != 1:
         raise ValueError(f"exclude: {exclude.shape[0]} planes; the per-pair profiles take one shared plane (known_pairs_mask without "
                          f"labels) -- a plane per outcome changes the counts inside the sweep and is out of scope")
     return exclude
@@ -757,6 +889,16 @@ def _most_flagged(profile_block, N: int, K: int, lo: int, max_bytes: int, dev, e
     return out_c, out_h, out_t, out_b, out_m
 
 
+def _most_flagged_pairs(head: _Head, thresholds, K, scale, label_range, max_bytes, exclude):
+    excl = _shared_plane(exclude)
+    _positive_int(K)
+    lo, hi = head.outcomes(label_range)
+    thr = _cuts(thresholds, hi - lo, head.device)
+    sc = None if scale is None else _cuts(scale, hi - lo, head.device)
+    return _most_flagged(lambda r0, r1: _profile_chunks(head, slice(r0, r1), slice(0, r1), thr, sc, lo, hi, "all", PROFILE_CHUNK), head.N, K, lo,
+                         max_bytes, head.device, excl)
+
+
 @torch.no_grad()
 def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, label_range: Optional[Tuple[int, int]] = None,
                        max_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
@@ -769,14 +911,7 @@ def most_flagged_pairs(model, z: torch.Tensor, thresholds, K: int, scale=None, l
     runs at any N.  Exact: a tie at the K-th place is broken by (i, j) like every other.  ``exclude``: ONE shared plane from
     ``known_pairs_mask`` (no ``labels``); its pairs are left out of the ranking, so the result lists novel pairs only (a plane per
     outcome is refused: it would change the counts inside the sweep)."""
-    excl = _shared_plane(exclude)
-    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
-        raise ValueError(f"K: expected a positive int, got {K!r}")
-    lo, hi = _outcomes(model, label_range)
-    thr = _cuts(thresholds, hi - lo, z.device)
-    sc = None if scale is None else _cuts(scale, hi - lo, z.device)
-    return _most_flagged(lambda r0, r1: _profile_chunks(model, z[r0:r1], z[:r1], thr, sc, lo, hi, "all", PROFILE_CHUNK), z.shape[0], K, lo,
-                         max_bytes, z.device, excl)
+    return _most_flagged_pairs(_ModelHead(model, z), thresholds, K, scale, label_range, max_bytes, exclude)
 
 
 # ---- per-pair highest outcomes of a rank or score tensor, streamed (ops.outcome_topk) ----
@@ -913,9 +1048,10 @@ def highest_outcomes(model, z: torch.Tensor, k: int = 5, *, of: str = "ranks", k
         raise ValueError(f"of: expected 'ranks' or 'scores', got {of!r}")
     if of == "ranks" and (scale is not None or shift is not None):
         raise ValueError("shift / scale apply to of='scores' (normalised ranks are comparable across outcomes as they are)")
-    lo, hi = _outcomes(model, label_range)
-    N, dev = z.shape[0], z.device
-    lab = _kept_labels(keep, _n_outcomes(model), lo, hi)
+    head = _ModelHead(model, z)
+    lo, hi = head.outcomes(label_range)
+    N, dev = head.N, head.device
+    lab = _kept_labels(keep, head.n_outcomes, lo, hi)
     sh = None if shift is None else _cuts(shift, hi - lo, dev)
     sc = None if scale is None else _cuts(scale, hi - lo, dev)
     plane = N * ops.empty_scores(0, N, N, dev).stride(1) * 4 if N else 1
@@ -944,12 +1080,13 @@ def ensemble_highest_outcomes(models, zs, k: int = 5, *, keep=None, label_range:
     models, zs = list(models), list(zs)
     if not models or len(models) != len(zs):
         raise ValueError(f"ensemble_highest_outcomes: {len(models)} models and {len(zs)} embeddings")
-    lo, hi = _outcomes(models[0], label_range)
-    N, dev = zs[0].shape[0], zs[0].device
+    head = _ModelHead(models[0], zs[0])                   # the seeds are ranked one model at a time: the first one's head stands for all
+    lo, hi = head.outcomes(label_range)
+    N, dev = head.N, head.device
     for m, zz in zip(models, zs):
-        if _n_outcomes(m) != _n_outcomes(models[0]) or zz.shape[0] != N:
+        if _n_outcomes(m) != head.n_outcomes or zz.shape[0] != N:
             raise ValueError("ensemble_highest_outcomes: every seed needs the same outcomes and the same drugs")
-    lab = _kept_labels(keep, _n_outcomes(models[0]), lo, hi)
+    lab = _kept_labels(keep, head.n_outcomes, lo, hi)
     plane = N * ops.empty_scores(0, N, N, dev).stride(1) * 4 if N else 1
     chunk = max(1, min(max(hi - lo, 1), int(max_bytes) // ((len(models) + 2) * plane)))          # the seeds' ranks, their gmean, its ranks
     state = None
@@ -991,9 +1128,10 @@ def pair_ranks(model, z: torch.Tensor, heads, tails, label_range: Optional[Tuple
     ``top_pairs`` re-scores its open rows), in row and outcome chunks whose temporaries stay under ``max_temp_bytes``: in "f32" /
     "bf16x3" they are bit for bit what the counting sweep sees.  The ranks are ``normalized_ranks_of`` those scores (its tie rule
     applies).  Multi-GPU: pass the rank's outcome shard as ``label_range``."""
-    lo, hi = _outcomes(model, label_range)
-    N = z.shape[0]
-    h, t = _index(heads, N, "heads", z.device), _index(tails, N, "tails", z.device)
+    head = _ModelHead(model, z)
+    lo, hi = head.outcomes(label_range)
+    N = head.N
+    h, t = _index(heads, N, "heads", head.device), _index(tails, N, "tails", head.device)
     if h is None or t is None or h.numel() != t.numel():
         raise ValueError("heads / tails: two index lists of one length")
     if bool((h == t).any()):
@@ -1008,13 +1146,12 @@ def pair_ranks(model, z: torch.Tensor, heads, tails, label_range: Optional[Tuple
         for r0 in range(0, int(rows.numel()), rb):
             r1 = min(int(rows.numel()), r0 + rb)
             mine = ((where >= r0) & (where < r1)).nonzero()[:, 0]
-            zr = z[rows[r0:r1]].contiguous()
             for s in range(lo, hi, chunk):
                 e = min(hi, s + chunk)
-                dense = model.decoder(zr, z, (s, e))
+                dense = head.dense_rows(rows[r0:r1], s, e)
                 scores[s - lo:e - lo, mine] = dense[:, where[mine] - r0, small[mine]]
                 del dense
-    return scores, normalized_ranks_of(model, z, scores, (lo, hi))
+    return scores, ranks_from_counts(_count_below(head, scores, (lo, hi), None)[0], N)
 
 
 @torch.no_grad()
@@ -1073,7 +1210,6 @@ def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_ind
     the sweep (``ops.bilinear_ensemble_sigmoid``), bit for bit the fp32 tensor cast afterwards -- half the HBM and, with a host
     destination (a ``np.float16`` array or memmap; numpy has no bfloat16), half the PCIe and disk bytes: the staging buffers and
     copies are 16-bit too."""
-    from .models import get_precision
     if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"out_dtype: expected torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
     if isinstance(out, torch.Tensor):
@@ -1087,26 +1223,14 @@ def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_ind
             raise ValueError("out: expected a CUDA tensor, or a float32 / float16 numpy array or memmap")
         if out_dtype is not None and out_dtype != host_dtype:
             raise ValueError(f"out: dtype {out.dtype} does not match out_dtype {out_dtype}")
-    K = len(models)
-    if not 1 <= K <= 8 or len(zs) != K:
-        raise ValueError(f"ensemble_all_pairs: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
-    z0 = zs[0]
-    if not (isinstance(z0, torch.Tensor) and z0.is_cuda):
-        raise ValueError("zs: embeddings must be GPU tensors")
-    N, dev = z0.shape[0], z0.device
-    ws = [_ensemble_weight(m) for m in models]
-    L_all = ws[0].shape[0]
-    oi = _index(outcome_inds, L_all, "outcome_inds", dev)
+    head = _EnsembleHead(models, zs, "ensemble_all_pairs")
+    zs, ws, N, dev, prec = head.zs, head.ws, head.N, head.device, head.prec
+    oi = _index(outcome_inds, head.n_outcomes, "outcome_inds", dev)
     di = _index(drug_inds, N, "drug_inds", dev)
     d2 = _index(drug_2_inds, N, "drug_2_inds", dev)
-    for k in range(K):
-        if zs[k].shape != z0.shape or ws[k].shape[0] != L_all:
-            raise ValueError(f"ensemble_all_pairs: checkpoint {k} has z {tuple(zs[k].shape)} and {ws[k].shape[0]} outcomes; "
-                             f"checkpoint 0 has {tuple(z0.shape)} and {L_all}")
     heads = [z if di is None else z.index_select(0, di) for z in zs]
     tails = heads if d2 is None else [z.index_select(0, d2) for z in zs]
     wsel = ws if oi is None else [w.index_select(0, oi) for w in ws]
-    prec = get_precision()
     L, A, B = wsel[0].shape[0], heads[0].shape[0], tails[0].shape[0]
     if out is None or isinstance(out, torch.Tensor):
         return ops.bilinear_ensemble_sigmoid(heads, tails, wsel, precision=prec, out=out, out_dtype=out_dtype)
@@ -1141,43 +1265,6 @@ def ensemble_all_pairs(models, zs, drug_inds=None, drug_2_inds=None, outcome_ind
     return out
 
 
-def _ensemble_operands(models, zs, label_range, what: str):
-    """Checked operands of the ensemble screens -> (zs, W_sym slices [hi - lo,D,D] per checkpoint, lo, hi, L_all, precision)."""
-    from .models import get_precision
-    models, zs = list(models), list(zs)
-    K = len(models)
-    if not 1 <= K <= 8 or len(zs) != K:
-        raise ValueError(f"{what}: 1..8 models with one embedding matrix each, got {K} models and {len(zs)} embeddings")
-    z0 = zs[0]
-    if not (isinstance(z0, torch.Tensor) and z0.is_cuda):
-        raise ValueError("zs: embeddings must be GPU tensors")
-    ws = [_ensemble_weight(m) for m in models]
-    L_all = ws[0].shape[0]
-    for k in range(K):
-        if zs[k].shape != z0.shape or ws[k].shape[0] != L_all:
-            raise ValueError(f"{what}: checkpoint {k} has z {tuple(zs[k].shape)} and {ws[k].shape[0]} outcomes; "
-                             f"checkpoint 0 has {tuple(z0.shape)} and {L_all}")
-    lo, hi = (0, L_all) if label_range is None else label_range
-    if not (0 <= lo <= hi <= L_all):
-        raise ValueError(f"label_range {label_range} outside [0, {L_all}]")
-    return zs, [w[lo:hi] for w in ws], lo, hi, L_all, get_precision()
-
-
-def _ensemble_exclusion(exclude, L_all: int) -> Optional[torch.Tensor]:
-    if exclude is None:
-        return None
-    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 3:
-        raise ValueError("exclude: expected a mask from known_pairs_mask / ops.pair_mask")
-    if exclude.shape[0] not in (1, L_all):
-        raise ValueError(f"exclude: {exclude.shape[0]} planes; expected 1 or one per outcome of the head ({L_all})")
-    return exclude
-
-
-def _planes(excl, s: int, e: int):
-    """The planes of outcomes [s, e) of an exclusion mask (a shared plane serves every range)."""
-    return None if excl is None else (excl if excl.shape[0] == 1 else excl[s:e])
-
-
 @torch.no_grad()
 def ensemble_top_partners(models, zs, k: int, label_range: Optional[Tuple[int, int]] = None, drug_rows=None,
                           max_temp_bytes: int = 1 << 30, exclude: Optional[torch.Tensor] = None):
@@ -1191,23 +1278,7 @@ def ensemble_top_partners(models, zs, k: int, label_range: Optional[Tuple[int, i
     [N,128] embeddings of the same drugs.  ``label_range`` slices every checkpoint's W_sym; ``drug_rows``, ``max_temp_bytes`` and
     ``exclude`` as ``top_partners``.  Precision follows ``models.precision(...)``; P is bit for bit the general sweep's of
     ``ops.bilinear_ensemble_sigmoid``."""
-    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_top_partners")
-    N, dev = zs[0].shape[0], zs[0].device
-    rows = _index(drug_rows, N, "drug_rows", dev)
-    excl = _ensemble_exclusion(exclude, L_all)
-    if rows is None:
-        return ops.bilinear_ensemble_topk(zs, zs, ws, k, eligible="not_self", precision=prec, exclude=_planes(excl, lo, hi))
-    n = int(rows.numel())
-    vals = torch.empty((hi - lo, n, k), dtype=torch.float32, device=dev)
-    idx = torch.empty((hi - lo, n, k), dtype=torch.int32, device=dev)
-    chunk = max(1, int(max_temp_bytes) // max(N * k * 8, 1))
-    for s in range(lo, hi, chunk):
-        e = min(hi, s + chunk)
-        v, i = ops.bilinear_ensemble_topk(zs, zs, [w[s - lo:e - lo] for w in ws], k, eligible="not_self", precision=prec,
-                                          exclude=_planes(excl, s, e))
-        vals[s - lo:e - lo] = v[:, rows]
-        idx[s - lo:e - lo] = i[:, rows]
-    return vals, idx
+    return _top_partners(_EnsembleHead(models, zs, "ensemble_top_partners"), k, label_range, drug_rows, max_temp_bytes, exclude)
 
 
 @torch.no_grad()
@@ -1221,8 +1292,9 @@ def ensemble_spread_all_pairs(models, zs, label_range: Optional[Tuple[int, int]]
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``out`` as ``ops.bilinear_ensemble_spread``.  ``mean`` is bit
     for bit the general sweep's of ``ops.bilinear_ensemble_sigmoid``: (z_i W) z_j, not mirrored, so it is symmetric only up to
     rounding.  Precision follows ``models.precision(...)``."""
-    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_spread_all_pairs")
-    return ops.bilinear_ensemble_spread(zs, zs, ws, kappa=kappa, precision=prec, out=out)
+    head = _EnsembleHead(models, zs, "ensemble_spread_all_pairs")
+    lo, hi = head.outcomes(label_range)
+    return ops.bilinear_ensemble_spread(head.zs, head.zs, head.w(lo, hi), kappa=kappa, precision=head.prec, out=out)
 
 
 @torch.no_grad()
@@ -1238,11 +1310,12 @@ def ensemble_confident_partners(models, zs, k: int, kappa=-1.0, label_range: Opt
 
     ``models`` / ``zs`` / ``label_range`` / ``drug_rows`` / ``exclude`` as ``ensemble_top_partners``; ``eligible``: "not_self"
     (j != i), "lower" (j < i) or "all"."""
-    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_confident_partners")
-    N, dev = zs[0].shape[0], zs[0].device
-    rows = _index(drug_rows, N, "drug_rows", dev)
-    excl = _ensemble_exclusion(exclude, L_all)
-    res = ops.bilinear_ensemble_spread_topk(zs, zs, ws, k, kappa, eligible=eligible, precision=prec, exclude=_planes(excl, lo, hi))
+    head = _EnsembleHead(models, zs, "ensemble_confident_partners")
+    lo, hi = head.outcomes(label_range)
+    rows = _index(drug_rows, head.N, "drug_rows", head.device)
+    excl = head.exclusion(exclude)
+    res = ops.bilinear_ensemble_spread_topk(head.zs, head.zs, head.w(lo, hi), k, kappa, eligible=eligible, precision=head.prec,
+                                            exclude=_planes(excl, lo, hi))
     return res if rows is None else tuple(t[:, rows] for t in res)
 
 
@@ -1257,45 +1330,7 @@ def ensemble_top_pairs(models, zs, K: int, label_range: Optional[Tuple[int, int]
     re-scored probabilities are bit for bit what the lists saw -- merged by ``merge_row_candidates``.  Probabilities tie often (many
     round to exactly 1), so open rows are common with a small ``k_row``; the result stays exact.
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``max_temp_bytes``, ``info`` and ``exclude`` as ``top_pairs``."""
-    max_k = ops.bilinear_topk_max_k()
-    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
-        raise ValueError(f"K: expected a positive int, got {K!r}")
-    k_row = min(K, 16) if k_row is None else k_row
-    if isinstance(k_row, bool) or not isinstance(k_row, int) or not 1 <= k_row <= max_k:
-        raise ValueError(f"k_row: expected an int in 1..{max_k}, got {k_row!r}")
-    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, "ensemble_top_pairs")
-    N, dev = zs[0].shape[0], zs[0].device
-    excl = _ensemble_exclusion(exclude, L_all)
-    out_v = torch.empty((hi - lo, K), dtype=torch.float32, device=dev)
-    out_h = torch.empty((hi - lo, K), dtype=torch.int64, device=dev)
-    out_t = torch.empty((hi - lo, K), dtype=torch.int64, device=dev)
-    opened = []
-    chunk = max(1, int(max_temp_bytes) // max(N * k_row * 48, 1))
-    for s in range(lo, hi, chunk):
-        e = min(hi, s + chunk)
-        vals, idx = ops.bilinear_ensemble_topk(zs, zs, [w[s - lo:e - lo] for w in ws], k_row, eligible="lower", precision=prec,
-                                               exclude=_planes(excl, s, e))
-        part = {}
-
-        def rescore(l, rows, s=s):
-            ws_l = [w[s - lo + l:s - lo + l + 1] for w in ws]
-            dense = ops.bilinear_ensemble_sigmoid([z[rows] for z in zs], zs, ws_l, precision=prec)[0]
-            if excl is not None:
-                dense.masked_fill_(ops.pair_mask_rows(excl, 0 if excl.shape[0] == 1 else s + l, rows, N), float("-inf"))
-            return dense
-
-        v, h, t = merge_row_candidates(vals, idx, K, rescore, part)
-        out_v[s - lo:e - lo], out_h[s - lo:e - lo], out_t[s - lo:e - lo] = v, h, t
-        opened += part["open_rows"]
-        del vals, idx, v, h, t
-    if info is not None:
-        info["open_rows"] = opened
-    return out_v, out_h, out_t
-
-
-def _ensemble_select_operands(models, zs, thresholds, label_range, exclude, what: str):
-    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, what)
-    return zs, ws, _cuts(thresholds, hi - lo, zs[0].device), prec, _planes(_ensemble_exclusion(exclude, L_all), lo, hi), hi - lo
+    return _top_pairs(_EnsembleHead(models, zs, "ensemble_top_pairs"), K, label_range, k_row, max_temp_bytes, info, exclude)
 
 
 @torch.no_grad()
@@ -1311,8 +1346,7 @@ def ensemble_partner_counts(models, zs, thresholds, label_range: Optional[Tuple[
     the ensemble's probability needs no calibration per outcome, unlike a cut on one model's logit.  Normalised ranks under the
     ensemble: ``ensemble_normalized_ranks_of``.  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as
     ``partner_counts``; ``max_bytes`` is accepted for symmetry with ``ensemble_partners_above`` (the result is 4 L' N bytes)."""
-    zs, ws, thr, prec, excl, _ = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_partner_counts")
-    return ops.bilinear_ensemble_select_count(zs, zs, ws, thr, eligible="not_self", precision=prec, exclude=excl)
+    return _partner_counts(_EnsembleHead(models, zs, "ensemble_partner_counts"), thresholds, label_range, exclude)
 
 
 @torch.no_grad()
@@ -1329,8 +1363,7 @@ def ensemble_partners_above(models, zs, thresholds, label_range: Optional[Tuple[
     the rule is ``>=``, so ties with the K-th pair are included, and at saturated inputs many probabilities are exactly 1.0.
     Normalised ranks under the ensemble: ``ensemble_normalized_ranks_of``.  ``models`` / ``zs`` / ``label_range`` as
     ``ensemble_top_partners``; ``exclude`` as ``partners_above``."""
-    zs, ws, thr, prec, excl, _ = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_partners_above")
-    return ops.bilinear_ensemble_select(zs, zs, ws, thr, eligible="not_self", precision=prec, max_bytes=max_bytes, exclude=excl)
+    return _select_above(_EnsembleHead(models, zs, "ensemble_partners_above"), thresholds, label_range, "not_self", max_bytes, exclude)
 
 
 @torch.no_grad()
@@ -1352,34 +1385,7 @@ def ensemble_pairs_above(models, zs, thresholds, label_range: Optional[Tuple[int
         are exactly 1.0, so such a tie set can be large: ``max_bytes`` bounds it.
     The returned probabilities can go straight into ``ensemble_normalized_ranks_of`` (``normalized_ranks_of`` ranks one model's scores).
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``; ``exclude`` as ``pairs_above``."""
-    zs, ws, thr, prec, excl, n_out = _ensemble_select_operands(models, zs, thresholds, label_range, exclude, "ensemble_pairs_above")
-    row_ptr, cols, vals = ops.bilinear_ensemble_select(zs, zs, ws, thr, eligible="lower", precision=prec, max_bytes=max_bytes, exclude=excl)
-    N = zs[0].shape[0]
-    _, head, offsets = csr_rows(row_ptr, N, total=int(cols.numel()))
-    if N == 0:
-        offsets = torch.zeros(n_out + 1, dtype=torch.int64, device=zs[0].device)
-    return offsets, head, cols.long(), vals
-
-
-def _known_mask(known, required: bool) -> None:
-    """The cheap part of the check of ``known=``, ahead of the operands; ``_ensemble_exclusion`` checks the planes against the head."""
-    if known is None and not required:
-        return
-    if not isinstance(known, torch.Tensor) or known.dim() != 3:
-        raise ValueError("known: expected a mask from known_pairs_mask")
-
-
-def _ensemble_counting(models, zs, label_range, known, eligible: str, what: str):
-    """Checked operands of the ensemble's counting products -> (counting, n_out, device): ``counting(edges)`` is
-    ``ops.bilinear_ensemble_bincount`` of contiguous fp32 ``edges`` [L', B] over the outcomes of ``label_range``, int64 [L', B+1], or
-    [2, L', B+1] split by ``known``."""
-    zs, ws, lo, hi, L_all, prec = _ensemble_operands(models, zs, label_range, what)
-    split = _planes(_ensemble_exclusion(known, L_all), lo, hi)
-
-    def counting(edges):
-        return ops.bilinear_ensemble_bincount(zs, zs, ws, edges, eligible=eligible, precision=prec, split=split)
-
-    return counting, hi - lo, zs[0].device
+    return _pairs_above(_EnsembleHead(models, zs, "ensemble_pairs_above"), thresholds, label_range, max_bytes, exclude)
 
 
 @torch.no_grad()
@@ -1399,22 +1405,7 @@ def ensemble_score_histogram(models, zs, edges: torch.Tensor, label_range: Optio
     cumulative counts below such an edge are that pair's rank, the lowest of its tie group (``ensemble_normalized_ranks_of``; not
     ``ensemble_pair_ranks``, which is the geometric mean of per-model ranks).
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``.  Multi-GPU: pass the rank's outcome shard as ``label_range``."""
-    _known_mask(known, False)
-    counting, n_out, dev = _ensemble_counting(models, zs, label_range, known, eligible, "ensemble_score_histogram")
-    e = torch.as_tensor(edges, dtype=torch.float32, device=dev)
-    if e.dim() == 1:
-        e = e[None, :].expand(n_out, -1)
-    if e.dim() != 2 or e.shape[0] != n_out:
-        raise ValueError(f"edges: expected [B] or [{n_out}, B], got {tuple(e.shape)}")
-    return counting(e.contiguous())
-
-
-def _ensemble_count_below(models, zs, probs, label_range, known, what: str):
-    counting, n_out, dev = _ensemble_counting(models, zs, label_range, known, "lower", what)
-    s = torch.as_tensor(probs, dtype=torch.float32, device=dev)
-    if s.dim() != 2 or s.shape[0] != n_out:
-        raise ValueError(f"probs: expected [{n_out}, Q], got {tuple(s.shape)}")
-    return _count_below_sweeps(counting, s, known is not None)
+    return _score_histogram(_EnsembleHead(models, zs, "ensemble_score_histogram"), edges, label_range, eligible, known)
 
 
 @torch.no_grad()
@@ -1431,8 +1422,7 @@ def ensemble_count_below(models, zs, probs: torch.Tensor, label_range: Optional[
     is a different quantity, the geometric mean of every checkpoint's own rank of the pair.
     ``known``: a ``known_pairs_mask`` -> int64 [2, L', Q]: the novel (``[0]``) and the known pairs (``[1]``) below every query.
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``."""
-    _known_mask(known, False)
-    return _ensemble_count_below(models, zs, probs, label_range, known, "ensemble_count_below")[0]
+    return _count_below(_EnsembleHead(models, zs, "ensemble_count_below"), probs, label_range, known)[0]
 
 
 @torch.no_grad()
@@ -1461,11 +1451,7 @@ def ensemble_recovery_at_cuts(models, zs, known: torch.Tensor, cuts: torch.Tenso
     recall and enrichment over all N (N - 1) / 2 pairs, with no [L', N, N] tensor.  ``known``: a ``known_pairs_mask``; the class
     sizes are read from the same sweeps.  The rule is ``>=`` and ties are exact: a cut at 1.0 selects the whole saturated tie group.
     Cuts taken from ``ensemble_top_pairs`` / ``ensemble_pairs_above`` can be fed straight in (the same arithmetic, bit for bit)."""
-    _known_mask(known, True)
-    less, totals = _ensemble_count_below(models, zs, cuts, label_range, known, "ensemble_recovery_at_cuts")
-    if totals is None:                                          # no outcome or no cut: nothing was swept
-        totals = torch.zeros((2, less.shape[1]), dtype=torch.int64, device=less.device)
-    return recovery_from_counts(less[0] + less[1], less[1], (totals[0] + totals[1])[:, None], totals[1][:, None])
+    return _recovery_at_cuts(_EnsembleHead(models, zs, "ensemble_recovery_at_cuts"), known, cuts, label_range)
 
 
 @torch.no_grad()
@@ -1475,24 +1461,10 @@ def ensemble_auroc_bounds(models, zs, known: torch.Tensor, edges: torch.Tensor, 
     ``ensemble_score_histogram(known=)`` followed by ``auroc_bounds_from_counts`` -- one sweep, no sampled negatives.  Pairs that
     share a bin count towards the gap between the bounds; exactly tied probabilities (the saturated group at 1.0) share a bin
     whatever the edges, and the exact AUROC counts them 1/2, inside the interval."""
-    _known_mask(known, True)
-    return auroc_bounds_from_counts(ensemble_score_histogram(models, zs, edges, label_range, eligible="lower", known=known))
+    return _auroc_bounds(_EnsembleHead(models, zs, "ensemble_auroc_bounds"), known, edges, label_range)
 
 
 # ---- per-pair outcome profiles of the checkpoint ensemble (ops.bilinear_ensemble_profile) ----
-def _ensemble_profile_chunks(zh, zt, ws, thr, scale, eligible, chunk, prec):
-    """``ops.bilinear_ensemble_profile`` over the outcomes of ``ws`` in chunks, merged -> (count, best, margin), ``best`` relative to
-    the first outcome of ``ws``."""
-    L = ws[0].shape[0]
-    res = None
-    for s in range(0, max(L, 1), chunk):
-        e = min(L, s + chunk)
-        part = ops.bilinear_ensemble_profile(zh, zt, [w[s:e] for w in ws], thr[s:e], scale=None if scale is None else scale[s:e],
-                                             eligible=eligible, precision=prec)
-        res = part if res is None else ops.profile_merge(res, part, s)
-    return res
-
-
 @torch.no_grad()
 def ensemble_outcome_profile(models, zs, thresholds, scale=None, label_range: Optional[Tuple[int, int]] = None,
                              eligible: str = "not_self", head_rows: Optional[Tuple[int, int]] = None, chunk: int = PROFILE_CHUNK,
@@ -1511,38 +1483,7 @@ def ensemble_outcome_profile(models, zs, thresholds, scale=None, label_range: Op
     None, a positive number or [L'].  ``eligible`` and ``head_rows`` as ``outcome_profile``.  ``exclude``: ONE shared plane from
     ``known_pairs_mask`` (no ``labels``); its pairs are blanked to 0 / -1 / -inf like ineligible ones (a plane per outcome is
     refused: it would change the counts inside the sweep).  ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``."""
-    if eligible not in ops.TOPK_ELIGIBLE:
-        raise ValueError(f"unknown eligible {eligible!r}; expected one of {sorted(ops.TOPK_ELIGIBLE)}")
-    if isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= PROFILE_CHUNK:
-        raise ValueError(f"chunk: expected an int in 1..{PROFILE_CHUNK}, got {chunk!r}")
-    excl = _shared_plane(exclude)
-    zs, ws, lo, hi, _, prec = _ensemble_operands(models, zs, label_range, "ensemble_outcome_profile")
-    N, dev = zs[0].shape[0], zs[0].device
-    thr = _cuts(thresholds, hi - lo, dev)
-    sc = None if scale is None else _cuts(scale, hi - lo, dev)
-    out = None                                  # the entries to blank afterwards
-    if head_rows is None:
-        r0, r1 = 0, N
-        count, best, margin = _ensemble_profile_chunks(zs, zs, ws, thr, sc, eligible, chunk, prec)
-    else:
-        r0, r1 = head_rows
-        if not (0 <= r0 <= r1 <= N):
-            raise ValueError(f"head_rows {head_rows} outside [0, {N}]")
-        # a rectangle: the sweep runs in "all" mode and the block's self / upper entries are blanked here
-        count, best, margin = _ensemble_profile_chunks([z[r0:r1] for z in zs], zs, ws, thr, sc, "all", chunk, prec)
-        if eligible != "all":
-            i = torch.arange(r0, r1, device=dev)[:, None]
-            j = torch.arange(N, device=dev)[None, :]
-            out = (j == i) if eligible == "not_self" else (j >= i)
-    if excl is not None:
-        known = ops.pair_mask_rows(excl, 0, torch.arange(r0, r1, device=dev), N)
-        out = known if out is None else (out | known)
-    if out is not None:
-        count = count.masked_fill(out, 0)
-        best = best.masked_fill(out, -1)
-        margin = margin.masked_fill(out, float("-inf"))
-    best = best.long()
-    return count, torch.where(best >= 0, best + lo, best), margin
+    return _outcome_profile(_EnsembleHead(models, zs, "ensemble_outcome_profile"), thresholds, scale, label_range, eligible, head_rows, chunk, exclude)
 
 
 @torch.no_grad()
@@ -1555,15 +1496,4 @@ def ensemble_most_flagged_pairs(models, zs, thresholds, K: int, scale=None, labe
     tie rule at the K-th place are ``most_flagged_pairs``'s (one shared walk); no [N, N] and no [L', N, N] tensor, so it runs at
     any N.  ``exclude``: ONE shared plane from ``known_pairs_mask``; its pairs are left out of the ranking (novel pairs only).
     ``models`` / ``zs`` / ``label_range`` as ``ensemble_top_partners``."""
-    excl = _shared_plane(exclude)
-    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
-        raise ValueError(f"K: expected a positive int, got {K!r}")
-    zs, ws, lo, hi, _, prec = _ensemble_operands(models, zs, label_range, "ensemble_most_flagged_pairs")
-    N, dev = zs[0].shape[0], zs[0].device
-    thr = _cuts(thresholds, hi - lo, dev)
-    sc = None if scale is None else _cuts(scale, hi - lo, dev)
-
-    def block(r0, r1):
-        return _ensemble_profile_chunks([z[r0:r1] for z in zs], [z[:r1] for z in zs], ws, thr, sc, "all", PROFILE_CHUNK, prec)
-
-    return _most_flagged(block, N, K, lo, max_bytes, dev, excl)
+    return _most_flagged_pairs(_EnsembleHead(models, zs, "ensemble_most_flagged_pairs"), thresholds, K, scale, label_range, max_bytes, exclude)
